@@ -8,6 +8,8 @@ second-order) -> one all-reduce of the 2.455 MB flat gradient (N > 1) -> Adam.  
 at 4096 rays (BASELINE.json configs[3]/[4]) and split evenly over the ranks: strong scaling.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full     # + roofline, inference, configs[1] and CPU-baseline legs
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -18,6 +20,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -111,8 +114,8 @@ def main():
     ap.add_argument("--no-cfg2", action="store_true", help="skip the BASELINE configs[1] (256x512, bf16, 512 rays) leg (N = 1 only)")
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="capture forward+loss+backward (and Adam when N=1) in one HIP graph and replay it per step; auto = up "
-                         "to 2048 rays per GPU (eager fallback if capture fails); off: eager launches, per-launch HIP events "
-                         "inside the timed region")
+                         "to 2048 rays per GPU (eager fallback if capture fails); off: eager launches (with --full: per-launch "
+                         "HIP events inside the timed region)")
     ap.add_argument("--mlp-mode", choices=("fused", "fused_f16x2", "fused_f16x2_t32", "fused_bf16", "layerwise"),
                     default=os.environ.get("PN_MLP_MODE", DEFAULT_MODE),
                     help="fused_f16x2 (default): on-chip MLP chains, fp16 pairs with power-of-two scaling, 3 partial products "
@@ -127,6 +130,13 @@ def main():
                          "share of the CUs (on), or in line on the main stream, one batched job per layer (off)")
     ap.add_argument("--chain-wgs", type=int, default=None, help="--overlap on: workgroups (CUs) of a chain kernel while weight gradients run beside it")
     ap.add_argument("--wgrad-wgs", type=int, default=None, help="--overlap on: CUs of a weight-gradient job while a chain runs beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the per-kernel roofline (HIP events around every launch, inside the "
+                         "timed region or on eager steps after it), the full-panorama inference leg, the BASELINE configs[1] "
+                         "leg and the CPU baseline (--no-inference / --no-cfg2 / --no-cpu-baseline drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, fine-level colours, target colours, flat gradient, "
+                         "parameters after Adam) as DIR/<name>.npy (float32; rank 0's shard when N > 1)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -328,18 +338,25 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
-    _lib.load().pn_prof_enable(1)
+    # a plain run records no per-launch events; --full brackets every launch of the timed region with HIP events
+    prof_live = args.full and graph is None and n_streams == 1
+    if prof_live:
+        _lib.load().pn_prof_enable(1)
     t0 = time.perf_counter()
     # HIP events cannot be recorded inside a replayed graph, and with concurrent sub-batches a launch's wall duration
     # includes the other chain's share of the matrix cores: in both cases the roofline leg runs right after the region
-    prof_live = graph is None and n_streams == 1
-    if not prof_live:
-        _lib.load().pn_prof_enable(0)
     for i in range(args.steps):
         loss, pred, gt = step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
     used_graph = graph is not None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last run, before any measurement leg moves the model on
+        dump = {"loss": loss, "rgb_fine": pred, "rgb_target": gt, "flat_grad": state["last_g"],
+                "flat_params": model.mlp.flat_params()}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
     # audit trail of the data-parallel step: every rank's ray count and last loss, and the norm of the gradient block as it
     # stood after the last all-reduce (identical on all ranks by construction; rank 0 reports it)
     audit = {"rays_per_rank": [nb], "last_loss_per_rank": [float(loss)],
@@ -353,7 +370,7 @@ def main():
                  "allreduced_grad_l2_spread_over_ranks": float(max(r[2].item() for r in recs) - min(r[2].item() for r in recs))}
     prof = read_prof()
     _lib.load().pn_prof_enable(0)
-    if not prof_live:  # graph mode: measure the per-launch figures on eager steps right after the timed region
+    if args.full and not prof_live:  # graph mode: measure the per-launch figures on eager steps right after the timed region
         eager_graph, graph = graph, None
         state["streams"] = 1  # one chain: with concurrent sub-batches a launch's wall duration is not its cost
         step(args.warmup + args.steps)  # one untimed eager step first (the allocator and the caches settle after the replays)
@@ -367,7 +384,7 @@ def main():
         graph = None
     # the same kernels with the side stream off: per-launch durations without time-sharing (not part of `value`)
     iso = {}
-    if rank == 0 and args.overlap == "on":
+    if args.full and rank == 0 and args.overlap == "on":
         model.overlap_weight_grads = False
         step(args.warmup + args.steps, local=True)
         torch.cuda.synchronize()
@@ -391,49 +408,89 @@ def main():
     if not bool(torch.isfinite(loss)):  # a step that ran fast on garbage is not a measurement (seen once: see try_capture)
         raise RuntimeError(f"bench: non-finite loss {float(loss)} after the timed region on rank {rank}")
     if rank == 0:
-        dom = max(prof, key=lambda k: prof[k][0])
-        ms, n, fl = prof[dom]
-        avg_us = 1e3 * ms / max(n, 1)
-        achieved = fl / max(ms, 1e-9) / 1e9  # TFLOP/s  (FLOP / ms / 1e9)
-        # this path is priced against the MFMA roof.  `achieved` = the 16-bit matrix-core FLOP/s the kernel
-        # ISSUES (algorithmic 2 M N K FLOPs x partial products per fp32 product) against the dense 16-bit peak (2.5 PF);
-        # `algorithmic_tflops` = the fp32-equivalent figure (frac_algorithmic = that / 2.5 PF).  The HBM view of the same
-        # kernel (algorithmic operand bytes / duration against 8 TB/s) is kept as `roofline.hbm`.
-        prod = {3: 6.0, 2: 3.0, 1: 1.0}[np_] if dom.startswith("k_chain") else 1.0
-        peak_dom = PEAK_BF16_MFMA_TFLOPS if dom.startswith("k_chain") else PEAK_F32_MFMA_TFLOPS
-        roof_mfma = {"achieved": achieved * prod, "peak": peak_dom, "unit": "TFLOP/s", "frac": achieved * prod / peak_dom,
-                     "algorithmic_tflops": achieved, "frac_algorithmic": achieved / peak_dom,
-                     "partial_products_per_fp32_product": prod}
-        roof_hbm = None
-        if dom.startswith("k_chain_wgrad") and ", 2, 4, 4, 2," in dom:
-            # the 256 x 256 weight-gradient tile reads (256 ex + 256 ey) bytes per sample row for 2 * 256 * 256 FLOP: 4 bytes per
-            # element of an fp32 tensor, 3 of a Q24 tensor, 2 with bf16 tensors
-            esz = 2.0 if args.mlp_mode == "fused_bf16" else 4.0
-            ex, ey = (3.0 if dom.endswith("true, true>") else esz), (3.0 if dom.endswith("true>") else esz)
-            row_bytes = 256 * (ex + ey)
-            gbs = fl / (2.0 * 256 * 256) * row_bytes / max(ms, 1e-9) / 1e6  # algorithmic bytes / time, GB/s
-            roof_hbm = {"achieved": gbs, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBPS,
-                        "algorithmic_bytes_per_launch": fl / max(n, 1) / (2.0 * 256 * 256) * row_bytes}
-        bound = "mfma"  # this path is priced against the MFMA roof (top-level figure); `nearer_roof` says which roof
-        top = roof_mfma  # the dominant kernel is actually nearer to (the 256 x 256 weight-gradient tile: HBM)
-        nearer = "hbm" if (roof_hbm is not None and roof_hbm["frac"] > roof_mfma["frac"]) else "mfma"
-        traffic, pmc_tab, pmc_src = None, {}, None
-        for cand in (["r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"] if fused else ["r01_pmc_summary.json"]):
-            pmc = os.path.join(ROOT, "profiles", cand)
-            if os.path.exists(pmc):
-                try:
-                    pmc_tab = json.load(open(pmc))
-                    traffic = pmc_tab.get(dom, {}).get("hbm_bytes_per_launch")
-                    pmc_src = {"file": "profiles/" + cand, "taken_on": pmc_tab.get("_taken_on"), "note": pmc_tab.get("_note")}
-                    break
-                except Exception:
-                    traffic, pmc_tab, pmc_src = None, {}, None
+        roofline = None
+        if args.full:  # per-kernel figures of the dominant launch against the MFMA and HBM roofs
+            dom = max(prof, key=lambda k: prof[k][0])
+            ms, n, fl = prof[dom]
+            avg_us = 1e3 * ms / max(n, 1)
+            achieved = fl / max(ms, 1e-9) / 1e9  # TFLOP/s  (FLOP / ms / 1e9)
+            # this path is priced against the MFMA roof.  `achieved` = the 16-bit matrix-core FLOP/s the kernel
+            # ISSUES (algorithmic 2 M N K FLOPs x partial products per fp32 product) against the dense 16-bit peak (2.5 PF);
+            # `algorithmic_tflops` = the fp32-equivalent figure (frac_algorithmic = that / 2.5 PF).  The HBM view of the same
+            # kernel (algorithmic operand bytes / duration against 8 TB/s) is kept as `roofline.hbm`.
+            prod = {3: 6.0, 2: 3.0, 1: 1.0}[np_] if dom.startswith("k_chain") else 1.0
+            peak_dom = PEAK_BF16_MFMA_TFLOPS if dom.startswith("k_chain") else PEAK_F32_MFMA_TFLOPS
+            roof_mfma = {"achieved": achieved * prod, "peak": peak_dom, "unit": "TFLOP/s", "frac": achieved * prod / peak_dom,
+                         "algorithmic_tflops": achieved, "frac_algorithmic": achieved / peak_dom,
+                         "partial_products_per_fp32_product": prod}
+            roof_hbm = None
+            if dom.startswith("k_chain_wgrad") and ", 2, 4, 4, 2," in dom:
+                # the 256 x 256 weight-gradient tile reads (256 ex + 256 ey) bytes per sample row for 2 * 256 * 256 FLOP: 4 bytes per
+                # element of an fp32 tensor, 3 of a Q24 tensor, 2 with bf16 tensors
+                esz = 2.0 if args.mlp_mode == "fused_bf16" else 4.0
+                ex, ey = (3.0 if dom.endswith("true, true>") else esz), (3.0 if dom.endswith("true>") else esz)
+                row_bytes = 256 * (ex + ey)
+                gbs = fl / (2.0 * 256 * 256) * row_bytes / max(ms, 1e-9) / 1e6  # algorithmic bytes / time, GB/s
+                roof_hbm = {"achieved": gbs, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBPS,
+                            "algorithmic_bytes_per_launch": fl / max(n, 1) / (2.0 * 256 * 256) * row_bytes}
+            bound = "mfma"  # this path is priced against the MFMA roof (top-level figure); `nearer_roof` says which roof
+            top = roof_mfma  # the dominant kernel is actually nearer to (the 256 x 256 weight-gradient tile: HBM)
+            nearer = "hbm" if (roof_hbm is not None and roof_hbm["frac"] > roof_mfma["frac"]) else "mfma"
+            traffic, pmc_tab, pmc_src = None, {}, None
+            for cand in (["r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"] if fused else ["r01_pmc_summary.json"]):
+                pmc = os.path.join(ROOT, "profiles", cand)
+                if os.path.exists(pmc):
+                    try:
+                        pmc_tab = json.load(open(pmc))
+                        traffic = pmc_tab.get(dom, {}).get("hbm_bytes_per_launch")
+                        pmc_src = {"file": "profiles/" + cand, "taken_on": pmc_tab.get("_taken_on"), "note": pmc_tab.get("_note")}
+                        break
+                    except Exception:
+                        traffic, pmc_tab, pmc_src = None, {}, None
 
-        def hbm_rate(k, avg_us):
-            """HBM GB/s of kernel k: PMC bytes per launch (profiles/r02_pmc_summary.json, same workload) / live duration;
-            only at the profiled size (4096 rays on one GPU)."""
-            b = pmc_tab.get(k, {}).get("hbm_bytes_per_launch") if (world == 1 and args.global_batch == 4096) else None
-            return None if not b else b / max(avg_us, 1e-9) / 1e3
+            def hbm_rate(k, avg_us):
+                """HBM GB/s of kernel k: PMC bytes per launch (profiles/r02_pmc_summary.json, same workload) / live duration;
+                only at the profiled size (4096 rays on one GPU)."""
+                b = pmc_tab.get(k, {}).get("hbm_bytes_per_launch") if (world == 1 and args.global_batch == 4096) else None
+                return None if not b else b / max(avg_us, 1e-9) / 1e3
+            roofline = {"bound": bound, "nearer_roof": nearer, "kernel": dom, "achieved": top["achieved"],
+                        "peak": top["peak"],
+                        "unit": top["unit"], "frac": top["frac"],
+                        "mfma": roof_mfma, "hbm": roof_hbm,
+                        "traffic": traffic, "traffic_source": pmc_src,
+                        "avg_launch_us": avg_us, "launches": n,
+                        "measured": "HIP events around every GEMM launch " + ("during the timed region" if prof_live else
+                                    "on 3 eager single-chain steps (after one untimed) right after the timed region (events cannot be recorded "
+                                    "inside a replayed graph, and concurrent sub-batches time-share the matrix cores; same "
+                                    "kernels; with sub-batches the timed region's GEMMs have 1/streams of these rows)"),
+                        "note": ("timed region runs the weight-gradient GEMMs (k_gemm_tn) on a side stream, concurrently "
+                                 "with the k_gemm_nt chain: per-launch durations include time sharing; `isolated` = the "
+                                 "same kernels in 2 extra steps with the side stream off.  " if args.overlap == "on" else
+                                 "all launches on one stream (no time sharing between kernels).  ") +
+                                ("top-level `achieved` / `peak` / `frac` are the SURVEY.md 8(d) MFMA figure: 16-bit matrix-core "
+                                 "FLOP/s issued (algorithmic 2*M*N*K FLOPs per launch x partial products per fp32 product: six "
+                                 "for the bf16 three-term split, three for the fp16 pair) against the dense 16-bit MFMA peak "
+                                 "(2.5 PF); `mfma.algorithmic_tflops` is the fp32-equivalent rate; `hbm` is the same kernel's "
+                                 "algorithmic operand bytes against 8 TB/s; `other[*].tflops` are fp32-equivalent"
+                                 if args.mlp_mode in ("fused", "fused_f16x2", "fused_f16x2_t32") else
+                                 ("`peak` is the dense bf16 MFMA figure (2.5 PF)" if args.mlp_mode == "fused_bf16" else
+                                  "`peak` is the 2.4 GHz datasheet figure; under the power cap the same k_gemm_nt binary runs "
+                                  "126 TF on zero/constant operands and 101 TF on N(0,1) operands (tools/experiments/bench_clock.py, "
+                                  "profiles/r01_clock_vs_data.txt) and sustains a 2.10 GHz shader clock inside its K loop "
+                                  "(tools/experiments/trace_nt.py, profiles/r01_nt_phase_trace_K256.txt), i.e. 137.5 TF are available")),
+                        "isolated": iso,
+                        "flop_per_launch": fl / max(n, 1),
+                        "other": {k: {"total_ms": v[0], "launches": v[1], "avg_launch_us": 1e3 * v[0] / max(v[1], 1),
+                                      "tflops": v[2] / max(v[0], 1e-9) / 1e9,
+                                      "frac": v[2] / max(v[0], 1e-9) / 1e9 / peak_of(k),
+                                      "frac_is": "fp32-equivalent TFLOP/s over (2.5 PF / partial products) = issued 16-bit FLOP/s over 2.5 PF",
+                                      "hbm_gbs_from_pmc_traffic": hbm_rate(k, 1e3 * v[0] / max(v[1], 1))}
+                                  for k, v in prof.items()},
+                        "end_to_end_frac": value / world * flop_per_ray_step(args.samples) /
+                                           ((peak_chain if fused else PEAK_F32_MFMA_TFLOPS) * 1e12),
+                        "end_to_end_frac_is": "rays/s/GPU x 1.696 GFLOP (SURVEY.md 8d) x partial products / 2.5 PF",
+                        "end_to_end_frac_of_fp32_mfma_peak": value / world * flop_per_ray_step(args.samples) /
+                                                             (PEAK_F32_MFMA_TFLOPS * 1e12)}
         out = {
             "metric": "rays/sec (train step)", "value": value, "unit": "rays/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -477,47 +534,11 @@ def main():
                                     if fused else
                                     ("split: x = h + m + l (bf16), six partial products on v_mfma_f32_32x32x16_bf16, fp32 "
                                      "accumulate; weight gradients on fp32 MFMA" if split else "exact fp32 MFMA")},
-            "roofline": {"bound": bound, "nearer_roof": nearer, "kernel": dom, "achieved": top["achieved"],
-                         "peak": top["peak"],
-                         "unit": top["unit"], "frac": top["frac"],
-                         "mfma": roof_mfma, "hbm": roof_hbm,
-                         "traffic": traffic, "traffic_source": pmc_src,
-                         "avg_launch_us": avg_us, "launches": n,
-                         "measured": "HIP events around every GEMM launch " + ("during the timed region" if prof_live else
-                                     "on 3 eager single-chain steps (after one untimed) right after the timed region (events cannot be recorded "
-                                     "inside a replayed graph, and concurrent sub-batches time-share the matrix cores; same "
-                                     "kernels; with sub-batches the timed region's GEMMs have 1/streams of these rows)"),
-                         "note": ("timed region runs the weight-gradient GEMMs (k_gemm_tn) on a side stream, concurrently "
-                                  "with the k_gemm_nt chain: per-launch durations include time sharing; `isolated` = the "
-                                  "same kernels in 2 extra steps with the side stream off.  " if args.overlap == "on" else
-                                  "all launches on one stream (no time sharing between kernels).  ") +
-                                 ("top-level `achieved` / `peak` / `frac` are the SURVEY.md 8(d) MFMA figure: 16-bit matrix-core "
-                                  "FLOP/s issued (algorithmic 2*M*N*K FLOPs per launch x partial products per fp32 product: six "
-                                  "for the bf16 three-term split, three for the fp16 pair) against the dense 16-bit MFMA peak "
-                                  "(2.5 PF); `mfma.algorithmic_tflops` is the fp32-equivalent rate; `hbm` is the same kernel's "
-                                  "algorithmic operand bytes against 8 TB/s; `other[*].tflops` are fp32-equivalent"
-                                  if args.mlp_mode in ("fused", "fused_f16x2", "fused_f16x2_t32") else
-                                  ("`peak` is the dense bf16 MFMA figure (2.5 PF)" if args.mlp_mode == "fused_bf16" else
-                                   "`peak` is the 2.4 GHz datasheet figure; under the power cap the same k_gemm_nt binary runs "
-                                   "126 TF on zero/constant operands and 101 TF on N(0,1) operands (tools/experiments/bench_clock.py, "
-                                   "profiles/r01_clock_vs_data.txt) and sustains a 2.10 GHz shader clock inside its K loop "
-                                   "(tools/experiments/trace_nt.py, profiles/r01_nt_phase_trace_K256.txt), i.e. 137.5 TF are available")),
-                         "isolated": iso,
-                         "flop_per_launch": fl / max(n, 1),
-                         "other": {k: {"total_ms": v[0], "launches": v[1], "avg_launch_us": 1e3 * v[0] / max(v[1], 1),
-                                       "tflops": v[2] / max(v[0], 1e-9) / 1e9,
-                                       "frac": v[2] / max(v[0], 1e-9) / 1e9 / peak_of(k),
-                                       "frac_is": "fp32-equivalent TFLOP/s over (2.5 PF / partial products) = issued 16-bit FLOP/s over 2.5 PF",
-                                       "hbm_gbs_from_pmc_traffic": hbm_rate(k, 1e3 * v[0] / max(v[1], 1))}
-                                   for k, v in prof.items()},
-                         "end_to_end_frac": value / world * flop_per_ray_step(args.samples) /
-                                            ((peak_chain if fused else PEAK_F32_MFMA_TFLOPS) * 1e12),
-                         "end_to_end_frac_is": "rays/s/GPU x 1.696 GFLOP (SURVEY.md 8d) x partial products / 2.5 PF",
-                         "end_to_end_frac_of_fp32_mfma_peak": value / world * flop_per_ray_step(args.samples) /
-                                                              (PEAK_F32_MFMA_TFLOPS * 1e12)},
-            "psnr_batch_db": psnr, "loss": float(loss),
         }
-        if world == 1 and not args.no_inference:
+        if roofline is not None:
+            out["roofline"] = roofline
+        out.update({"psnr_batch_db": psnr, "loss": float(loss)})
+        if args.full and world == 1 and not args.no_inference:
             # inference rays/s for one full panorama: the first camera's H x W rays through render_image
             # (normals + env light + surface shading, 32768-ray chunks), after the timed training region
             hw = args.height * args.width
@@ -569,7 +590,7 @@ def main():
                         "launches (the module's default); `graph_replay_per_chunk` = the same loop with "
                         "model.replay_inference = True (a HIP graph captured once per chunk size inside the module, render.py "
                         "_replayed: six input copies + one graph launch + ten output clones per call)"}
-        if world == 1 and not args.no_cfg2:
+        if args.full and world == 1 and not args.no_cfg2:
             # BASELINE.json configs[1] (panonerf.yaml, 256x512 pano, 128 samples, bf16) on this GPU, after the timed region
             # and outside `value`: its own 3-camera 256x512 pool, a fresh model in plain-bf16 arithmetic, 512-ray batches
             # (configs/panonerf.yaml:4), 5 timed eager steps after 2 warm-up steps
@@ -693,7 +714,7 @@ def main():
                                                                      "frac": v[2] / max(v[0], 1e-9) / 1e9 / PEAK_BF16_MFMA_TFLOPS}
                                                                  for k, v in prof2.items()}}}}
             del m2, opt2, pool2
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             k = args.cpu_rays
             rays_k, gt_k = ray_pool.take(torch.arange(0, k * 997, 997, device=dev) % n_pool)
             rays_cpu = pn.Rays(*[x.cpu() for x in rays_k])

@@ -1,21 +1,66 @@
-"""The zero-edit integration route of INTEGRATION.md: with the reference checkout and this repository on sys.path and
+"""The zero-edit integration route of INTEGRATION.md: with the upstream tree and this repository on sys.path and
 `pano_nerf_amd.install()` called, every module that systems/base_system.py:1-6 and systems/panonerf_system.py:2-11 import
-resolves — the two model modules to the MI355X classes, everything else to the reference's own code.  Runs in a
-subprocess (it rearranges sys.path / sys.modules) and only where the reference checkout exists (the build container)."""
+resolves — the two model modules to the MI355X classes, everything else to the upstream tree's own code.  The upstream tree is
+a stand-in written from tests/golden/dropin_layout.json (its packages and modules, what the two systems import from them, the
+keyword arguments base_system.py builds the model with; tests/golden/make_dropin_golden.py).  Runs in a subprocess (it
+rearranges sys.path / sys.modules)."""
+import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+LAYOUT = os.path.join(ROOT, "tests", "golden", "dropin_layout.json")
+
+
+def write_stand_in(root, layout):
+    """The upstream tree's layout under `root`: a module per upstream module, defining the names the two systems import from
+    it; systems/base_system.py builds the model with the upstream keyword arguments, systems/panonerf_system.py makes the
+    upstream imports."""
+    wanted = {}
+    for imports in layout["system_imports"].values():
+        for mod, names in imports:
+            wanted.setdefault(mod, set()).update(n for n in names if n != "*")
+    for pkg, info in layout["packages"].items():
+        os.makedirs(os.path.join(root, pkg))
+        if info["regular"]:
+            open(os.path.join(root, pkg, "__init__.py"), "w").close()
+        for m in info["modules"]:
+            src = "".join(f"def {n}(*args, **kwargs):\n    raise NotImplementedError('stand-in')\n\n\n"
+                          for n in sorted(wanted.get(f"{pkg}.{m}", ())))
+            with open(os.path.join(root, pkg, m + ".py"), "w") as f:
+                f.write(src)
+
+    def import_lines(mod, skip_models=False):
+        return "".join(f"from {m} import {', '.join(names)}\n" for m, names in layout["system_imports"][mod]
+                       if not (skip_models and m.startswith("models.")))
+    with open(os.path.join(root, "systems", "base_system.py"), "w") as f:
+        f.write("from pytorch_lightning import LightningModule\n" + import_lines("systems.base_system", skip_models=True) + f"""
+KWARGS = {layout["model_kwargs"]!r}
+DENSITY_CHANNELS = {layout["num_density_channels"]!r}
+
+
+class BaseSystem(LightningModule):
+    def __init__(self, hparams):
+        super().__init__()
+        self.save_hyperparameters(hparams)
+        if hparams["nerf.mlp_name"] == "mipnerf":
+            from models.mip_nerf import MipNeRF as NeRFModel
+        else:
+            from models.pano_mip_nerf import PanoMipNeRF as NeRFModel
+        local = {{"num_density_channels": DENSITY_CHANNELS[hparams["nerf.mlp_name"]]}}
+        self.mip_nerf = NeRFModel(**{{k: hparams[v["hparam"]] if "hparam" in v else local[v["local"]]
+                                      for k, v in KWARGS.items()}})
+""")
+    with open(os.path.join(root, "systems", "panonerf_system.py"), "w") as f:
+        f.write(import_lines("systems.panonerf_system"))
+
 
 SCRIPT = r'''
 import sys, types
 sys.dont_write_bytecode = True
 REF, ROOT = sys.argv[1], sys.argv[2]
-sys.path[:0] = [REF, ROOT]          # exactly what INTEGRATION.md says: the reference first, then this repository
+sys.path[:0] = [REF, ROOT]          # exactly what INTEGRATION.md says: the upstream tree first, then this repository
 # libraries the reference imports that this image lacks (as tests/golden/make_golden.py does); none is on the hot path
 for name in ("cv2", "Imath", "lpips", "torchvision", "torchvision.utils", "wandb", "matplotlib", "matplotlib.pyplot",
              "matplotlib.cm"):
@@ -84,14 +129,18 @@ keys = list(system.mip_nerf.state_dict().keys())
 assert "mlp.layers.0.0.weight" in keys and "mlp.color_layer.bias" in keys and len(keys) == 24
 opt = torch.optim.Adam(system.mip_nerf.mlp.parameters(), lr=2e-4)   # base_system.py:82
 assert len(opt.param_groups[0]["params"]) == 24
+import systems.panonerf_system as ps  # systems/panonerf_system.py:2-11 resolve with the drop-in installed
+assert ps.BaseSystem is bs.BaseSystem and ps.rearrange_render_image is rearrange_render_image and ps.__file__.startswith(REF)
 print("DROPIN_OK")
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
-def test_install_resolves_reference_imports():
+def test_install_resolves_reference_imports(tmp_path):
+    with open(LAYOUT) as f:
+        write_stand_in(str(tmp_path), json.load(f))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    res = subprocess.run([sys.executable, "-c", SCRIPT, REF, ROOT], capture_output=True, text=True, timeout=300, env=env)
+    res = subprocess.run([sys.executable, "-c", SCRIPT, str(tmp_path), ROOT], capture_output=True, text=True, timeout=300,
+                         env=env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     assert "DROPIN_OK" in res.stdout
 

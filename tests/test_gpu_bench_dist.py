@@ -21,7 +21,7 @@ def test_two_rank_bench_flow(graph):
         env["PN_BENCH_FAIL_CAPTURE_RANK"] = "1"
         graph = "on"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+           "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--global-batch", "256", "--samples", "32", "--height", "64", "--width", "128", "--graph",
            graph]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)

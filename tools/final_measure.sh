@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final
 mkdir -p $O
 cd $R
-timeout -k 10 500 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 500 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "default bench done"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --no-cfg2 > $O/bench_under_rocprof.json 2> $O/kt.err
@@ -22,8 +22,8 @@ python3 $R/tools/pmc_summary.py $O/f2/f_counter_collection.csv $O/w2/w_counter_c
 cd $R && tools/pmc_pass.sh sq 2 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT
 echo "pmc done"
 cd $R
-timeout -k 10 200 python3 bench.py --global-batch 512 --steps 20 --warmup 5 --no-cpu-baseline --no-inference --no-cfg2 > $O/bench_b512.json 2> $O/bench_b512.err
+timeout -k 10 200 python3 bench.py --full --global-batch 512 --steps 20 --warmup 5 --no-cpu-baseline --no-inference --no-cfg2 > $O/bench_b512.json 2> $O/bench_b512.err
 for m in fused fused_f16x2_t32 fused_bf16 layerwise; do
-  timeout -k 10 200 python3 bench.py --mlp-mode $m --steps 10 --warmup 3 --no-cpu-baseline --no-cfg2 > $O/bench_$m.json 2> $O/bench_$m.err
+  timeout -k 10 200 python3 bench.py --full --mlp-mode $m --steps 10 --warmup 3 --no-cpu-baseline --no-cfg2 > $O/bench_$m.json 2> $O/bench_$m.err
 done
 echo "modes done"
