@@ -345,6 +345,39 @@ int64_t pn_gemm_tn_work_floats(int64_t M, int N1, int N2);
 int pn_gemm_tn(int64_t M, int N1, int N2, const float* X, int ldx, const float* Y, int ldy, float* C, int ldc,
                int accumulate, float* work, void* stream);
 
+/* ---- evaluation metrics of a rendered panorama (utils/metrics.py; pn_metrics.hip) ----------------------------
+ * Reductions over [C, H, W] equirectangular images, C = 1 or 3.  Element (c, i, j) of an operand is read at
+ * p[c * cs + (i * W + j) * ps] (cs: channel stride, ps: pixel stride, in floats), so the [1, C, H, W] permuted views
+ * that render_image returns are read in place.  Pixel weights are the solid angles sin((i + 1/2) pi / H), normalised
+ * to sum 1 over the H x W pixels (utils/surface_rendering.py:294-316).  Tone mapping per operand (`*_tone`): 0 none,
+ * 1 hdr_to_ldr(x), 2 hdr_to_ldr(x, dtype='uint8') (utils/surface_rendering.py:319-341).  Results are fp64 SUMS
+ * written to `out` (device); means are formed by the caller.  Partial sums go to `work` (device, at least
+ * pn_metrics_work_doubles(C, H, W) doubles) and are summed in a fixed order: no atomics, bit-reproducible.
+ * A non-finite input propagates to the sums, as in torch.  Errors: PN_ERR_BAD_SHAPE (H or W <= 0, C not 1 or 3,
+ * n <= 0), PN_ERR_UNSUPPORTED (unknown tone mode, window != 11, y_normalize not 0..2). */
+int64_t pn_metrics_work_doubles(int C, int H, int W);
+/* d = tone(x) - tone(y): out[6] = [sum d^2, sum |d|, sum w d^2, sum w |d|, sum d, element count] */
+int pn_metric_sums(int C, int H, int W, const float* x, int64_t x_cs, int64_t x_ps, int x_tone, const float* y,
+                   int64_t y_cs, int64_t y_ps, int y_tone, double* out, double* work, void* stream);
+/* SSIM of tone(x) and tone(y) per channel (utils/metrics.py:44-200: 11 x 11 Gaussian window of sigma 1.5, zero
+ * padding, C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2): out[3] = [sum s, sum w s (over channels), count];
+ * taps: the window's 1-D factor, `window` (= 11) device doubles (the reference builds it as fp32
+ * exp(-(k - 5)^2 / 4.5) over its fp32 sum; passing it in keeps every caller on the same bits);
+ * map (nullable): the SSIM map, [C, H, W] contiguous fp32. */
+int pn_metric_ssim(int C, int H, int W, const float* x, int64_t x_cs, int64_t x_ps, int x_tone, const float* y,
+                   int64_t y_cs, int64_t y_ps, int y_tone, int window, const double* taps, double max_val, float* map,
+                   double* out, double* work, void* stream);
+/* [3, H, W] normal images; y goes through y_normalize passes of F.normalize first.  cos = F.cosine_similarity over the
+ * channels (fp32, as ATen evaluates it), angle = nan_to_num(acos(cos)) in degrees (utils/metrics.py:240-257,
+ * 368-397): out[5] = [sum angle, sum w angle, sum cos, sum w cos, count] */
+int pn_metric_normals(int H, int W, const float* x, int64_t x_cs, int64_t x_ps, const float* y, int64_t y_cs,
+                      int64_t y_ps, int y_normalize, double* out, double* work, void* stream);
+/* depth metrics (utils/metrics.py:290-315) over n strided elements with mask > 0 (mask nullable: every element):
+ * out[9] = [count, sum |d|/g, sum d^2/g, sum d^2, log count (also p, g > 1e-7), sum (log p - log g)^2,
+ * then the counts of max(p/g, g/p) < 1.25, 1.25^2, 1.25^3] */
+int pn_metric_depth(int64_t n, const float* pred, int64_t pred_st, const float* gt, int64_t gt_st, const float* mask,
+                    int64_t mask_st, double* out, double* work, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

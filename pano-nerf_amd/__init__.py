@@ -7,7 +7,8 @@ Public surface (mirrors the reference's names):
     pano_loss, mip_loss           systems/panonerf_system.py:15-75, systems/mipnerf_system.py:22-53
     FlatAdam, mip_lr              systems/base_system.py:82-87, utils/lr_schedule.py:51-59
     render_image                  systems/panonerf_system.py:133-192
-    metrics, io_exr               utils/metrics.py:210-397 (calc_* / calc_ws_*), utils/io_exr.py:6-47
+    metrics, io_exr               utils/metrics.py (calc_* / calc_ws_*, SSIM, depth, calc_simse), utils/io_exr.py:6-47
+    evaluate_panorama             every metric of one render_image output against its ground truths (HIP kernels)
     concurrent_step               one training step as concurrent sub-batches on separate HIP streams
     install                       register PanoMipNeRF / MipNeRF under the reference's import paths (zero-edit drop-in)
 """
@@ -20,5 +21,6 @@ from .loss import pano_loss, mip_loss  # noqa
 from .optim import FlatAdam, mip_lr  # noqa
 from .renderer import render_image  # noqa
 from . import metrics, io_exr  # noqa
+from .metrics import evaluate_panorama  # noqa
 from .parallel import concurrent_step  # noqa
 from .install import install, uninstall  # noqa

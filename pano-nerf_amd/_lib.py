@@ -59,6 +59,11 @@ SIGNATURES = {
     "pn_chain_wgrad_work_floats": ("l", ""),
     "pn_chain_q24_slots": ("i", "iii"),
     "pn_chain_wgrad": ("i", "ipiippliiip"),
+    "pn_metrics_work_doubles": ("l", "iii"),
+    "pn_metric_sums": ("i", "iii" + "plli" * 2 + "ppp"),
+    "pn_metric_ssim": ("i", "iii" + "plli" * 2 + "ipd" + "pppp"),
+    "pn_metric_normals": ("i", "ii" + "pll" * 2 + "i" + "ppp"),
+    "pn_metric_depth": ("i", "l" + "pl" * 3 + "ppp"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),
