@@ -378,6 +378,49 @@ int pn_metric_normals(int H, int W, const float* x, int64_t x_cs, int64_t x_ps, 
 int pn_metric_depth(int64_t n, const float* pred, int64_t pred_st, const float* gt, int64_t gt_st, const float* mask,
                     int64_t mask_st, double* out, double* work, void* stream);
 
+/* ---- geometry export: field queries and marching tetrahedra (pn_geometry.hip) -----------------------------------
+ * Grid of nx x ny x nz vertices (every axis >= 2, nx ny nz < 2^31): vertex v = (i ny + j) nz + k sits at
+ * (x0 + i dx, y0 + j dy, z0 + k dz), each coordinate evaluated in fp32 in exactly that form.  Cell (i, j, k),
+ * i < nx - 1 etc., has index (i (ny - 1) + j)(nz - 1) + k.  A shape outside these bounds is PN_ERR_BAD_SHAPE. */
+/* (mean, cov) rows [m, 3] of the vertices first .. first + m - 1; every axis of cov gets `variance` */
+int pn_grid_points(int nx, int ny, int nz, int64_t first, int64_t m, float x0, float y0, float z0, float dx, float dy,
+                   float dz, float variance, float* mean, float* cov, void* stream);
+/* The activations of compute_graph (models/pano_mip_nerf.py:235-280) with the renderer's arithmetic, per row of
+ * raw_rgb [M,3] / raw_density [M,nc] / grad_mean [M,3] (+ d sigma / d mean, as pn_chain_density_grad writes it).
+ * Every output is nullable: sigma [M] = softplus(raw_0 + density_bias); albedo [M,3] = sigmoid(raw_1..3) 0.77 + 0.03
+ * (nc = 5 only, PN_ERR_UNSUPPORTED otherwise); rgb [M,3] = softplus(raw_rgb) (1 + 2 rgb_padding) - rgb_padding;
+ * normal [M,3] = -grad_mean / max(|grad_mean|, 1e-12).  sigma may point into a slab of a [nx, ny, nz] volume. */
+int pn_field_epilogue(int64_t M, int num_density_channels, float density_bias, float rgb_padding, const float* raw_rgb,
+                      const float* raw_density, const float* grad_mean, float* sigma, float* albedo, float* rgb,
+                      float* normal, void* stream);
+/* Marching tetrahedra of sigma [nx, ny, nz] (contiguous fp32) at `level`.
+ *   inside <=> sigma > level (strict; NaN is outside).
+ *   Each cell splits into 6 tetrahedra (Freudenthal / Kuhn): T0 = p, T1 = p + e_a, T2 = p + e_a + e_b, T3 = p + (1,1,1)
+ *   for (a, b, c) = xyz, xzy, yxz, yzx, zxy, zyx in that order.  Every tetrahedron edge runs from a grid vertex u to
+ *   u + o_s, o_s one of the 7 offsets s = 0 (1,0,0), 1 (0,1,0), 2 (0,0,1), 3 (1,1,0), 4 (1,0,1), 5 (0,1,1), 6 (1,1,1):
+ *   neighbouring cells share every edge, so the mesh is watertight inside the grid.  Edge id = 7 u + s.
+ *   Vertices [V,3]: one per edge whose endpoints differ in inside-ness, at p_u + t (p_b - p_u),
+ *   t = (level - sigma_u) / (sigma_b - sigma_u), in ascending edge-id order.
+ *   Faces [F,3] int32: by cell index, then tetrahedron, then the order of the case table below.
+ *   Case table: case = in(T0) | in(T1) << 1 | in(T2) << 2 | in(T3) << 3; tetrahedron edges 0 (T0,T1), 1 (T0,T2),
+ *   2 (T0,T3), 3 (T1,T2), 4 (T1,T3), 5 (T2,T3); triangles as edge triples for the even tetrahedra xyz, yzx, zxy:
+ *     0: -            1: 012          2: 043          3: 124 143      4: 135          5: 052 035      6: 045 051
+ *     7: 245          8: 254          9: 015 054     10: 053 025     11: 153         12: 134 142     13: 034
+ *     14: 021         15: -
+ *   (one lone vertex: its three edges; two and two, inside {a < b}, outside {c < d}: (ac, ad, bd), (ac, bd, bc)),
+ *   wound so that (v1 - v0) x (v2 - v0) points to the outside (sigma <= level).  The odd tetrahedra xzy, yxz, zyx emit
+ *   each triangle with its last two vertices swapped.
+ * pn_mt_count: work = pn_mt_work_bytes(nx, ny, nz) bytes (device); writes totals[2] (device int64) = {V, F}.
+ * pn_mt_emit: after pn_mt_count on the same sigma, level and work; num_vertices / num_faces are the rows of
+ *   vertices / faces (the totals, copied by the caller); rows beyond them are not written.  Both must be < 2^31
+ *   (PN_ERR_BAD_SHAPE otherwise).  Vertex coordinates use the placement of pn_grid_points.
+ * Block sums, a scan of the block sums and a fix-up pass in separate launches: no atomics, the same output on every run. */
+int64_t pn_mt_work_bytes(int nx, int ny, int nz);
+int pn_mt_count(int nx, int ny, int nz, const float* sigma, float level, void* work, int64_t* totals, void* stream);
+int pn_mt_emit(int nx, int ny, int nz, const float* sigma, float level, const void* work, int64_t num_vertices,
+               int64_t num_faces, float x0, float y0, float z0, float dx, float dy, float dz, float* vertices,
+               int32_t* faces, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -9,6 +9,9 @@ Public surface (mirrors the reference's names):
     render_image                  systems/panonerf_system.py:133-192
     metrics, io_exr               utils/metrics.py (calc_* / calc_ws_*, SSIM, depth, calc_simse), utils/io_exr.py:6-47
     evaluate_panorama             every metric of one render_image output against its ground truths (HIP kernels)
+    geometry                      field queries (sigma, albedo, rgb, normal at 3-D points), sigma volumes, marching-tetrahedra
+                                  meshes and PLY output of a trained model (HIP kernels)
+    extract_mesh                  Mesh(vertices, faces, normals, colors) of {sigma > level} over a box
     concurrent_step               one training step as concurrent sub-batches on separate HIP streams
     install                       register PanoMipNeRF / MipNeRF under the reference's import paths (zero-edit drop-in)
 """
@@ -22,5 +25,7 @@ from .optim import FlatAdam, mip_lr  # noqa
 from .renderer import render_image  # noqa
 from . import metrics, io_exr  # noqa
 from .metrics import evaluate_panorama  # noqa
+from . import geometry  # noqa
+from .geometry import extract_mesh  # noqa
 from .parallel import concurrent_step  # noqa
 from .install import install, uninstall  # noqa

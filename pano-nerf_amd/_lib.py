@@ -64,6 +64,11 @@ SIGNATURES = {
     "pn_metric_ssim": ("i", "iii" + "plli" * 2 + "ipd" + "pppp"),
     "pn_metric_normals": ("i", "ii" + "pll" * 2 + "i" + "ppp"),
     "pn_metric_depth": ("i", "l" + "pl" * 3 + "ppp"),
+    "pn_grid_points": ("i", "iiill" + "f" * 7 + "ppp"),
+    "pn_field_epilogue": ("i", "liff" + "p" * 7 + "p"),
+    "pn_mt_work_bytes": ("l", "iii"),
+    "pn_mt_count": ("i", "iiipfppp"),
+    "pn_mt_emit": ("i", "iiipfpll" + "f" * 6 + "ppp"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

@@ -1,6 +1,7 @@
 // pn_common.h — shared declarations for the gfx950 kernels of libpanonerf_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include "../../include/panonerf_hip.h"
 
@@ -98,5 +99,9 @@ struct PnPack {
     int64_t total;
 };
 PnPack pn_pack_layout();
+
+// activations of the radiance field (pn_render.hip composites, pn_geometry.hip field queries: one definition, the same bits)
+__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 static inline int64_t pn_pad(int64_t m) { return (m + PN_ROW_PAD - 1) / PN_ROW_PAD * PN_ROW_PAD; }

@@ -12,14 +12,12 @@
 #define HALF_PI_F 1.5707964f /* fl32(0.5 * fl32(pi)), models/mip.py:428,437 */
 
 // ------------------------------------------------------------------------------- helpers
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float softplus_d1(float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float softplus_d2(float x) {
     if (x > 20.f) return 0.f;
     float s = 1.f / (1.f + expf(-x));
     return s * (1.f - s);
 }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // torch.linspace(a, b, steps)[i] (symmetric evaluation used by ATen)
 __device__ __forceinline__ float linspace_at(float a, float b, int steps, int i) {

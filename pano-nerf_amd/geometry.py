@@ -1,0 +1,331 @@
+"""Export of the learned geometry: field queries, sigma volumes, marching-tetrahedra meshes and PLY files.
+
+Everything runs on the HIP device through the kernels of ``libpanonerf_hip.so`` (``pn_geometry.hip`` plus the MLP
+entry points the renderer uses), under ``torch.no_grad()`` on the current stream.  CPU tensors raise: there is no host
+fallback.  The only host synchronisation is the copy of the two mesh totals that sizes the outputs.
+
+    query_field(model, points, ...)             sigma / albedo / rgb / normal / grad (d sigma / d mean) at [M, 3] points
+    grid_points(bounds, resolution, ...)        the (mean, cov) rows of a grid's vertices
+    density_grid(model, bounds, resolution)     sigma on an [nx, ny, nz] vertex grid
+    marching_tetrahedra(sigma, level, bounds)   (vertices [V, 3], faces [F, 3] int32) of {sigma > level}
+    extract_mesh(model, bounds, resolution, level)  Mesh(vertices, faces, normals, colors)
+    write_ply(path, vertices, faces, normals, colors)  binary little-endian PLY
+
+The mesh contract (edge ids, vertex and face order, winding) is stated in include/panonerf_hip.h.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from .render import _Eval, _mlp_forward, _planes_of, _tfmt_of
+
+Mesh = collections.namedtuple("Mesh", ["vertices", "faces", "normals", "colors"])
+
+FIELD_OUTPUTS = ("sigma", "albedo", "rgb", "normal", "grad")
+
+# default rows per chunk: the layer-wise path keeps ~10 KB per row (activations), +8 KB for the density-gradient sweep;
+# the chains keep ~0.7 KB (gate words, encoding, raw outputs), +1 KB for the density-gradient slot
+_CHUNK_LAYERWISE = 1 << 16
+_CHUNK_CHAIN = 1 << 19
+
+
+def _device_of(*tensors):
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.device.type != "cuda":
+            raise RuntimeError("pano_nerf_amd.geometry runs on a HIP device only (a tensor is on %s); there is no CPU "
+                               "fallback" % t.device)
+    return tensors[0].device
+
+
+def _model_device(model):
+    dev = model.mlp.flat_params().device
+    if dev.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.geometry runs on a HIP device only (the model is on %s); there is no CPU "
+                           "fallback" % dev)
+    return dev
+
+
+def _resolution(resolution):
+    r = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(x) for x in resolution)
+    if len(r) != 3 or min(r) < 2:
+        raise ValueError(f"resolution must be an int or 3 ints, each >= 2; got {resolution!r}")
+    if r[0] * r[1] * r[2] >= 1 << 31:
+        raise ValueError(f"resolution {r} has 2^31 or more vertices")
+    return r
+
+
+def _placement(bounds, res):
+    """((x0, y0, z0), (dx, dy, dz)) of inclusive corner vertices `bounds` on `res` vertices per axis."""
+    try:
+        lo, hi = [tuple(float(v) for v in c) for c in bounds]
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)); got {bounds!r}")
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)); got {bounds!r}")
+    step = tuple((b - a) / (n - 1) for a, b, n in zip(lo, hi, res))
+    # the kernels see fp32 values: report the same
+    return tuple(float(np.float32(v)) for v in lo), tuple(float(np.float32(v)) for v in step)
+
+
+def _variance(model, variance, step=None):
+    if getattr(model, "disable_integration", False):  # models/pano_mip_nerf.py:241-243: zero covariance everywhere
+        return 0.0
+    if variance is None:
+        return 0.0 if step is None else max(abs(s) for s in step) ** 2 / 12.0
+    return variance
+
+
+def _field_rows(model, dev, M, fill, outputs, viewdirs, chunk_rows, results):
+    """Evaluate the field over M rows in chunks; fill(first, m, mean, cov) writes a chunk's (mean, cov) rows; results:
+    output name -> [M, ...] tensor (or, for "sigma", any [M] view, e.g. a flat volume)."""
+    mlp, nc = model.mlp, model._NC
+    mode = model.mlp_mode
+    planes, tfmt = _planes_of(mode), _tfmt_of(mode)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    params = mlp.flat_params()
+    wpack = mlp.chain_packed(st, planes) if planes else mlp.packed(st)
+    want_grad = "normal" in results or "grad" in results
+    chunk = int(chunk_rows) if chunk_rows else (_CHUNK_CHAIN if planes else _CHUNK_LAYERWISE)
+    if chunk <= 0:
+        raise ValueError(f"chunk_rows must be positive; got {chunk_rows!r}")
+    dummy_view = torch.zeros(1, 3, dtype=torch.float32, device=dev)
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    for first in range(0, M, chunk):
+        m = min(chunk, M - first)
+        if viewdirs is None:  # sigma / albedo / normals do not read the view: one dummy view row for the whole chunk
+            vd, rpr = dummy_view, m
+        elif viewdirs.shape[0] == 1:
+            vd, rpr = viewdirs, m
+        else:
+            vd, rpr = viewdirs[first:first + m], 1
+        ev = _Eval(m, rpr, vd, nc, dev, planes, False, tfmt)
+        fill(first, m, ev.mean, ev.cov)
+        _mlp_forward(ev, params, wpack, st)
+        gmean = None
+        if want_grad:
+            gmean = results["grad"][first:first + m] if "grad" in results else e(m, 3)
+            if planes:
+                rs = e(ev.Mp * 256)
+                _lib.call("pn_chain_density_grad", m, nc, planes, model.density_bias, params.data_ptr(), wpack.data_ptr(),
+                          ev.mean.data_ptr(), ev.cov.data_ptr(), ev.masks.data_ptr(), ev.raw_den.data_ptr(),
+                          rs.data_ptr(), 0, gmean.data_ptr(), None, tfmt, 0, st)
+            else:
+                rs, scratch = e(8, ev.Mp, 256), e(ev.Mp, 96)
+                _lib.call("pn_density_grad", m, nc, model.density_bias, params.data_ptr(), wpack.data_ptr(),
+                          ev.mean.data_ptr(), ev.cov.data_ptr(), ev.acts.data_ptr(), ev.masks.data_ptr(),
+                          ev.raw_den.data_ptr(), rs.data_ptr(), scratch.data_ptr(), gmean.data_ptr(), st)
+            del rs
+        sl = lambda k: (results[k][first:first + m] if k in results else None)
+        _lib.call("pn_field_epilogue", m, nc, model.density_bias, model.rgb_padding, ev.raw_rgb.data_ptr(),
+                  ev.raw_den.data_ptr(), _lib.ptr(gmean), _lib.ptr(sl("sigma")), _lib.ptr(sl("albedo")),
+                  _lib.ptr(sl("rgb")), _lib.ptr(sl("normal")), st)
+        del ev
+
+
+def _check_outputs(model, outputs, viewdirs):
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in FIELD_OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown field outputs {bad}; choose from {FIELD_OUTPUTS}")
+    if "albedo" in outputs and model._NC != 5:
+        raise ValueError(f"albedo needs a 5-channel density head (PanoMipNeRF); {type(model).__name__} has {model._NC}")
+    if "rgb" in outputs and viewdirs is None:
+        raise ValueError("rgb needs viewdirs ([M, 3] or one [3] direction)")
+    return outputs
+
+
+def query_field(model, points, variance=None, viewdirs=None, outputs=("sigma", "albedo", "normal"), chunk_rows=None):
+    """The trained field at `points` [M, 3]: a dict of [M] ("sigma") and [M, 3] ("albedo", "rgb", "normal" = -grad
+    normalised, "grad" = d sigma / d mean) fp32 tensors on the points' device.
+
+    variance: None (0: plain positional encoding), a float or an [M, 3] tensor - the diagonal covariance of the
+    integrated encoding; a model built with disable_integration=True always uses 0.  viewdirs ([M, 3] or [3]) is needed
+    for "rgb" only.  "albedo" needs a PanoMipNeRF (5 density channels).  chunk_rows bounds the rows evaluated at once."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be an [M, 3] tensor; got {getattr(points, 'shape', type(points))}")
+    outputs = _check_outputs(model, outputs, viewdirs)
+    if viewdirs is not None:
+        if not isinstance(viewdirs, torch.Tensor) or viewdirs.shape not in ((3,), (points.shape[0], 3)):
+            raise ValueError(f"viewdirs must be [M, 3] or [3]; got {getattr(viewdirs, 'shape', type(viewdirs))}")
+    var_t = None
+    if isinstance(variance, torch.Tensor):
+        if variance.shape != points.shape:
+            raise ValueError(f"a variance tensor must be [M, 3] like the points; got {tuple(variance.shape)}")
+        var_t = variance
+    dev = _device_of(points, *[t for t in (viewdirs, var_t) if t is not None])
+    if _model_device(model) != dev:
+        raise RuntimeError(f"points are on {dev}, the model on {_model_device(model)}")
+    variance = _variance(model, variance)
+    M = points.shape[0]
+    with torch.no_grad(), torch.cuda.device(dev):
+        pts = points.detach().to(torch.float32).contiguous()
+        vd = None
+        if viewdirs is not None:
+            vd = viewdirs.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        cov_src = variance.detach().to(torch.float32).contiguous() if isinstance(variance, torch.Tensor) else None
+
+        def fill(first, m, mean, cov):
+            mean.copy_(pts[first:first + m])
+            if cov_src is not None:
+                cov.copy_(cov_src[first:first + m])
+            else:
+                cov.fill_(float(variance))
+
+        res = {k: torch.empty((M,) if k == "sigma" else (M, 3), dtype=torch.float32, device=dev) for k in outputs}
+        if M:
+            _field_rows(model, dev, M, fill, outputs, vd if "rgb" in outputs else None, chunk_rows, res)
+    return res
+
+
+def grid_points(bounds, resolution, variance=0.0, device=None):
+    """(mean, cov) [nx ny nz, 3] of the grid's vertices in vertex order (i ny + j) nz + k, as the kernels place them."""
+    res = _resolution(resolution)
+    lo, step = _placement(bounds, res)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.geometry runs on a HIP device only; there is no CPU fallback")
+    n = res[0] * res[1] * res[2]
+    with torch.cuda.device(dev):
+        mean = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        cov = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        _lib.call("pn_grid_points", *res, 0, n, *lo, *step, float(variance), mean.data_ptr(), cov.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+    return mean, cov
+
+
+def density_grid(model, bounds, resolution, variance=None, chunk_rows=None):
+    """sigma at the vertices of a grid: a contiguous fp32 [nx, ny, nz] tensor on the model's device.
+
+    bounds = ((x0, y0, z0), (x1, y1, z1)) are the inclusive corner vertices; resolution is an int or 3 ints (vertices
+    per axis, each >= 2).  variance: a float; None gives max(dx, dy, dz)^2 / 12, the second moment of a voxel."""
+    res = _resolution(resolution)
+    lo, step = _placement(bounds, res)
+    if isinstance(variance, torch.Tensor):
+        raise ValueError("density_grid takes a scalar variance")
+    variance = float(_variance(model, variance, step))
+    dev = _model_device(model)
+    vol = torch.empty(res, dtype=torch.float32, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+
+        def fill(first, m, mean, cov):
+            _lib.call("pn_grid_points", *res, first, m, *lo, *step, variance, mean.data_ptr(), cov.data_ptr(), st)
+
+        _field_rows(model, dev, vol.numel(), fill, ("sigma",), None, chunk_rows, {"sigma": vol.view(-1)})
+    return vol
+
+
+def marching_tetrahedra(sigma, level, bounds=None):
+    """Iso-surface {sigma > level} of an [nx, ny, nz] volume: (vertices [V, 3] fp32, faces [F, 3] int32) on its device.
+
+    Without bounds the vertices are in grid units from the origin (vertex (i, j, k) at (i, j, k)); with bounds, in the
+    placement of density_grid.  Faces are wound so that (v1 - v0) x (v2 - v0) points to the outside (sigma <= level).
+    An empty surface gives [0, 3] tensors."""
+    if not isinstance(sigma, torch.Tensor) or sigma.dim() != 3:
+        raise ValueError(f"sigma must be an [nx, ny, nz] tensor; got {getattr(sigma, 'shape', type(sigma))}")
+    res = tuple(int(x) for x in sigma.shape)
+    if min(res) < 2:
+        raise ValueError(f"every axis of sigma must have >= 2 vertices; got {res}")
+    if res[0] * res[1] * res[2] >= 1 << 31:
+        raise ValueError(f"sigma {res} has 2^31 or more vertices")
+    dev = _device_of(sigma)
+    if bounds is None:
+        lo, step = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+    else:
+        lo, step = _placement(bounds, res)
+    level = float(level)
+    with torch.no_grad(), torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        s = sigma.detach().to(torch.float32).contiguous()
+        work = torch.empty(int(_lib.load().pn_mt_work_bytes(*res)), dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.call("pn_mt_count", *res, s.data_ptr(), level, work.data_ptr(), totals.data_ptr(), st)
+        nv, nf = (int(x) for x in totals.cpu())  # the one host sync: sizes the outputs
+        if nv >= 1 << 31 or nf >= 1 << 31:
+            raise RuntimeError(f"mesh of {nv} vertices / {nf} faces does not fit int32 indices; use a coarser grid")
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        _lib.call("pn_mt_emit", *res, s.data_ptr(), level, work.data_ptr(), nv, nf, *lo, *step,
+                  _lib.ptr(verts) if nv else None, _lib.ptr(faces) if nf else None, st)
+    return verts, faces
+
+
+def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, colors="auto", chunk_rows=None):
+    """Mesh(vertices [V, 3], faces [F, 3] int32, normals [V, 3] | None, colors [V, 3] | None) of {sigma > level} on the
+    model's device: density_grid -> marching_tetrahedra, then the field queried at the vertices with the grid's
+    variance.  normals: the model's normals (-grad sigma, normalised).  colors: "auto" (albedo for PanoMipNeRF, radiance
+    for MipNeRF), "albedo", "radiance" (rgb seen along -normal) or None."""
+    if colors not in ("auto", "albedo", "radiance", None):
+        raise ValueError(f"colors must be 'auto', 'albedo', 'radiance' or None; got {colors!r}")
+    if colors == "auto":
+        colors = "albedo" if model._NC == 5 else "radiance"
+    if colors == "albedo" and model._NC != 5:
+        raise ValueError(f"colors='albedo' needs a PanoMipNeRF (5 density channels); {type(model).__name__} has none")
+    if level is None:
+        raise ValueError("level is required")
+    res = _resolution(resolution)
+    _, step = _placement(bounds, res)
+    if isinstance(variance, torch.Tensor):
+        raise ValueError("extract_mesh takes a scalar variance")
+    variance = float(_variance(model, variance, step))
+    _model_device(model)
+    sigma = density_grid(model, bounds, res, variance, chunk_rows)
+    verts, faces = marching_tetrahedra(sigma, level, bounds)
+    del sigma
+    nrm = col = None
+    want = (("normal",) if (normals or colors == "radiance") else ()) + (("albedo",) if colors == "albedo" else ())
+    if want:
+        q = query_field(model, verts, variance, outputs=want, chunk_rows=chunk_rows)
+        nrm, col = q.get("normal"), q.get("albedo")
+        if colors == "radiance":
+            col = query_field(model, verts, variance, viewdirs=-nrm, outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
+        if not normals:
+            nrm = None
+    return Mesh(verts, faces, nrm, col)
+
+
+def write_ply(path, vertices, faces, normals=None, colors=None):
+    """Binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue] per vertex, a uchar-counted int list of
+    vertex_indices per face.  Colours are clamped to [0, 1] and scaled by 255 (rounded to nearest)."""
+    v = _host(vertices, np.float32, "vertices")
+    f = _host(faces, np.int32, "faces")
+    n = None if normals is None else _host(normals, np.float32, "normals")
+    c = None if colors is None else _host(colors, np.float32, "colors")
+    for name, a in (("normals", n), ("colors", c)):
+        if a is not None and a.shape != v.shape:
+            raise ValueError(f"{name} must be [V, 3] like the vertices; got {a.shape}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if n is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if c is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vrec = np.empty(v.shape[0], dtype=fields)
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if c is not None:
+        q = np.rint(np.clip(np.nan_to_num(c), 0.0, 1.0) * 255.0).astype(np.uint8)
+        vrec["red"], vrec["green"], vrec["blue"] = q[:, 0], q[:, 1], q[:, 2]
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    frec["n"] = 3
+    frec["i"] = f
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    head += [f"property float {k}" for k in ("x", "y", "z")]
+    if n is not None:
+        head += [f"property float {k}" for k in ("nx", "ny", "nz")]
+    if c is not None:
+        head += [f"property uchar {k}" for k in ("red", "green", "blue")]
+    head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def _host(x, dtype, name):
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{name} must be [N, 3]; got {a.shape}")
+    return np.ascontiguousarray(a, dtype=dtype)
