@@ -421,6 +421,38 @@ int pn_mt_emit(int nx, int ny, int nz, const float* sigma, float level, const vo
                int64_t num_faces, float x0, float y0, float z0, float dx, float dy, float dz, float* vertices,
                int32_t* faces, void* stream);
 
+/* ---- spatially-varying lighting: light probes, SH and irradiance (pn_lighting.hip) ----------------------------
+ * A light probe is an H x W equirectangular image (H, W >= 2) of HDR radiance.  Pixel pix = i W + j looks along the
+ * viewdir pn_raygen_pano gives a camera with identity rotation (sample_dir_by_pano, utils/sampling.py:5-20; y up) and
+ * covers the solid angle omega_i = sin((i + 1/2) pi / H) (2 pi / W) (pi / H) (solid_angle_refinement,
+ * utils/surface_rendering.py:294-316).  That is upstream's unnormalised midpoint rule: its sum exceeds 4 pi by about
+ * (pi / H)^2 / 24 relative (0.6 % at H = 8, 0.04 % at H = 32).  The caller passes the table: dirs [H W, 3], omega [H W].
+ * Radiance of P probes is read at x[p * probe_stride + c * cs + pix * ps] (c = 0..2; strides in floats), so the
+ * [P, 3, H, W] views of [P, H, W, 3] buffers are read in place.
+ * SH: real, l <= 2, 9 coefficients per channel in the order (0,0) (1,-1) (1,0) (1,1) (2,-2) (2,-1) (2,0) (2,1) (2,2):
+ * Y = 0.282095, 0.488603 {y, z, x}, 1.092548 {xy, yz}, 0.315392 (3 z^2 - 1), 1.092548 xz, 0.546274 (x^2 - y^2)
+ * (constants to full double precision).  SH tensors are [., 9, 3] fp32 (coefficient-major, channel-minor).
+ * Irradiance from SH (Ramamoorthi & Hanrahan 2001): E(n) = sum_lm A_l L_lm Y_lm(n), A = (pi, 2 pi / 3, pi / 4).
+ * Every sum is fp64 in a fixed order, without atomics: repeated calls give the same bits.  NaN radiance propagates.
+ * Errors: PN_ERR_BAD_SHAPE (P <= 0 or >= 2^25, H or W < 2, H W >= 2^30, K <= 0, a grid axis < 2). */
+/* L_lm = sum_pix L(pix) Y_lm(dir_pix) omega_pix -> out [P, 9, 3]; work: pn_probe_sh_work_doubles(P, H, W) device
+ * doubles of per-workgroup partial sums, added in order by a second launch */
+int64_t pn_probe_sh_work_doubles(int64_t P, int H, int W);
+int pn_probe_sh(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+                const float* dirs, const float* omega, float* out, double* work, void* stream);
+/* exact quadrature E_p(n) = sum_pix L_p(pix) max(0, n . dir_pix) omega_pix (the shading of surface_rendering,
+ * utils/surface_rendering.py:129-165, over every probe pixel) for normals [K, 3] shared by every probe
+ * (per_probe_normals = 0) or [P, K, 3] (1) -> out [P, K, 3].  max as torch.relu: a NaN dot product stays NaN. */
+int pn_probe_irradiance(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+                        const float* dirs, const float* omega, int64_t K, const float* normals, int per_probe_normals,
+                        float* out, void* stream);
+/* SH irradiance volume: sh [nx ny nz, 9, 3] at the vertices of a grid placed as by pn_grid_points (vertex
+ * (i ny + j) nz + k at (x0 + i dx, ...)).  Per point of points [M, 3]: clamp it to the box, interpolate the 27
+ * coefficients trilinearly, E(normal) with the A_l weights above -> out [M, 3] (normals [M, 3], unit length). */
+int pn_sh_volume_irradiance(int nx, int ny, int nz, float x0, float y0, float z0, float dx, float dy, float dz,
+                            const float* sh, int64_t M, const float* points, const float* normals, float* out,
+                            void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

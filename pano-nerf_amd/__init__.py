@@ -12,6 +12,8 @@ Public surface (mirrors the reference's names):
     geometry                      field queries (sigma, albedo, rgb, normal at 3-D points), sigma volumes, marching-tetrahedra
                                   meshes and PLY output of a trained model (HIP kernels)
     extract_mesh                  Mesh(vertices, faces, normals, colors) of {sigma > level} over a box
+    lighting                      spatially-varying lighting: HDR light probes, SH projection, exact and SH irradiance,
+                                  the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
     concurrent_step               one training step as concurrent sub-batches on separate HIP streams
     install                       register PanoMipNeRF / MipNeRF under the reference's import paths (zero-edit drop-in)
 """
@@ -27,5 +29,6 @@ from . import metrics, io_exr  # noqa
 from .metrics import evaluate_panorama  # noqa
 from . import geometry  # noqa
 from .geometry import extract_mesh  # noqa
+from . import lighting  # noqa
 from .parallel import concurrent_step  # noqa
 from .install import install, uninstall  # noqa

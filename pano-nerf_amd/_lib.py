@@ -69,6 +69,10 @@ SIGNATURES = {
     "pn_mt_work_bytes": ("l", "iii"),
     "pn_mt_count": ("i", "iiipfppp"),
     "pn_mt_emit": ("i", "iiipfpll" + "f" * 6 + "ppp"),
+    "pn_probe_sh_work_doubles": ("l", "lii"),
+    "pn_probe_sh": ("i", "liip" + "lll" + "pppp" + "p"),
+    "pn_probe_irradiance": ("i", "liip" + "lll" + "pp" + "lpi" + "p" + "p"),
+    "pn_sh_volume_irradiance": ("i", "iii" + "f" * 6 + "plppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

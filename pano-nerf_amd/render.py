@@ -214,6 +214,29 @@ def _chain_wgrad(evals, nc, planes, flat_grad, st, which=3, wgs=0):
     return work
 
 
+def _light_gather(cfg, params, wpack, o, d, dist, env_d, env_rad, env_near, env_far, env_omega, env_rand, albedo, normal,
+                  keep, st):
+    """The light estimate at x_surf = o + d * dist (models/pano_mip_nerf.py:319-359): D light rays of Ne samples each
+    through the field, composited, then the Lambertian sums of the surface shading (utils/surface_rendering.py:104-165).
+    Shared by the renderer and lighting.field_irradiance.  -> (env evaluation, env_rgb [B D, 3], diffuse, shading)."""
+    dev, B, nc, planes = o.device, o.shape[0], cfg.nc, cfg.planes
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    D, Ne = env_d.shape[0], cfg.num_env_samples
+    ee = _Eval(B * D * Ne, Ne, env_d, nc, dev, planes, keep, cfg.tfmt)
+    ee.t = e(B * D, Ne + 1)
+    _lib.call("pn_sample_env", B, D, Ne, o.data_ptr(), d.data_ptr(), dist.data_ptr(), env_d.data_ptr(),
+              env_rad.data_ptr(), env_near.data_ptr(), env_far.data_ptr(), _lib.ptr(env_rand),
+              ee.t.data_ptr(), ee.mean.data_ptr(), ee.cov.data_ptr(), st)
+    if cfg.disable_integration:
+        ee.cov.zero_()
+    _mlp_forward(ee, params, wpack, st)
+    env_rgb, _, _, _ = _composite_forward(ee, B * D, Ne, cfg, False, env_d, D, st)
+    diffuse, shading = e(B, 3), e(B, 3)
+    _lib.call("pn_surface_forward", B, D, env_rgb.data_ptr(), albedo.data_ptr(), normal.data_ptr(),
+              env_d.data_ptr(), env_omega.data_ptr(), diffuse.data_ptr(), shading.data_ptr(), st)
+    return ee, env_rgb, diffuse, shading
+
+
 class _RenderFn(torch.autograd.Function):
     """(rays, env rays, noise, 24 parameters) -> the ten differentiable outputs of both levels."""
 
@@ -284,19 +307,8 @@ class _RenderFn(torch.autograd.Function):
             if not keep:
                 e1.acts = e1.masks = e1.enc = None
             if cfg.surf:
-                D, Ne = env_d.shape[0], cfg.num_env_samples
-                ee = _Eval(B * D * Ne, Ne, env_d, nc, dev, planes, keep, cfg.tfmt)
-                ee.t = e(B * D, Ne + 1)
-                _lib.call("pn_sample_env", B, D, Ne, o.data_ptr(), d.data_ptr(), dist1.data_ptr(), env_d.data_ptr(),
-                          env_rad.data_ptr(), env_near.data_ptr(), env_far.data_ptr(), _lib.ptr(env_rand),
-                          ee.t.data_ptr(), ee.mean.data_ptr(), ee.cov.data_ptr(), st)
-                if cfg.disable_integration:
-                    ee.cov.zero_()
-                _mlp_forward(ee, params, wpack, st)
-                env_rgb, _, _, _ = _composite_forward(ee, B * D, Ne, cfg, False, env_d, D, st)
-                diffuse, shading = e(B, 3), e(B, 3)
-                _lib.call("pn_surface_forward", B, D, env_rgb.data_ptr(), albedo.data_ptr(), normal.data_ptr(),
-                          env_d.data_ptr(), env_omega.data_ptr(), diffuse.data_ptr(), shading.data_ptr(), st)
+                ee, env_rgb, diffuse, shading = _light_gather(cfg, params, wpack, o, d, dist1, env_d, env_rad, env_near,
+                                                              env_far, env_omega, env_rand, albedo, normal, keep, st)
                 surface = diffuse.clone()
         ctx.cfg, ctx.mlp = cfg, mlp
         # `normal` and `albedo` are OUTPUTS of this Function: they go through save_for_backward (an output kept as a plain
