@@ -453,6 +453,37 @@ int pn_sh_volume_irradiance(int nx, int ny, int nz, float x0, float y0, float z0
                             const float* sh, int64_t M, const float* points, const float* normals, float* out,
                             void* stream);
 
+/* ---- novel views: pinhole rays and viewable frames (pn_views.hip) -----------------------------------------------
+ * Pinhole camera: pix2cam [3, 3] fp32 row-major maps pixel (x + 1/2, y + 1/2, 1) (x = column, y = row) to a camera-space
+ * direction; the Blender form is ((x + 1/2 - W/2) / f, -(y + 1/2 - H/2) / f, -1): x right, y up, looking along -z
+ * (datasets/base_datasets.py:216-265; Multicam passes its own pix2cam, :118-170).  Per ray, each product a 3-term fp32
+ * dot product in index order: directions = c2w[:3,:3] @ (pix2cam @ p), NOT normalised; viewdirs = directions / |.|;
+ * origins = c2w[:3, 3]; lossmult = 1; near / far as given; noise_var = 0; radii = |d(i, j) - d(i + 1, j)| 2 / sqrt(12)
+ * with the NEXT ROW's direction (upstream's rule as written, although its comment says "x-axis neighbor"); row H - 1
+ * reuses row H - 2's value.  Cameras: pix2cams [n_cam, 9], c2ws [n_cam, 16] (row-major 4x4), both device arrays.
+ * Batch ray b is pixel idx[b] % (H W) of camera idx[b] / (H W) (an index outside the pool reads ray 0); rgb_pool
+ * [n_cam H W, 3] and rgb_out [B, 3] are both given (target colours are gathered) or both NULL.
+ * Errors: PN_ERR_BAD_SHAPE (B <= 0, n_cam <= 0, H or W < 2, H W >= 2^31). */
+int pn_sample_pinhole_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* pix2cams,
+                           const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
+                           float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
+                           float* far_out, float* noise_var, float* rgb_out, void* stream);
+/* Frames: one H x W image, element (c, pix) at x[c cs + pix ps] (strides in floats), -> out [H W, 3] uint8 (device),
+ * the bytes systems/panonerf_system.py:77-131 writes through save_results (utils/vis.py:25-41): trunc(255 v), NaN -> 0.
+ *   PN_FRAME_LDR     hdr_to_ldr(scale x, dtype='uint8'): k = trunc(255 clamp(aces)), v = (k / 255) ** (1 / 2.2)
+ *   PN_FRAME_LDR_GT  hdr_to_ldr(scale x): v = clamp(aces) ** (1 / 2.2)
+ *   PN_FRAME_DEPTH   hotmap((d - near) / range) (utils/vis.py:13-22): t = (d - near) / range, x = t - min / (max - min)
+ *                    (upstream's precedence; min / max over the image, NaN-propagating), then matplotlib jet: i = trunc(256 x),
+ *                    x == 1 -> 255, x < 0 -> lut[0], x > 1 -> lut[255], NaN -> black.  lut: [256, 3] fp32 (device);
+ *                    work: 2 device floats (the min / max, written by a first single-workgroup launch)
+ *   PN_FRAME_NORMAL  v = (x / max(|x|, 1e-12) + 1) / 2
+ *   PN_FRAME_ALBEDO  v = clamp(x, 0, 1)
+ * The tone mapping is pn_metrics.hip's (fp32, upstream's order of operations).  No atomics: repeated calls give the same
+ * bytes.  Errors: PN_ERR_BAD_SHAPE (H or W <= 0, H W >= 2^31), PN_ERR_UNSUPPORTED (unknown kind). */
+enum { PN_FRAME_LDR = 0, PN_FRAME_LDR_GT = 1, PN_FRAME_DEPTH = 2, PN_FRAME_NORMAL = 3, PN_FRAME_ALBEDO = 4 };
+int pn_to_frame(int kind, int H, int W, const float* x, int64_t cs, int64_t ps, float scale, float near_, float range,
+                const float* lut, float* work, uint8_t* out, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -14,6 +14,8 @@ Public surface (mirrors the reference's names):
     extract_mesh                  Mesh(vertices, faces, normals, colors) of {sigma > level} over a box
     lighting                      spatially-varying lighting: HDR light probes, SH projection, exact and SH irradiance,
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
+    views                         novel views: perspective cameras and ray pools, camera paths, render_view / render_path
+                                  and the reference's viewable uint8 frames (HIP kernels)
     concurrent_step               one training step as concurrent sub-batches on separate HIP streams
     install                       register PanoMipNeRF / MipNeRF under the reference's import paths (zero-edit drop-in)
 """
@@ -30,5 +32,6 @@ from .metrics import evaluate_panorama  # noqa
 from . import geometry  # noqa
 from .geometry import extract_mesh  # noqa
 from . import lighting  # noqa
+from . import views  # noqa
 from .parallel import concurrent_step  # noqa
 from .install import install, uninstall  # noqa

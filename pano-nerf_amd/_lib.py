@@ -73,6 +73,8 @@ SIGNATURES = {
     "pn_probe_sh": ("i", "liip" + "lll" + "pppp" + "p"),
     "pn_probe_irradiance": ("i", "liip" + "lll" + "pp" + "lpi" + "p" + "p"),
     "pn_sh_volume_irradiance": ("i", "iii" + "f" * 6 + "plppp" + "p"),
+    "pn_sample_pinhole_rays": ("i", "liiipppffp" + "p" * 9 + "p"),
+    "pn_to_frame": ("i", "iiipllfffppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

@@ -104,4 +104,17 @@ PnPack pn_pack_layout();
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
+// tone mapping of the LDR metrics (pn_metrics.hip) and the LDR frames (pn_views.hip): one definition, the same bytes
+// torch.clamp(x, 0, 1): NaN stays NaN (fminf / fmaxf would drop it)
+__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+
+// hdr_to_ldr (utils/surface_rendering.py:319-341) as the reference evaluates it on fp32 tensors: ACES, clamp,
+// optional uint8 truncation, then ** (1 / 2.2).  Separate fp32 operations (the library builds with -ffp-contract=off).
+__device__ __forceinline__ float tonemap(float c, int mode) {
+    if (mode == 0) return c;
+    float a = clamp01((c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f));
+    if (mode == 2) a = truncf(a * 255.f) / 255.f;
+    return powf(a, (float)(1.0 / 2.2));
+}
+
 static inline int64_t pn_pad(int64_t m) { return (m + PN_ROW_PAD - 1) / PN_ROW_PAD * PN_ROW_PAD; }

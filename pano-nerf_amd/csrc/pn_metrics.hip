@@ -32,17 +32,7 @@ inline unsigned elem_grid(int64_t n) {
 }
 #define ST(s) ((hipStream_t)(s))
 
-// torch.clamp(x, 0, 1): NaN stays NaN (fminf / fmaxf would drop it)
-__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-
-// hdr_to_ldr (utils/surface_rendering.py:319-341) as the reference evaluates it on fp32 tensors: ACES, clamp,
-// optional uint8 truncation, then ** (1 / 2.2).  Separate fp32 operations (the library builds with -ffp-contract=off).
-__device__ __forceinline__ float tonemap(float c, int mode) {
-    if (mode == 0) return c;
-    float a = clamp01((c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f));
-    if (mode == 2) a = truncf(a * 255.f) / 255.f;
-    return powf(a, (float)(1.0 / 2.2));
-}
+// clamp01 and tonemap (hdr_to_ldr) live in pn_common.h: pn_views.hip's LDR frames use the same arithmetic
 
 __device__ __forceinline__ float load(const Img& m, int c, int64_t pix) { return tonemap(m.p[c * m.cs + pix * m.ps], m.tone); }
 

@@ -1,0 +1,544 @@
+"""Novel views of a trained model: perspective (pinhole) cameras, camera paths and viewable frames.
+
+Pano-NeRF's models are trained on panoramas, but what a user renders from a trained model is a new view.  This module
+renders one (or a whole path of them) and turns the renderer's outputs into the uint8 images the reference's validation
+writes.  Ray generation and frames run on the HIP device through ``pn_views.hip`` (the renderer's own entry points do the
+rest), under ``torch.no_grad()`` on the current stream; CPU tensors raise, there is no host fallback.  Cameras and paths
+are host-side numpy.
+
+    perspective_camera(h, w, focal | fov_x_deg | pix2cam)   PinholeCamera(h, w, pix2cam [3, 3] fp32)
+    pano_camera(h, w)                           PanoCamera(h, w): the equirectangular camera of generate_pano_rays
+    generate_perspective_rays(camera, c2w, ...) Rays of [H W, C] device tensors (datasets/base_datasets.py:118-265)
+    PerspectiveRayPool(camera, c2ws, images)    the pinhole counterpart of DeviceRayPool: take / sample / rays / len
+    interpolate_path(c2ws, n_views)             gen_render_path (utils/vis.py:136-165), numpy only
+    spiral_path(radii, focus_depth, n_poses)    create_spiral_poses (utils/vis.py:168-200), as 4x4 matrices
+    spheric_path(radius, n_poses)               create_spheric_poses (utils/vis.py:203-242), as 4x4 matrices
+    look_at(eye, target, up)                    a c2w whose -z looks from eye at target
+    to_frame(image, kind, near, far, exposure)  uint8 [H, W, 3] of one render_image output (utils/vis.py:13-41)
+    render_view(model, camera, c2w, ...)        dict of [1, C, H, W] outputs named as render_image's
+    render_path(model, camera, poses, ...)      dict kind -> uint8 [n, H, W, 3] frames (or PNG / EXR files)
+
+Conventions (pixel directions, radii, frame bytes) are stated in include/panonerf_hip.h.
+"""
+import collections
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .geometry import _model_device
+from .rays import Rays, _DIMS
+
+PinholeCamera = collections.namedtuple("PinholeCamera", ["h", "w", "pix2cam"])
+PanoCamera = collections.namedtuple("PanoCamera", ["h", "w"])
+
+_FRAME_KINDS = {"ldr": 0, "ldr_gt": 1, "depth": 2, "normal": 3, "albedo": 4}
+# render_view outputs -> the render_image names they fill
+_OUTPUTS = {"rgb": ("coarse_rgb", "fine_rgb"), "depth": ("coarse_dep", "fine_dep"), "normal": ("fine_nor",),
+            "albedo": ("albedo",), "surface": ("surface_rgb",), "shading": ("shading",)}
+_SURF = ("albedo", "surface", "shading")
+# render_path kinds: (render_view output, render_image name, to_frame kind); systems/panonerf_system.py:77-131
+_PATH_KINDS = {"ldr": ("rgb", "fine_rgb", "ldr"), "ldr_surf": ("surface", "surface_rgb", "ldr"),
+               "depth": ("depth", "fine_dep", "depth"), "normal": ("normal", "fine_nor", "normal"),
+               "albedo": ("albedo", "albedo", "albedo"), "hdr": ("rgb", "fine_rgb", None)}
+_PATH_GROUP_RAYS = 1 << 22  # rays rendered per group of frames in render_path (~220 MB of outputs at most)
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _cuda_device(device):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (got %s); there is no CPU fallback" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+# ---------------------------------------------------------------------------------------------------------- cameras
+def _hw(height, width, min_w=2):
+    h, w = int(height), int(width)
+    if h < 2 or w < min_w:
+        raise ValueError(f"a camera needs height >= 2 and width >= {min_w}; got {height} x {width}")
+    return h, w
+
+
+def perspective_camera(height, width, focal=None, fov_x_deg=None, pix2cam=None):
+    """PinholeCamera(h, w, pix2cam [3, 3] fp32).  With a focal length (pixels) or a horizontal field of view (degrees) the
+    Blender matrix: pixel (x + 1/2, y + 1/2, 1) -> ((x + 1/2 - w/2) / f, -(y + 1/2 - h/2) / f, -1), x right, y up, looking
+    along -z (datasets/base_datasets.py:216-265; focal = w / 2 / tan(fov / 2) as :212-213).  With pix2cam, that matrix as
+    given (the Multicam form, :118-170).  h, w >= 2: the cone radius takes the next row's direction."""
+    h, w = _hw(height, width)
+    if pix2cam is not None:
+        if focal is not None or fov_x_deg is not None:
+            raise ValueError("give pix2cam, or one of focal and fov_x_deg, not both")
+        m = np.asarray(pix2cam, dtype=np.float32)
+        if m.shape != (3, 3) or not np.isfinite(m).all():
+            raise ValueError(f"pix2cam must be a finite 3x3 matrix; got shape {m.shape}")
+        return PinholeCamera(h, w, np.ascontiguousarray(m))
+    if (focal is None) == (fov_x_deg is None):
+        raise ValueError("give exactly one of focal and fov_x_deg (or pix2cam)")
+    if focal is None:
+        fov = float(fov_x_deg)
+        if not 0.0 < fov < 180.0:
+            raise ValueError(f"fov_x_deg must lie in (0, 180); got {fov_x_deg!r}")
+        focal = 0.5 * w / math.tan(0.5 * math.radians(fov))
+    f = float(focal)
+    if not (f > 0.0 and math.isfinite(f)):
+        raise ValueError(f"focal must be positive and finite; got {focal!r}")
+    m = np.array([[1.0 / f, 0.0, -0.5 * w / f], [0.0, -1.0 / f, 0.5 * h / f], [0.0, 0.0, -1.0]])
+    return PinholeCamera(h, w, m.astype(np.float32))
+
+
+def pano_camera(height, width):
+    """PanoCamera(h, w): the equirectangular camera of generate_pano_rays (pn_raygen_pano), for render_view / render_path."""
+    return PanoCamera(*_hw(height, width, 3))
+
+
+def _camera(camera):
+    if isinstance(camera, PinholeCamera):
+        if np.asarray(camera.pix2cam).shape != (3, 3):
+            raise ValueError("PinholeCamera.pix2cam must be 3x3")
+        return camera
+    if isinstance(camera, PanoCamera):
+        return camera
+    raise ValueError(f"camera must come from perspective_camera or pano_camera; got {type(camera).__name__}")
+
+
+def _c2w_stack(c2ws, single=False):
+    """[n, 4, 4] float64 of one c2w ([4, 4] or [3, 4]) or a sequence of them; ValueError on any other shape."""
+    a = np.asarray(c2ws, dtype=np.float64)
+    if single:
+        a = a[None]
+    if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] not in ((4, 4), (3, 4)):
+        raise ValueError("a c2w must be a 4x4 or 3x4 matrix" + ("" if single else " (c2ws: [n, 4, 4] or [n, 3, 4])")
+                         + f"; got shape {np.shape(c2ws)}")
+    if not np.isfinite(a).all():
+        raise ValueError("c2w holds a non-finite value")
+    out = np.tile(np.eye(4), (a.shape[0], 1, 1))
+    out[:, :3, :] = a[:, :3, :]
+    return out
+
+
+def _device_cams(camera, c2ws, dev):
+    """(pix2cams [n, 9] or None, c2ws [n, 16]) fp32 device arrays for the ray kernels."""
+    n = c2ws.shape[0]
+    c = torch.from_numpy(np.ascontiguousarray(c2ws.astype(np.float32).reshape(n, 16))).to(dev)
+    if isinstance(camera, PanoCamera):
+        return None, c
+    p = np.tile(np.asarray(camera.pix2cam, np.float32).reshape(1, 9), (n, 1))
+    return torch.from_numpy(p).to(dev), c
+
+
+def _sample(camera, n_cam, pix2cams, c2ws, idx, near, far, rgb_pool, dev):
+    """Rays (and gathered colours) of the (camera, pixel) rows idx [B] int64 (device)."""
+    B = int(idx.numel())
+    outs = [torch.empty(B, d, dtype=torch.float32, device=dev) for d in _DIMS]
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if rgb_pool is not None else None
+    ptrs = [x.data_ptr() for x in outs]
+    with torch.cuda.device(dev):
+        if isinstance(camera, PanoCamera):
+            _lib.call("pn_sample_pano_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), c2ws.data_ptr(), float(near),
+                      float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
+        else:
+            _lib.call("pn_sample_pinhole_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), pix2cams.data_ptr(),
+                      c2ws.data_ptr(), float(near), float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
+    return Rays(*outs), rgb
+
+
+def generate_perspective_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
+    """One pinhole camera -> Rays of [H W, C] fp32 device tensors (row-major pixels): pn_sample_pinhole_rays over
+    idx = arange(H W), the arithmetic every pinhole ray of this module comes from."""
+    if not isinstance(camera, PinholeCamera):
+        raise ValueError("camera must come from perspective_camera")
+    _camera(camera)
+    c2ws = _c2w_stack(c2w, single=True)
+    dev = _cuda_device(device)
+    p, c = _device_cams(camera, c2ws, dev)
+    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
+    return _sample(camera, 1, p, c, idx, near, far, None, dev)[0]
+
+
+class PerspectiveRayPool:
+    """Batch sampler over the pixels of a set of pinhole cameras sharing one PinholeCamera: the counterpart of
+    DeviceRayPool for Blender- or Multicam-style data.  No ray pool is stored: a batch is one kernel
+    (pn_sample_pinhole_rays) that regenerates the drawn rows' rays from the camera matrices.  Only the target colours
+    (``images`` = [H, W, 3] arrays per camera, optional) are kept and gathered."""
+
+    def __init__(self, camera, c2ws, images=None, near=0.0, far=10.0, device="cuda"):
+        if not isinstance(camera, PinholeCamera):
+            raise ValueError("camera must come from perspective_camera")
+        self.camera = _camera(camera)
+        self.h, self.w = camera.h, camera.w
+        self.near, self.far = float(near), float(far)
+        self.c2ws_host = _c2w_stack(c2ws).astype(np.float32)
+        self.device = _cuda_device(device)
+        self.n_cam = self.c2ws_host.shape[0]
+        self.pix2cams, self.c2ws = _device_cams(camera, self.c2ws_host, self.device)
+        self.rgbs = None
+        if images is not None:
+            self.rgbs = torch.cat([torch.as_tensor(im, dtype=torch.float32).reshape(-1, 3) for im in images], 0).to(self.device)
+            if self.rgbs.shape[0] != len(self):
+                raise ValueError("images must be [H, W, 3] per camera")
+
+    def __len__(self):
+        return self.n_cam * self.h * self.w
+
+    @property
+    def rays(self):
+        """The materialised pool (camera-major, row-major pixels) - for tests and one-off uses; NOT cached."""
+        return self.take(torch.arange(len(self), dtype=torch.int64, device=self.device))[0]
+
+    def take(self, idx):
+        """Rays (and target colours) of the pool rows `idx` (int64 device tensor, row = camera * H * W + pixel)."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
+        return _sample(self.camera, self.n_cam, self.pix2cams, self.c2ws, idx, self.near, self.far, self.rgbs, self.device)
+
+    def sample(self, batch_size, generator=None):
+        """-> (Rays of [B, C], rgb [B, 3] or None), all on the device."""
+        idx = torch.randint(0, len(self), (int(batch_size),), device=self.device, generator=generator)
+        return self.take(idx)
+
+
+# ------------------------------------------------------------------------------------------------------------ paths
+def _euler_xyz_from_matrix(m):
+    """[3] extrinsic x-y-z Euler angles (degrees) of a rotation matrix R = Rz(c) Ry(b) Rx(a), in scipy's ranges
+    (a, c in [-180, 180], b in [-90, 90])."""
+    a = math.atan2(m[2, 1], m[2, 2])
+    b = math.atan2(-m[2, 0], math.hypot(m[0, 0], m[1, 0]))
+    c = math.atan2(m[1, 0], m[0, 0])
+    return np.degrees(np.array([a, b, c]))
+
+
+def _matrix_from_euler_xyz(angles):
+    a, b, c = np.radians(angles)
+    ca, sa, cb, sb, cc, sc = math.cos(a), math.sin(a), math.cos(b), math.sin(b), math.cos(c), math.sin(c)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]])
+    ry = np.array([[cb, 0.0, sb], [0.0, 1.0, 0.0], [-sb, 0.0, cb]])
+    rz = np.array([[cc, -sc, 0.0], [sc, cc, 0.0], [0.0, 0.0, 1.0]])
+    return rz @ ry @ rx
+
+
+def interpolate_path(c2ws, n_views=30):
+    """gen_render_path (utils/vis.py:136-165): [N (n_views // 3), 4, 4] float64 c2ws that run through the N poses and back
+    to the first, interpolating Euler 'xyz' angles (extrinsic, degrees) and positions linearly, n_views // 3 per leg.
+    As upstream, an angle more than 180 degrees away from the FIRST pose's is unwrapped by +360 (only +360, and only
+    relative to the first pose).  Rotations must be proper (orthonormal); pitch near +-90 degrees is gimbal lock."""
+    c = _c2w_stack(c2ws)
+    k = int(n_views) // 3
+    if k < 1:
+        raise ValueError(f"n_views must be >= 3; got {n_views!r}")
+    weight = np.linspace(1.0, .0, k, endpoint=False).reshape(-1, 1)
+    rot, pos, rot_i, pos_i = [], [], [], []
+    for i in range(c.shape[0]):
+        e = _euler_xyz_from_matrix(c[i, :3, :3]).reshape(1, 3)
+        if i:
+            mask = np.abs(e - rot[0]) > 180
+            e[mask] += 360.0
+        rot.append(e)
+        pos.append(c[i, :3, 3:].reshape(1, 3))
+        if i:
+            rot_i.append(weight * rot[i - 1] + (1.0 - weight) * rot[i])
+            pos_i.append(weight * pos[i - 1] + (1.0 - weight) * pos[i])
+    rot_i.append(weight * rot[-1] + (1.0 - weight) * rot[0])
+    pos_i.append(weight * pos[-1] + (1.0 - weight) * pos[0])
+    angles, positions = np.concatenate(rot_i), np.concatenate(pos_i)
+    out = np.tile(np.eye(4), (angles.shape[0], 1, 1))
+    for j in range(angles.shape[0]):
+        out[j, :3, :3] = _matrix_from_euler_xyz(angles[j])
+        out[j, :3, 3] = positions[j]
+    return out
+
+
+def _normalize(v):
+    return v / np.linalg.norm(v)
+
+
+def _to44(poses):
+    p = np.asarray(poses, dtype=np.float64)
+    out = np.tile(np.eye(4), (p.shape[0], 1, 1))
+    out[:, :3, :] = p
+    return out
+
+
+def spiral_path(radii, focus_depth, n_poses=120):
+    """create_spiral_poses (utils/vis.py:168-200) as [n_poses, 4, 4] float64: two turns of a spiral of the given radii
+    (3 values) around the origin, every pose looking at (0, 0, -focus_depth)."""
+    poses = []
+    for t in np.linspace(0, 4 * np.pi, int(n_poses) + 1)[:-1]:
+        center = np.array([np.cos(t), -np.sin(t), -np.sin(0.5 * t)]) * radii
+        z = _normalize(center - np.array([0, 0, -focus_depth]))
+        y_ = np.array([0, 1, 0])
+        x = _normalize(np.cross(y_, z))
+        y = np.cross(z, x)
+        poses += [np.stack([x, y, z, center], 1)]
+    return _to44(np.stack(poses, 0))
+
+
+def spheric_path(radius, n_poses=120):
+    """create_spheric_poses (utils/vis.py:203-242) as [n_poses, 4, 4] float64: a circle of poses at distance `radius`,
+    looking 36 degrees downwards at the origin."""
+    def trans_t(t):
+        return np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, t], [0, 0, 0, 1]])
+
+    def rot_phi(phi):
+        return np.array([[1, 0, 0, 0], [0, np.cos(phi), -np.sin(phi), 0], [0, np.sin(phi), np.cos(phi), 0], [0, 0, 0, 1]])
+
+    def rot_theta(th):
+        return np.array([[np.cos(th), 0, -np.sin(th), 0], [0, 1, 0, 0], [np.sin(th), 0, np.cos(th), 0], [0, 0, 0, 1]])
+
+    poses = []
+    for th in np.linspace(0, 2 * np.pi, int(n_poses) + 1)[:-1]:
+        c2w = rot_theta(th) @ rot_phi(-np.pi / 5) @ trans_t(radius)
+        c2w = np.array([[-1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]]) @ c2w
+        poses += [c2w[:3]]
+    return _to44(np.stack(poses, 0))
+
+
+def look_at(eye, target, up=(0, 1, 0)):
+    """[4, 4] float64 c2w at `eye` whose -z axis points at `target` (the axis construction of create_spiral_poses):
+    z = normalize(eye - target), x = normalize(up x z), y = z x x; right-handed, x right, y up, as perspective_camera.
+
+    The same c2w given to an equirectangular camera (pn_raygen_pano, generate_pano_rays) looks along -z at the centre of
+    the panorama: the corner shared by pixels (H/2 - 1, W/2 - 1) and (H/2, W/2) (theta = -pi, phi = pi / 2); column
+    3 W / 4 looks along +x and row 0 towards +y.  So a perspective view with this c2w shows the middle of the panorama
+    rendered at the same pose."""
+    e, t, u = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    z = e - t
+    if not np.linalg.norm(z) > 0:
+        raise ValueError("eye and target coincide")
+    z = _normalize(z)
+    x = np.cross(u, z)
+    if not np.linalg.norm(x) > 1e-12:
+        raise ValueError("up is parallel to the viewing direction")
+    x = _normalize(x)
+    y = np.cross(z, x)
+    out = np.eye(4)
+    out[:3, :4] = np.stack([x, y, z, e], 1)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------- frames
+def _jet_lut():
+    """matplotlib's 'jet' lookup table ([256, 3], utils/vis.py:13-22 hotmap) from its published segment data, with
+    LinearSegmentedColormap's float64 arithmetic, then rounded to float32 as torch.Tensor(h) rounds it."""
+    segments = (((0., 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1., 0.5, 0.5)),
+                ((0., 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.64, 1, 1), (0.91, 0, 0), (1., 0, 0)),
+                ((0., 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1., 0, 0)))
+    N = 256
+    cols = []
+    for data in segments:
+        a = np.array(data)
+        x, y0, y1 = a[:, 0] * (N - 1), a[:, 1], a[:, 2]
+        xind = (N - 1) * np.linspace(0, 1, N) ** 1.0
+        ind = np.searchsorted(x, xind)[1:-1]
+        distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        lut = np.concatenate([[y1[0]], distance * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]])
+        cols.append(np.clip(lut, 0.0, 1.0))
+    return np.stack(cols, 1).astype(np.float32)
+
+
+JET_LUT = _jet_lut()
+_LUTS = {}
+
+
+def _lut(dev):
+    key = str(dev)
+    if key not in _LUTS:
+        _LUTS[key] = torch.from_numpy(JET_LUT.reshape(-1).copy()).to(dev)
+    return _LUTS[key]
+
+
+def to_frame(image, kind, near=None, far=None, exposure=0.0):
+    """uint8 [H, W, 3] device tensor: the bytes the reference's validation writes for one [1, C, H, W] render_image
+    output (systems/panonerf_system.py:77-131 through save_results, utils/vis.py:25-41), read in place through its strides.
+
+        "ldr"     hdr_to_ldr(x, dtype='uint8')   (pred_ldr, pred_ldr_surf)
+        "ldr_gt"  hdr_to_ldr(x)                  (gt_ldr: no quantisation)
+        "depth"   hotmap((d - near) / (far - near)), min / max over the image (C = 1; needs near and far)
+        "normal"  (F.normalize(n, dim=1) + 1) / 2
+        "albedo"  albedo, clamped to [0, 1]
+
+    exposure scales the HDR input of "ldr" / "ldr_gt" by 2 ** exposure first (0: the reference's bytes).  A NaN depth
+    anywhere gives a black frame, as upstream's hotmap does."""
+    if kind not in _FRAME_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_FRAME_KINDS)}; got {kind!r}")
+    if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] != 1:
+        raise ValueError(f"image must be a [1, C, H, W] tensor; got {getattr(image, 'shape', type(image))}")
+    C, H, W = (int(s) for s in image.shape[1:])
+    want = 1 if kind == "depth" else 3
+    if C != want:
+        raise ValueError(f"a {kind!r} frame takes {want} channel(s); got {C}")
+    if H < 1 or W < 1:
+        raise ValueError("image is empty")
+    if image.device.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (the image is on %s); there is no CPU fallback"
+                           % image.device)
+    near_f, range_f = 0.0, 1.0
+    if kind == "depth":
+        if near is None or far is None:
+            raise ValueError("a depth frame needs near and far")
+        near_f, range_f = float(near), float(far - near)  # far - near in double, rounded once (as Python does upstream)
+    dev = image.device
+    x = image.detach()[0]
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    cs, sh, sw = x.stride()
+    if sh != W * sw:  # rows are not evenly spaced pixels: read a copy
+        x = x.contiguous()
+        cs, sh, sw = x.stride()
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        work = torch.empty(2, dtype=torch.float32, device=dev) if kind == "depth" else None
+        _lib.call("pn_to_frame", _FRAME_KINDS[kind], H, W, x.data_ptr(), cs, sw, float(2.0 ** float(exposure)), near_f,
+                  range_f, _lib.ptr(_lut(dev) if kind == "depth" else None), _lib.ptr(work), out.data_ptr(), _stream(dev))
+    return out
+
+
+# -------------------------------------------------------------------------------------------------------- rendering
+def _flags(model, outputs, env_rays):
+    """-> (surf, normals) of the least renderer configuration that yields `outputs`."""
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in _OUTPUTS]
+    if bad or not outputs:
+        raise ValueError(f"outputs must be a non-empty subset of {sorted(_OUTPUTS)}; got {outputs!r}")
+    surf = any(o in _SURF for o in outputs)
+    if surf:
+        if model._NC != 5:
+            raise ValueError(f"{type(model).__name__} has no surface outputs ({', '.join(_SURF)}): use a PanoMipNeRF")
+        if env_rays is None:
+            raise ValueError("surface outputs need env_rays (e.g. generate_lit_rays(10, radius))")
+    return surf, surf or "normal" in outputs
+
+
+def _render_rows(model, camera, pix2cams, c2ws, n_cam, first, count, env_rays, surf, normals, near, far, chunk, bufs,
+                 dev, streams=2):
+    """Render rays [first, first + count) of the (frame, pixel) index space into bufs[name][0:count].  The chunks are
+    dealt to `streams` HIP streams with the weight packs built once and frozen, as render_image deals them (the same
+    kernels on the same rays: the same bits)."""
+    starts = list(range(0, count, chunk))
+    cur = torch.cuda.current_stream(dev)
+    lanes = [cur]
+    forked = streams > 1 and len(starts) > 1
+    if forked:
+        from .parallel import _streams
+        if surf:  # the cached fp32 env rays are made on this stream, before the other lanes fork from it
+            model._env_inputs(env_rays, True, dev)
+        from .render import _planes_of
+        planes = _planes_of(model.mlp_mode)
+        model.mlp._frozen = False
+        if planes:
+            model.mlp.chain_packed(cur.cuda_stream, planes)
+        else:
+            model.mlp.packed(cur.cuda_stream)
+        model.mlp._frozen = True
+        lanes += _streams(dev, min(int(streams), len(starts)) - 1)
+        for s in lanes[1:]:
+            s.wait_stream(cur)
+    try:
+        for i, s in enumerate(starts):
+            with torch.cuda.stream(lanes[i % len(lanes)]):
+                n = min(chunk, count - s)
+                idx = torch.arange(first + s, first + s + n, dtype=torch.int64, device=dev)
+                rays, _ = _sample(camera, n_cam, pix2cams, c2ws, idx, near, far, None, dev)
+                outs, _ = model._run(rays, env_rays if surf else None, False, False, surf, False, normals)
+                comp0, dist0, comp1, dist1, _, normal, albedo, surface, _, shading = outs
+                got = dict(coarse_rgb=comp0, fine_rgb=comp1, coarse_dep=dist0, fine_dep=dist1, fine_nor=normal,
+                           albedo=albedo, surface_rgb=surface, shading=shading)
+                for name, buf in bufs.items():
+                    buf[s:s + n].copy_(got[name].reshape(n, -1))
+    finally:
+        if forked:
+            model.mlp._frozen = False
+    for s in lanes[1:]:
+        cur.wait_stream(s)
+
+
+def _setup(model, camera, chunk_rays):
+    camera = _camera(camera)
+    dev = _model_device(model)
+    if dev.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.views renders on a HIP device only (the model is on %s); there is no CPU "
+                           "fallback" % dev)
+    chunk = int(chunk_rays)
+    if chunk <= 0:
+        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
+    return camera, dev, chunk
+
+
+_WIDTH = dict(coarse_rgb=3, fine_rgb=3, coarse_dep=1, fine_dep=1, fine_nor=3, albedo=3, surface_rgb=3, shading=3)
+
+
+def render_view(model, camera, c2w, env_rays=None, outputs=("rgb", "depth", "normal"), near=0.0, far=10.0,
+                chunk_rays=32768):
+    """One view -> dict of [1, C, H, W] fp32 tensors named as render_image's (coarse_rgb, fine_rgb for "rgb"; coarse_dep,
+    fine_dep for "depth"; fine_nor for "normal"; albedo, surface_rgb, shading).  camera: perspective_camera(...) or
+    pano_camera(h, w).  Runs the least renderer configuration the outputs need: rgb and depth take the two levels only,
+    "normal" adds the density-gradient sweep, albedo / surface / shading add the light gather (a PanoMipNeRF and env_rays
+    required).  PanoMipNeRF and MipNeRF both work."""
+    camera, dev, chunk = _setup(model, camera, chunk_rays)
+    surf, normals = _flags(model, outputs, env_rays)
+    c2ws = _c2w_stack(c2w, single=True)
+    H, W = camera.h, camera.w
+    names = [k for o in outputs for k in _OUTPUTS[o]]
+    bufs = {k: torch.empty(H * W, _WIDTH[k], dtype=torch.float32, device=dev) for k in dict.fromkeys(names)}
+    with torch.no_grad(), torch.cuda.device(dev):
+        p, c = _device_cams(camera, c2ws, dev)
+        _render_rows(model, camera, p, c, 1, 0, H * W, env_rays, surf, normals, near, far, chunk, bufs, dev)
+    return {k: v.view(1, H, W, -1).permute(0, 3, 1, 2) for k, v in bufs.items()}
+
+
+def render_path(model, camera, poses, env_rays=None, kinds=("ldr", "depth", "normal"), near=0.0, far=10.0, exposure=0.0,
+                out_dir=None, chunk_rays=32768):
+    """Render every pose of poses ([n, 4, 4] or [n, 3, 4] c2ws) and turn the outputs into frames: dict kind -> uint8
+    [n, H, W, 3] device tensor, each frame to_frame of the render_view output the reference's validation takes for it
+    (ldr <- fine_rgb, ldr_surf <- surface_rgb, depth <- fine_dep with near / far, normal <- fine_nor, albedo <- albedo);
+    "hdr" is fine_rgb itself as fp32 [n, H, W, 3].  Rays are indexed over (frame, pixel), so small frames share full
+    chunks.  With out_dir, frames go to out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr) as they complete and the returned
+    dict is empty."""
+    from . import io_exr
+    camera, dev, chunk = _setup(model, camera, chunk_rays)
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in _PATH_KINDS]
+    if bad or not kinds:
+        raise ValueError(f"kinds must be a non-empty subset of {sorted(_PATH_KINDS)}; got {kinds!r}")
+    outputs = tuple(dict.fromkeys(_PATH_KINDS[k][0] for k in kinds))
+    surf, normals = _flags(model, outputs, env_rays)
+    c2ws = _c2w_stack(poses)
+    n, H, W = c2ws.shape[0], camera.h, camera.w
+    HW = H * W
+    names = tuple(dict.fromkeys(_PATH_KINDS[k][1] for k in kinds))
+    group = max(1, min(n, _PATH_GROUP_RAYS // HW))
+    frames = {}
+    if out_dir is None:
+        frames = {k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev) for k in kinds}
+    else:
+        for k in kinds:
+            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    with torch.no_grad(), torch.cuda.device(dev):
+        p, c = _device_cams(camera, c2ws, dev)
+        for g0 in range(0, n, group):
+            nf = min(group, n - g0)
+            bufs = {k: torch.empty(nf * HW, _WIDTH[k], dtype=torch.float32, device=dev) for k in names}
+            _render_rows(model, camera, p, c, n, g0 * HW, nf * HW, env_rays, surf, normals, near, far, chunk, bufs,
+                         dev)
+            for f in range(nf):
+                i = g0 + f
+                for k in kinds:
+                    src = bufs[_PATH_KINDS[k][1]][f * HW:(f + 1) * HW].view(H, W, -1)
+                    if k == "hdr":
+                        frame = src
+                    else:
+                        frame = to_frame(src[None].permute(0, 3, 1, 2), _PATH_KINDS[k][2], near, far,
+                                         exposure if _PATH_KINDS[k][2] == "ldr" else 0.0)
+                    if out_dir is None:
+                        frames[k][i].copy_(frame)
+                    elif k == "hdr":
+                        io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
+                    else:
+                        io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
+    return frames
