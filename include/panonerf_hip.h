@@ -484,6 +484,25 @@ enum { PN_FRAME_LDR = 0, PN_FRAME_LDR_GT = 1, PN_FRAME_DEPTH = 2, PN_FRAME_NORMA
 int pn_to_frame(int kind, int H, int W, const float* x, int64_t cs, int64_t ps, float scale, float near_, float range,
                 const float* lut, float* work, uint8_t* out, void* stream);
 
+/* ---- dataset ingest (pn_data.hip) ---------------------------------------------------------------------------------
+ * planes: the channel planes of one decoded scanline OpenEXR file as stored, [Hs][n_ch][Ws] (line, channel, column),
+ * fp16 (is_half != 0) or fp32, on the device.  out: [Hs / factor, Ws / factor, C] fp32 interleaved, C = 1 for
+ * PN_INGEST_DEPTH and 3 otherwise.  Output channel k reads plane c0 / c1 / c2 (R, G, B by plane index; depth reads c0 only).
+ * Each output value is the mean of its factor x factor source block (cv2.resize INTER_AREA at an integer factor that
+ * divides both sides; datasets/pano_datasets.py:76-78): HALF widened to fp32, ONE fp32 accumulator per channel over rows
+ * then columns in index order, divided by factor^2 - a fixed order, so repeated calls give the same bits.  Then the
+ * fix-up of datasets/pano_datasets.py:100-116:
+ *   PN_INGEST_IMAGE   NaN -> 0, then clip to [0, 1000]
+ *   PN_INGEST_ALBEDO  none
+ *   PN_INGEST_NORMAL  x * 2 - 1; flag != 0 (pano scenes): x and z negated (the right product with R_y(pi))
+ *   PN_INGEST_DEPTH   flag != 0 (normalize_depth): clip(d, near, far) (NaN stays NaN), then (d - near) / (far - near)
+ * One launch on `stream`; no workspace, no atomics.  Errors: PN_ERR_BAD_SHAPE (a size <= 0, factor does not divide Hs
+ * and Ws, Hs Ws n_ch >= 2^31, a plane index outside [0, n_ch), far <= near with normalised depth),
+ * PN_ERR_UNSUPPORTED (unknown kind). */
+enum { PN_INGEST_IMAGE = 0, PN_INGEST_ALBEDO = 1, PN_INGEST_NORMAL = 2, PN_INGEST_DEPTH = 3 };
+int pn_ingest_image(int Hs, int Ws, int n_ch, int is_half, const void* planes, int c0, int c1, int c2, int factor, int kind,
+                    int flag, float near_, float far_, float* out, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

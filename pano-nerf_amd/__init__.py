@@ -16,6 +16,11 @@ Public surface (mirrors the reference's names):
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
     views                         novel views: perspective cameras and ray pools, camera paths, render_view / render_path
                                   and the reference's viewable uint8 frames (HIP kernels)
+    data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
+                                  materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
+    load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
+    Trainer                       the fit loop of train.py / systems/*: step, graph replay, validation dumps, metrics,
+                                  checkpoints, resume, data-parallel ranks (python -m pano_nerf_amd.train)
     concurrent_step               one training step as concurrent sub-batches on separate HIP streams
     install                       register PanoMipNeRF / MipNeRF under the reference's import paths (zero-edit drop-in)
 """
@@ -33,5 +38,17 @@ from . import geometry  # noqa
 from .geometry import extract_mesh  # noqa
 from . import lighting  # noqa
 from . import views  # noqa
+from . import data  # noqa
+from .data import PanoScene  # noqa
+from .config import load_config  # noqa
 from .parallel import concurrent_step  # noqa
 from .install import install, uninstall  # noqa
+
+
+def __getattr__(name):
+    # `train` is also a program (python -m pano_nerf_amd.train): it is imported on first use, not with the package
+    if name in ("Trainer", "train"):
+        import importlib
+        mod = importlib.import_module(".train", __name__)
+        return mod.Trainer if name == "Trainer" else mod
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -75,6 +75,7 @@ SIGNATURES = {
     "pn_sh_volume_irradiance": ("i", "iii" + "f" * 6 + "plppp" + "p"),
     "pn_sample_pinhole_rays": ("i", "liiipppffp" + "p" * 9 + "p"),
     "pn_to_frame": ("i", "iiipllfffppp" + "p"),
+    "pn_ingest_image": ("i", "iiiipiiiiiiffpp"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

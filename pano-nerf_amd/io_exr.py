@@ -1,10 +1,15 @@
-"""Result writers for validation dumps: float32 OpenEXR and 8-bit PNG, with no third-party codec.
+"""OpenEXR reader / writer and 8-bit PNG writer for datasets and validation dumps, with no third-party codec.
 
 `utils/io_exr.py:30-47` writes an RGB float32 scanline OpenEXR through the OpenEXR python binding and
 `utils/io_exr.py:6-27` reads one back; the binding is not available here, so this module emits / parses the
 container itself (OpenEXR 2 single-part scanline file, channels B G R as FLOAT, NO_COMPRESSION, increasing Y) —
 the layout any OpenEXR reader accepts.  Parity with files written by the real library is unpinned (the library is
 absent on both boxes): the tests check the header fields and a write -> read round trip.  SURVEY.md 8f rank 4.
+
+The reader also takes what datasets contain (Blender writes ZIP-compressed, usually HALF files): FLOAT / HALF channels,
+NO_COMPRESSION / ZIPS / ZIP, any channel set, either lineOrder, any dataWindow origin.  ZIP is zlib + a byte-delta
+predictor + a two-halves byte interleave, all undone here.  The codec is checked against this writer and against an
+independent encoder in the tests, NOT against files of the OpenEXR library: that parity stays unpinned too.
 """
 import struct
 import zlib
@@ -18,41 +23,91 @@ def _attr(name, typ, payload):
     return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(payload)) + payload
 
 
-def write_exr(filename, data):
-    """data: float32 [H, W, 3] or [H, W, 1] (grey is replicated to R, G, B like upstream)."""
+_COMPRESSION = {"none": 0, "zips": 2, "zip": 3}
+_LINES = {0: 1, 2: 1, 3: 16}  # scanlines per block
+_CODECS = {1: "RLE", 4: "PIZ", 5: "PXR24", 6: "B44", 7: "B44A", 8: "DWAA", 9: "DWAB"}
+_PIXEL = {0: ("uint", np.uint32), 1: ("half", np.float16), 2: ("float", np.float32)}
+
+
+def _zip_pack(raw):
+    """OpenEXR's ZIP block: bytes split into (even, odd) halves, byte-delta predictor, deflate.  A block that does not
+    shrink is stored raw."""
+    a = np.frombuffer(raw, np.uint8)
+    t = np.concatenate([a[0::2], a[1::2]])
+    d = t.copy()
+    d[1:] = t[1:] - t[:-1] + np.uint8(128)  # uint8 arithmetic wraps mod 256
+    out = zlib.compress(d.tobytes(), 6)
+    return out if len(out) < len(raw) else raw
+
+
+def _zip_unpack(blob, raw_size):
+    if len(blob) == raw_size:  # stored raw
+        return blob
+    d = np.frombuffer(zlib.decompress(blob), np.uint8).copy()
+    if d.size != raw_size:
+        raise ValueError(f"ZIP block inflates to {d.size} bytes, {raw_size} expected")
+    d[1:] -= np.uint8(128)
+    t = np.cumsum(d, dtype=np.uint8)  # t[i] = t[i-1] + d[i] - 128 mod 256
+    half = (raw_size + 1) // 2
+    out = np.empty(raw_size, np.uint8)
+    out[0::2] = t[:half]
+    out[1::2] = t[half:]
+    return out.tobytes()
+
+
+def write_exr(filename, data, *, compression="none", half=False):
+    """data: float32 [H, W, 3] or [H, W, 1] (grey is replicated to R, G, B like upstream).  `compression` is "none",
+    "zips" (one line per block) or "zip" (16 lines per block); `half=True` stores HALF channels (values are rounded).
+    The defaults write the uncompressed FLOAT file this function has always written, byte for byte."""
     assert filename.endswith(".exr"), "extension must be .exr"
     data = np.asarray(data)
     assert data.dtype == np.float32, f"data type is {data.dtype}, should be float32"
+    if compression not in _COMPRESSION:
+        raise ValueError(f"compression must be one of {sorted(_COMPRESSION)}, got {compression!r}")
+    comp = _COMPRESSION[compression]
     h, w, c = data.shape
     if c == 1:
         data = np.repeat(data, 3, axis=2)
-    chlist = b"".join(n + b"\0" + struct.pack("<iBBBBii", 2, 0, 0, 0, 0, 1, 1) for n in (b"B", b"G", b"R")) + b"\0"
+    ptype, esize = (1, 2) if half else (2, 4)
+    chlist = b"".join(n + b"\0" + struct.pack("<iBBBBii", ptype, 0, 0, 0, 0, 1, 1) for n in (b"B", b"G", b"R")) + b"\0"
     box = struct.pack("<iiii", 0, 0, w - 1, h - 1)
-    header = (_attr("channels", "chlist", chlist) + _attr("compression", "compression", b"\0") +
+    header = (_attr("channels", "chlist", chlist) + _attr("compression", "compression", bytes([comp])) +
               _attr("dataWindow", "box2i", box) + _attr("displayWindow", "box2i", box) +
               _attr("lineOrder", "lineOrder", b"\0") + _attr("pixelAspectRatio", "float", struct.pack("<f", 1.0)) +
               _attr("screenWindowCenter", "v2f", struct.pack("<ff", 0.0, 0.0)) +
               _attr("screenWindowWidth", "float", struct.pack("<f", 1.0)) + b"\0")
     head = struct.pack("<ii", _MAGIC, 2) + header
-    line_bytes = 3 * w * 4
-    table_at = len(head)
-    first = table_at + 8 * h
-    offsets = struct.pack("<%dQ" % h, *[first + y * (8 + line_bytes) for y in range(h)])
     bgr = np.ascontiguousarray(data[:, :, ::-1].transpose(0, 2, 1))  # [H][B,G,R][W]
+    if half:
+        bgr = bgr.astype(np.float16)
+    lines = _LINES[comp]
+    blocks = []
+    for y in range(0, h, lines):
+        raw = bgr[y:y + lines].tobytes()
+        blocks.append((y, _zip_pack(raw) if comp else raw))
+    first = len(head) + 8 * len(blocks)
+    offsets, at = [], first
+    for _, blob in blocks:
+        offsets.append(at)
+        at += 8 + len(blob)
     with open(filename, "wb") as f:
         f.write(head)
-        f.write(offsets)
-        for y in range(h):
-            f.write(struct.pack("<ii", y, line_bytes))
-            f.write(bgr[y].tobytes())
+        f.write(struct.pack("<%dQ" % len(blocks), *offsets))
+        for y, blob in blocks:
+            f.write(struct.pack("<ii", y, len(blob)))
+            f.write(blob)
 
 
-def read_exr(filename, channel=3):
-    """Reads back an uncompressed FLOAT scanline file (what write_exr produces) -> float32 [H, W, channel]."""
-    buf = open(filename, "rb").read()
+def _decode(filename):
+    """-> (list of [H, W] arrays, one per stored channel and in its stored type, names, pixel type names)."""
+    with open(filename, "rb") as f:
+        buf = f.read()
     magic, version = struct.unpack_from("<ii", buf, 0)
-    if magic != _MAGIC or (version & 0xff) != 2 or (version & 0x1e00):
-        raise ValueError("not a single-part scanline OpenEXR file")
+    if magic != _MAGIC or (version & 0xff) != 2:
+        raise ValueError("not an OpenEXR 2 file")
+    for bit, what in ((0x200, "tiled"), (0x800, "deep"), (0x1000, "multi-part")):
+        if version & bit:
+            raise NotImplementedError(f"{what} OpenEXR files are not read here (single-part scanline files only)")
     pos, attrs = 8, {}
     while buf[pos] != 0:
         end = buf.index(b"\0", pos)
@@ -64,25 +119,65 @@ def read_exr(filename, channel=3):
         attrs[name] = buf[pos + 4:pos + 4 + size]
         pos += 4 + size
     pos += 1
-    if attrs["compression"] != b"\0":
-        raise NotImplementedError("only NO_COMPRESSION files are read here")
-    names, p, ch = [], 0, attrs["channels"]
+    comp = attrs["compression"][0]
+    if comp not in _LINES:
+        raise NotImplementedError(f"OpenEXR compression {_CODECS.get(comp, comp)} is not read here "
+                                  "(NO_COMPRESSION, ZIPS and ZIP only)")
+    names, types, p, ch = [], [], 0, attrs["channels"]
     while ch[p] != 0:
         end = ch.index(b"\0", p)
+        ptype, _, xs, ys = struct.unpack_from("<i4sii", ch, end + 1)
+        if ptype not in (1, 2):
+            raise NotImplementedError(f"channel {ch[p:end].decode()!r} is {_PIXEL.get(ptype, (ptype,))[0].upper()}: "
+                                      "only HALF and FLOAT channels are read here")
+        if (xs, ys) != (1, 1):
+            raise NotImplementedError("sub-sampled channels are not read here")
         names.append(ch[p:end].decode())
-        (ptype,) = struct.unpack_from("<i", ch, end + 1)
-        if ptype != 2:
-            raise NotImplementedError("only FLOAT channels are read here")
+        types.append(ptype)
         p = end + 1 + 16
     x0, y0, x1, y1 = struct.unpack("<iiii", attrs["dataWindow"])
     w, h = x1 - x0 + 1, y1 - y0 + 1
-    offsets = struct.unpack_from("<%dQ" % h, buf, pos)
-    planes = np.empty((h, len(names), w), np.float32)
-    for off in offsets:
+    lines = _LINES[comp]
+    n_blocks = (h + lines - 1) // lines
+    offsets = struct.unpack_from("<%dQ" % n_blocks, buf, pos)
+    dts = [_PIXEL[t][1] for t in types]
+    planes = [np.empty((h, w), dt) for dt in dts]
+    line_bytes = sum(w * np.dtype(dt).itemsize for dt in dts)
+    for off in offsets:  # a block carries its own first line, so either lineOrder reads the same way
         y, nbytes = struct.unpack_from("<ii", buf, off)
-        planes[y - y0] = np.frombuffer(buf, np.float32, len(names) * w, off + 8).reshape(len(names), w)
+        rows = min(lines, y1 - y + 1)
+        if not (y0 <= y <= y1) or (y - y0) % lines:
+            raise ValueError(f"scanline block at y = {y} lies outside the dataWindow")
+        blob = buf[off + 8:off + 8 + nbytes]
+        raw = _zip_unpack(blob, rows * line_bytes) if comp else blob
+        if len(raw) != rows * line_bytes:
+            raise ValueError(f"scanline block at y = {y} holds {len(raw)} bytes, {rows * line_bytes} expected")
+        at = 0
+        for r in range(rows):
+            for plane, dt in zip(planes, dts):
+                plane[y - y0 + r] = np.frombuffer(raw, dt, w, at)
+                at += w * np.dtype(dt).itemsize
+    return planes, names, [_PIXEL[t][0] for t in types]
+
+
+def read_exr_planes(filename):
+    """The undecoded channel planes of a single-part scanline file -> (planes [H, n_ch, W], names, pixel_types).
+    `planes` has the file's pixel type (float16 or float32; a file that mixes both is widened to float32, exactly),
+    channels in stored (alphabetical) order: the layout `data.ingest_image` hands to the device."""
+    planes, names, types = _decode(filename)
+    if len(set(types)) > 1:
+        planes, types = [p.astype(np.float32) for p in planes], ["float"] * len(types)
+    return np.ascontiguousarray(np.stack(planes, axis=1)), names, types
+
+
+def read_exr(filename, channel=3):
+    """Single-part scanline OpenEXR (FLOAT or HALF channels; NO_COMPRESSION, ZIPS or ZIP; any channel set, lineOrder
+    and dataWindow origin) -> float32 [H, W, channel]: R, G, B for channel == 3, A otherwise.  Tiled, multi-part and
+    deep files, UINT channels and the codecs RLE, PIZ, PXR24, B44[A], DWAA/B raise NotImplementedError naming what was
+    found.  Files written by the OpenEXR library itself are unpinned here for the same reason as the writer's."""
+    planes, names, _ = _decode(filename)
     want = "RGB" if channel == 3 else "A"
-    return np.stack([planes[:, names.index(c), :] for c in want], axis=2)
+    return np.stack([planes[names.index(c)].astype(np.float32) for c in want], axis=2)
 
 
 def write_png(filename, img):
