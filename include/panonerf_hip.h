@@ -503,6 +503,69 @@ enum { PN_INGEST_IMAGE = 0, PN_INGEST_ALBEDO = 1, PN_INGEST_NORMAL = 2, PN_INGES
 int pn_ingest_image(int Hs, int Ws, int n_ch, int is_half, const void* planes, int c0, int c1, int c2, int factor, int kind,
                     int flag, float near_, float far_, float* out, void* stream);
 
+/* ---- virtual object insertion: mesh tracing, probe shading, shadows (pn_objects.hip) ----------------------------------
+ * Triangles: pn_tri_setup turns vertices [V, 3] + faces [F, 3] int32 into tris [F, 12] fp32 rows (v0, 0, e1 = v1 - v0, 0,
+ * e2 = v2 - v0, 0), once per mesh; a face with an index outside [0, V) becomes the all-zero triangle, which nothing hits.
+ * bsphere: 4 device floats (centre, radius) of a sphere that holds every vertex, or NULL (pn_trace_mesh only): rays and
+ * points that cannot reach it (tested in fp64 with the radius widened by 0.1 % + 1e-6) skip the triangles; the results do
+ * not depend on it.
+ * Ray / triangle test (primary and shadow rays alike): Moeller-Trumbore in fp32, separate operations in this order:
+ * p = d x e2, det = e1 . p, inv = 1 / det, s = o - v0, u = (s . p) inv, q = s x e1, v = (d . q) inv, t = (e2 . q) inv.
+ * Edge rule: a hit needs det != 0, u >= -eps, v >= -eps, u + v <= 1 + eps (all inclusive, eps = PN_OBJ_EDGE_EPS: two
+ * triangles that share an edge both own a band of 2e-6 barycentric units around it, so fp32 rounding opens no gap in
+ * a closed mesh; u and v are reported as computed, so they may lie that far outside [0, 1]) and 0 < t < +inf (exclusive),
+ * t < t_max[r] (exclusive) where t_max is given.  Two-sided: the sign of det is not looked at.  Directions are NOT
+ * normalised: t is in units of d, as the renderer's `distance`.  hit = (1 - u - v) v0 + u v1 + v v2.
+ * Tie-break: faces are visited in index order and a face replaces the best so far only when its t is smaller, so among
+ * equal t the lowest face index wins, whatever the tile size.  A miss: t = +inf, face = -1, bary = 0.
+ * Shading (pn_shade): surface_rendering (utils/surface_rendering.py:129-165) with the probe's pixels as the lights:
+ * env = probe radiance, l = the probe directions, solid_angle = omega (the tables of the lighting section), and
+ * v = -viewdirs: viewdirs are camera-to-surface unit vectors (what the renderer calls viewdirs) and the BRDF wants the
+ * direction TOWARDS the eye.  K probes [K, 3, H, W] (1 <= K <= PN_OBJ_MAX_PROBES) are blended per row with weights
+ * [R, K] (NULL with K = 1: weight 1): the light of row r is sum_k weights[r, k] L_k(pix) (surface_rendering_wlit,
+ * :168-203; shading is linear in the light).  microfacet = 0: shading = sum L relu(n . l) omega, diffuse = albedo / pi
+ * shading, specular = 0.  microfacet = 1: microfeast_brdf (:6-61) term for term - h = normalize(l + v), NoH, VoH, NoL,
+ * NoV clamped at 0, alpha = r^2, k = r^2 / 2, D = alpha^2 / (pi (NoH^2 (alpha^2 - 1) + 1)^2), F = 0.04 + 0.96
+ * 2^(-(5.55473 VoH + 6.98316) VoH), G = NoL / ((1 - k) NoL + k) NoV / ((1 - k) NoV + k), spec = D F G / (4 NoL NoV) with
+ * NaN and +inf -> 0; diffuse = albedo / pi sum L NoL omega, specular = sum spec L omega (no NoL), shading not written
+ * (pass NULL).  roughness: [R] or NULL (then roughness_all for every row).  rgb = fl(diffuse) + fl(specular).  All of it
+ * in fp64 on the fp32 inputs, pixels in order, rounded once per output.
+ * Shadow (pn_shadow_ratio): for scene point x with unit normal n under ONE probe [3, H, W]: E(S) = sum_{pix in S}
+ * mean_c L_c(pix) max(0, n . l_pix) omega_pix; ratio = E(unoccluded) / E(all) clamped to [0, 1], where pix is occluded
+ * when the ray from fl(x + fl(bias n)) along l_pix hits a triangle (the test above, t > 0, no t_max).  Only pixels with
+ * n . l_pix > 0 are traced.  ratio = 1 when E(all) is not > 0, when x or n is not finite, and when F = 0.
+ * Hit attributes (pn_object_hits), per ray: mask = (0 <= face < F) and not (t >= scene_dep) (scene_dep NULL: every hit;
+ * a NaN depth counts as behind); for a masked ray points = o + t d, normals = the barycentric blend of vertex_normals
+ * (or, NULL, normalize(e1 x e2)) renormalised and negated when n . d > 0 (i.e. n . v < 0), albedo = the blend of
+ * vertex_albedo (or, NULL, the constant colour), viewdirs = d / |d|, weights [R, K] = 1 / |point - probe_positions[k]|
+ * normalised to sum 1 (a position within 1e-6 takes its probe alone; weights may be NULL); zeros for the other rays.
+ * scene_points (optional; needs scene_dep) = o + scene_dep d outside the mask, NaN inside.  fp64 on fp32 inputs, rounded once.
+ * Composite (pn_object_composite): rgb = mask ? object_rgb : scene_rgb * shadow, depth = mask ? t : scene_dep.
+ * No atomics anywhere; sums in pixel order: repeated calls give the same bits, whatever R.  R = 0 launches nothing.
+ * Errors: PN_ERR_BAD_SHAPE (a negative count, F = 0 in pn_trace_mesh, K outside [1, 8], H or W < 2, H W >= 2^30). */
+#define PN_OBJ_MAX_PROBES 8
+#define PN_OBJ_EDGE_EPS 2e-6f
+int pn_tri_setup(int64_t F, int64_t V, const float* vertices, const int32_t* faces, float* tris, void* stream);
+/* any_hit = 0: t [R], face [R], bary [R, 2] are written (hit unused); any_hit = 1: hit [R] uint8 only */
+int pn_trace_mesh(int64_t R, const float* origins, const float* directions, int64_t F, const float* tris,
+                  const float* t_max, const float* bsphere, int any_hit, float* t, int32_t* face, float* bary,
+                  uint8_t* hit, void* stream);
+int pn_shade(int64_t R, int K, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+             const float* dirs, const float* omega, const float* albedo, const float* normals, const float* viewdirs,
+             const float* roughness, float roughness_all, int microfacet, const float* weights, float* rgb,
+             float* diffuse, float* specular, float* shading, void* stream);
+int pn_shadow_ratio(int64_t R, int H, int W, const float* x, int64_t cs, int64_t ps, const float* dirs,
+                    const float* omega, const float* points, const float* normals, float bias, int64_t F,
+                    const float* tris, const float* bsphere, float* out, void* stream);
+int pn_object_hits(int64_t R, const float* origins, const float* directions, const float* t, const int32_t* face,
+                   const float* bary, const float* scene_dep, int64_t V, const float* vertices, int64_t F,
+                   const int32_t* faces, const float* vertex_normals, const float* vertex_albedo, float albedo_r,
+                   float albedo_g, float albedo_b, int K, const float* probe_positions, uint8_t* mask, float* points,
+                   float* normals, float* albedo, float* viewdirs, float* weights, float* scene_points, void* stream);
+int pn_object_composite(int64_t R, const uint8_t* mask, const float* object_rgb, const float* t,
+                        const float* scene_rgb, const float* scene_dep, const float* shadow, float* rgb, float* depth,
+                        void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

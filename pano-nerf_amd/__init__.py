@@ -16,6 +16,8 @@ Public surface (mirrors the reference's names):
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
     views                         novel views: perspective cameras and ray pools, camera paths, render_view / render_path
                                   and the reference's viewable uint8 frames (HIP kernels)
+    objects                       virtual object insertion: ray / triangle tracing, the reference's Lambertian and microfacet
+                                  shading under light probes, cast shadows, insert_object / insert_path (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -38,6 +40,7 @@ from . import geometry  # noqa
 from .geometry import extract_mesh  # noqa
 from . import lighting  # noqa
 from . import views  # noqa
+from . import objects  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

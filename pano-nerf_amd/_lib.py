@@ -76,6 +76,12 @@ SIGNATURES = {
     "pn_sample_pinhole_rays": ("i", "liiipppffp" + "p" * 9 + "p"),
     "pn_to_frame": ("i", "iiipllfffppp" + "p"),
     "pn_ingest_image": ("i", "iiiipiiiiiiffpp"),
+    "pn_tri_setup": ("i", "llpppp"),
+    "pn_trace_mesh": ("i", "lpplpppi" + "pppp" + "p"),
+    "pn_shade": ("i", "liiiplll" + "pppppp" + "fip" + "pppp" + "p"),
+    "pn_shadow_ratio": ("i", "liipllppppflppp" + "p"),
+    "pn_object_hits": ("i", "lpppppp" + "lplp" + "pp" + "fff" + "ip" + "p" * 7 + "p"),
+    "pn_object_composite": ("i", "l" + "p" * 8 + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

@@ -10,6 +10,7 @@ fallback.  The only host synchronisation is the copy of the two mesh totals that
     marching_tetrahedra(sigma, level, bounds)   (vertices [V, 3], faces [F, 3] int32) of {sigma > level}
     extract_mesh(model, bounds, resolution, level)  Mesh(vertices, faces, normals, colors)
     write_ply(path, vertices, faces, normals, colors)  binary little-endian PLY
+    read_ply(path)                              Mesh of host numpy arrays from such a file (binary or ASCII)
 
 The mesh contract (edge ids, vertex and face order, winding) is stated in include/panonerf_hip.h.
 """
@@ -329,3 +330,91 @@ def _host(x, dtype, name):
     if a.ndim != 2 or a.shape[1] != 3:
         raise ValueError(f"{name} must be [N, 3]; got {a.shape}")
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+_PLY_VERTEX = {"x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"}
+
+
+def read_ply(path):
+    """Mesh(vertices [V, 3] fp32, faces [F, 3] int32, normals [V, 3] fp32 | None, colors [V, 3] fp32 in [0, 1] | None) as
+    HOST numpy arrays (a file is host data; write_ply and objects.VirtualObject take them as they are and copy them to the
+    device themselves).  Reads what write_ply writes - binary little-endian, float x y z, optional float nx ny nz,
+    optional uchar red green blue, uchar-counted int (or uint) lists of 3 vertex_indices - and the ASCII form of the
+    same elements.  Anything else raises ValueError naming what it found."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' ... 'end_header' header)")
+    nl = data.find(b"\n", end)
+    if nl < 0:
+        raise ValueError(f"{path}: the header's last line is not terminated")
+    body = data[nl + 1:]
+    fmt, elements = None, []  # elements: [name, count, [(kind, type(s), name)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1] if len(w) > 1 else ""
+        elif w[0] == "element" and len(w) == 3:
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements:
+            if w[1] == "list" and len(w) == 5:
+                elements[-1][2].append(("list", (w[2], w[3]), w[4]))
+            elif len(w) == 3:
+                elements[-1][2].append(("scalar", w[1], w[2]))
+            else:
+                raise ValueError(f"{path}: unreadable header line {line!r}")
+        else:
+            raise ValueError(f"{path}: unreadable header line {line!r}")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{path}: format {fmt!r} is not supported (binary_little_endian or ascii)")
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError(f"{path}: elements {[e[0] for e in elements]} (expected vertex, then face)")
+    (_, nv, vprops), (_, nf, fprops) = elements
+    names = [p[2] for p in vprops]
+    for kind, typ, name in vprops:
+        want = ("uchar", "uint8") if name in ("red", "green", "blue") else ("float", "float32")
+        if kind != "scalar" or name not in _PLY_VERTEX or typ not in want:
+            raise ValueError(f"{path}: vertex property {typ if kind == 'scalar' else 'list'} {name} is not supported")
+    groups = [g for g in (("x", "y", "z"), ("nx", "ny", "nz"), ("red", "green", "blue")) if any(k in names for k in g)]
+    if names != [k for g in groups for k in g] or groups[:1] != [("x", "y", "z")]:
+        raise ValueError(f"{path}: vertex properties {names} (expected x y z [nx ny nz] [red green blue])")
+    if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][1][0] not in ("uchar", "uint8") or \
+            fprops[0][1][1] not in ("int", "int32", "uint", "uint32") or fprops[0][2] not in ("vertex_indices", "vertex_index"):
+        raise ValueError(f"{path}: face properties {fprops} (expected 'list uchar int vertex_indices')")
+    has_n, has_c = "nx" in names, "red" in names
+    if fmt == "ascii":
+        tok = body.split()
+        ncol = len(names)
+        if len(tok) < nv * ncol + nf * 4:
+            raise ValueError(f"{path}: the body ends early")
+        vt = np.array(tok[:nv * ncol], dtype=np.float64).reshape(nv, ncol)
+        ft = np.array(tok[nv * ncol:nv * ncol + nf * 4], dtype=np.int64).reshape(nf, 4)
+        if nf and not (ft[:, 0] == 3).all():
+            raise ValueError(f"{path}: a face with {int(ft[ft[:, 0] != 3][0, 0])} vertices (only triangles are supported)")
+        v = vt[:, :3].astype(np.float32)
+        n = vt[:, 3:6].astype(np.float32) if has_n else None
+        c = (vt[:, ncol - 3:] / 255.0).astype(np.float32) if has_c else None
+        f = ft[:, 1:].astype(np.int32)
+    else:
+        fields = [(k, "u1" if k in ("red", "green", "blue") else "<f4") for k in names]
+        vdt = np.dtype(fields)
+        fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+        if len(body) < nv * vdt.itemsize:
+            raise ValueError(f"{path}: the body ends early")
+        vrec = np.frombuffer(body, dtype=vdt, count=nv)
+        rest = body[nv * vdt.itemsize:]
+        if nf and rest[0] != 3:
+            raise ValueError(f"{path}: a face with {rest[0]} vertices (only triangles are supported)")
+        if len(rest) < nf * fdt.itemsize:
+            raise ValueError(f"{path}: the body ends early")
+        frec = np.frombuffer(rest, dtype=fdt, count=nf)
+        if nf and not (frec["n"] == 3).all():
+            raise ValueError(f"{path}: a face with {int(frec['n'][frec['n'] != 3][0])} vertices (only triangles are supported)")
+        v = np.stack([vrec["x"], vrec["y"], vrec["z"]], 1).astype(np.float32)
+        n = np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], 1).astype(np.float32) if has_n else None
+        c = (np.stack([vrec["red"], vrec["green"], vrec["blue"]], 1).astype(np.float32) / np.float32(255.0)) if has_c else None
+        f = np.ascontiguousarray(frec["i"], dtype=np.int32)
+    return Mesh(v.reshape(nv, 3), f.reshape(nf, 3), n, c)

@@ -1,0 +1,427 @@
+"""Virtual object insertion: a synthetic mesh placed into the captured scene, lit by the light that arrives at its
+position, hidden by what stands in front of it, and darkening the scene under it.
+
+Everything runs on the HIP device through the kernels of ``libpanonerf_hip.so`` (``pn_objects.hip`` plus the renderer's
+and the lighting module's entry points), under ``torch.no_grad()`` on the current stream.  CPU tensors raise: there is no
+host fallback.  No gradients flow through any of it.
+
+    trace_mesh(origins, directions, vertices, faces, t_max, any_hit)   closest hit (t, face, bary) of rays with a mesh
+    shade(probes, albedo, normals, viewdirs, roughness, weights)       the reference's surface_rendering under light probes
+    shadow_ratio(points, normals, probe, vertices, faces, bias)        share of a point's irradiance the mesh leaves
+    VirtualObject(vertices, faces, normals, albedo, roughness)         a mesh with its material; from_mesh, transformed
+    hit_attributes(obj, origins, directions, t, face, bary, ...)       mask, points, normals, albedo, viewdirs, weights
+    insert_object(model, camera, c2w, obj, ...)                        dict of [1, C, H, W]: the composited frame
+    insert_path(model, camera, poses, obj, ...)                        frames of a pose stack (or PNG files)
+
+Conventions (include/panonerf_hip.h states them in full): directions are not normalised and t is in their units, as the
+renderer's depth; viewdirs are camera-to-surface and the BRDF sees v = -viewdirs; triangle edges are inclusive with a
+band of 2e-6 barycentric units; among equal t the lowest face index wins.  Face indices outside [0, V) are not an error
+of trace_mesh / shadow_ratio (checking them would cost a device synchronisation per call): such a face is never hit.
+VirtualObject checks them once, when it is built.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .geometry import Mesh, _model_device
+from .lighting import _probe_view, _table, light_probes
+
+MAX_PROBES = 8
+
+
+def _cuda(*named):
+    dev = None
+    for name, t in named:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor; got {type(t).__name__}")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"pano_nerf_amd.objects runs on a HIP device only ({name} is on {t.device}); there is no "
+                               "CPU fallback")
+        if dev is not None and t.device != dev:
+            raise RuntimeError(f"tensors are on {dev} and {t.device}")
+        dev = t.device
+    return dev
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _rows3(t, name, R=None):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
+    if R is not None and t.shape[0] != R:
+        raise ValueError(f"{name} has {t.shape[0]} rows; expected {R}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _mesh(vertices, faces):
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be a [V, 3] tensor; got {getattr(vertices, 'shape', type(vertices))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be an [F, 3] tensor; got {getattr(faces, 'shape', type(faces))}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"faces must hold int32 indices; got {faces.dtype}")
+    return vertices.detach().to(torch.float32).contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+def _triangles(v, f, dev):
+    """(tris [F, 12], bsphere [4]) of a mesh with F > 0: the tracer's per-triangle rows and a sphere around the vertices."""
+    F = int(f.shape[0])
+    tris = torch.empty(F, 12, dtype=torch.float32, device=dev)
+    _lib.call("pn_tri_setup", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tris.data_ptr(), _stream(dev))
+    lo, hi = v.amin(0), v.amax(0)
+    centre = (lo + hi) * 0.5
+    radius = (v - centre).norm(dim=1).amax().reshape(1)
+    return tris, torch.cat([centre, radius]).contiguous()
+
+
+def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False):
+    """Closest intersection of the R rays o + t d (fp32 [R, 3]; d is not normalised, t is in its units) with the F
+    triangles of (vertices [V, 3], faces [F, 3] int32), two-sided: (t [R], +inf for a miss; face [R] int32, -1; bary
+    [R, 2] = Moeller-Trumbore's (u, v), hit = (1 - u - v) v0 + u v1 + v v2).  A hit has t > 0 and t < t_max[r] where
+    t_max [R] is given.  any_hit=True returns only a bool [R].  Brute force over the triangles, streamed through LDS."""
+    dev = _cuda(("origins", origins), ("directions", directions), ("vertices", vertices), ("faces", faces),
+                ("t_max", t_max))
+    o = _rows3(origins, "origins")
+    R = int(o.shape[0])
+    d = _rows3(directions, "directions", R)
+    v, f = _mesh(vertices, faces)
+    tm = None
+    if t_max is not None:
+        if t_max.numel() != R:
+            raise ValueError(f"t_max must hold {R} values; got {tuple(t_max.shape)}")
+        tm = t_max.detach().to(torch.float32).reshape(R).contiguous()
+    F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
+    with torch.no_grad(), torch.cuda.device(dev):
+        if any_hit:
+            hit = torch.zeros(R, dtype=torch.uint8, device=dev)
+            t = face = bary = None
+        else:
+            hit = None
+            t = torch.full((R,), float("inf"), dtype=torch.float32, device=dev)
+            face = torch.full((R,), -1, dtype=torch.int32, device=dev)
+            bary = torch.zeros(R, 2, dtype=torch.float32, device=dev)
+        if R and F:
+            tris, bs = _triangles(v, f, dev)
+            _lib.call("pn_trace_mesh", R, o.data_ptr(), d.data_ptr(), F, tris.data_ptr(), _lib.ptr(tm), bs.data_ptr(),
+                      int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit), _stream(dev))
+    return hit.bool() if any_hit else (t, face, bary)
+
+
+def shade(probes, albedo, normals, viewdirs, roughness=None, weights=None):
+    """The reference's surface_rendering (utils/surface_rendering.py) with the pixels of light probes as the lights:
+    (rgb, diffuse, specular, shading), each [R, 3] (shading is None in the microfacet branch, as upstream).
+
+    probes [K, 3, H, W] (1 <= K <= 8; the strided views light_probes returns are read in place); albedo, normals (unit),
+    viewdirs [R, 3]: viewdirs point from the camera to the surface and the BRDF is evaluated with v = -viewdirs.
+    roughness None: the Lambertian branch.  A float or an [R, 1] tensor: the microfacet branch (microfeast_brdf).
+    weights [R, K] blend the probes per row (required for K > 1): the light is sum_k weights[r, k] L_k."""
+    x, sp, sc, sw, K, H, W = _probe_view(probes)
+    if K > MAX_PROBES:
+        raise ValueError(f"shade blends at most {MAX_PROBES} probes; got {K}")
+    rough_t = roughness if isinstance(roughness, torch.Tensor) else None
+    dev = _cuda(("probes", x), ("albedo", albedo), ("normals", normals), ("viewdirs", viewdirs), ("roughness", rough_t),
+                ("weights", weights))
+    a = _rows3(albedo, "albedo")
+    R = int(a.shape[0])
+    n, vd = _rows3(normals, "normals", R), _rows3(viewdirs, "viewdirs", R)
+    rough_all = 0.0
+    if rough_t is not None:
+        if rough_t.numel() != R or rough_t.dim() > 2:
+            raise ValueError(f"roughness must be a float or an [R, 1] tensor; got {tuple(rough_t.shape)}")
+        rough_t = rough_t.detach().to(torch.float32).reshape(R).contiguous()
+    elif roughness is not None:
+        rough_all = float(roughness)
+    if weights is None:
+        if K != 1:
+            raise ValueError(f"{K} probes need weights [R, {K}]")
+        w = None
+    else:
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (R, K):
+            raise ValueError(f"weights must be [{R}, {K}]; got {getattr(weights, 'shape', type(weights))}")
+        w = weights.detach().to(torch.float32).contiguous()
+    micro = roughness is not None
+    with torch.no_grad(), torch.cuda.device(dev):
+        dirs, omega = _table(H, W, dev)
+        rgb, diffuse, specular = (torch.empty(R, 3, dtype=torch.float32, device=dev) for _ in range(3))
+        shading = None if micro else torch.empty(R, 3, dtype=torch.float32, device=dev)
+        if R:
+            _lib.call("pn_shade", R, K, H, W, x.data_ptr(), sp, sc, sw, dirs.data_ptr(), omega.data_ptr(), a.data_ptr(),
+                      n.data_ptr(), vd.data_ptr(), _lib.ptr(rough_t), rough_all, int(micro), _lib.ptr(w), rgb.data_ptr(),
+                      diffuse.data_ptr(), specular.data_ptr(), _lib.ptr(shading), _stream(dev))
+    return rgb, diffuse, specular, shading
+
+
+def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3):
+    """[R] fp32 in [0, 1]: the share of the irradiance of scene points [R, 3] (unit normals [R, 3]) that the mesh leaves,
+    under one probe [3, H, W] (or [1, 3, H, W]): E(unoccluded pixels) / E(all pixels), E(S) = sum over the probe pixels in
+    S of mean_c L(pix) max(0, n . l_pix) omega_pix; a pixel is occluded when the ray from x + bias n along l_pix hits the
+    mesh.  1 where E(all) is 0 or the point is not finite.  One fused kernel; meant for a coarse probe (8 x 16)."""
+    if isinstance(probe, torch.Tensor) and probe.dim() == 3:
+        probe = probe[None]
+    x, _, sc, sw, P, H, W = _probe_view(probe)
+    if P != 1:
+        raise ValueError(f"shadow_ratio takes one probe; got {P}")
+    dev = _cuda(("probe", x), ("points", points), ("normals", normals), ("vertices", vertices), ("faces", faces))
+    p = _rows3(points, "points")
+    R = int(p.shape[0])
+    n = _rows3(normals, "normals", R)
+    v, f = _mesh(vertices, faces)
+    F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
+    with torch.no_grad(), torch.cuda.device(dev):
+        dirs, omega = _table(H, W, dev)
+        out = torch.empty(R, dtype=torch.float32, device=dev)
+        if R:
+            tris, bs = _triangles(v, f, dev) if F else (None, None)
+            _lib.call("pn_shadow_ratio", R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(), p.data_ptr(),
+                      n.data_ptr(), float(bias), F, _lib.ptr(tris), _lib.ptr(bs), out.data_ptr(), _stream(dev))
+    return out
+
+
+class VirtualObject:
+    """A triangle mesh with its material, on the device.  vertices [V, 3], faces [F, 3] int32 (device tensors or arrays
+    on the host, which are copied to `device`); normals: per vertex (interpolated with the barycentrics and renormalised)
+    or None (the geometric normalize(e1 x e2)); albedo: one colour or [V, 3] (e.g. Mesh.colors); roughness: None
+    (Lambertian) or a float (microfacet).  The shading normal is flipped towards the eye.  Face indices are checked here."""
+
+    def __init__(self, vertices, faces, normals=None, albedo=(0.8, 0.8, 0.8), roughness=None, device=None):
+        dev = None
+        for t in (vertices, faces, normals, albedo):
+            if isinstance(t, torch.Tensor):
+                dev = t.device
+                break
+        if dev is None:
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise RuntimeError(f"pano_nerf_amd.objects runs on a HIP device only (the object is on {dev}); there is no CPU "
+                               "fallback")
+        to = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt)
+        self.vertices, self.faces = _mesh(to(vertices, torch.float32), to(faces, torch.int32))
+        V = int(self.vertices.shape[0])
+        if self.faces.numel() and (int(self.faces.min()) < 0 or int(self.faces.max()) >= V):
+            raise ValueError(f"faces index outside the {V} vertices")
+        self.normals = None
+        if normals is not None:
+            self.normals = to(normals, torch.float32).contiguous()
+            if tuple(self.normals.shape) != (V, 3):
+                raise ValueError(f"normals must be [V, 3] like the vertices; got {tuple(self.normals.shape)}")
+        self.albedo, self.vertex_albedo = None, None
+        if isinstance(albedo, torch.Tensor) or np.ndim(albedo) == 2:
+            self.vertex_albedo = to(albedo, torch.float32).contiguous()
+            if tuple(self.vertex_albedo.shape) != (V, 3):
+                raise ValueError(f"albedo must be one colour or [V, 3]; got {tuple(self.vertex_albedo.shape)}")
+        else:
+            a = np.asarray(albedo, dtype=np.float64).reshape(-1)
+            if a.shape != (3,):
+                raise ValueError(f"albedo must be one colour or [V, 3]; got shape {np.shape(albedo)}")
+            self.albedo = tuple(float(c) for c in a)
+        self.roughness = None if roughness is None else float(roughness)
+        self.device = dev
+
+    @classmethod
+    def from_mesh(cls, mesh, albedo=None, roughness=None, device=None):
+        """The object of a geometry.Mesh: its normals, and its colours as the albedo unless one is given."""
+        if albedo is None:
+            albedo = mesh.colors if mesh.colors is not None else (0.8, 0.8, 0.8)
+        return cls(mesh.vertices, mesh.faces, mesh.normals, albedo, roughness, device)
+
+    def transformed(self, matrix):
+        """The object moved by a 4x4 matrix (points: M x; normals: the inverse transpose of its 3x3 part, renormalised)."""
+        m = np.asarray(matrix, dtype=np.float64)
+        if m.shape != (4, 4) or not np.isfinite(m).all():
+            raise ValueError(f"matrix must be a finite 4x4 matrix; got shape {m.shape}")
+        a = torch.from_numpy(m[:3, :3].T.astype(np.float32)).to(self.device)
+        v = self.vertices @ a + torch.from_numpy(m[:3, 3].astype(np.float32)).to(self.device)
+        n = None
+        if self.normals is not None:
+            it = torch.from_numpy(np.linalg.inv(m[:3, :3]).astype(np.float32)).to(self.device)  # (M^-T n)^T = n^T M^-1
+            n = torch.nn.functional.normalize(self.normals @ it, dim=1)
+        return VirtualObject(v, self.faces, n, self.vertex_albedo if self.vertex_albedo is not None else self.albedo,
+                             self.roughness)
+
+    def centroid(self):
+        """[1, 3]: the mean of the vertices."""
+        return self.vertices.mean(0, keepdim=True)
+
+
+def _positions(obj, probe_positions, dev):
+    if probe_positions is None:
+        return obj.centroid()
+    if not isinstance(probe_positions, torch.Tensor):
+        probe_positions = torch.as_tensor(np.asarray(probe_positions, dtype=np.float32)).to(dev)
+    if probe_positions.dim() != 2 or probe_positions.shape[1] != 3 or not 1 <= probe_positions.shape[0] <= MAX_PROBES:
+        raise ValueError(f"probe_positions must be [K, 3] with 1 <= K <= {MAX_PROBES}; got {tuple(probe_positions.shape)}")
+    _cuda(("probe_positions", probe_positions))
+    return probe_positions.detach().to(torch.float32).contiguous()
+
+
+def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, probe_positions=None):
+    """What shade needs at the hits trace_mesh found, as a dict of per-ray tensors: mask [R] bool (hit, and not
+    t >= scene_dep where scene_dep [R] is given: a NaN depth counts as behind), points = o + t d, normals (interpolated
+    or geometric, flipped towards the eye), albedo, viewdirs = d / |d| [R, 3] and weights [R, K] (normalised inverse
+    distances of the point to probe_positions [K, 3]; a point within 1e-6 of a position takes that probe alone); rows
+    outside the mask are 0.  With scene_dep also scene_points [R, 3] = o + scene_dep d outside the mask and NaN inside:
+    the points insert_object hands to shadow_ratio (a NaN point's ratio is 1)."""
+    if not isinstance(obj, VirtualObject):
+        raise ValueError(f"obj must be a VirtualObject; got {type(obj).__name__}")
+    dev = _cuda(("origins", origins), ("directions", directions), ("t", t), ("face", face), ("bary", bary),
+                ("scene_dep", scene_dep), ("vertices", obj.vertices))
+    o = _rows3(origins, "origins")
+    R = int(o.shape[0])
+    d = _rows3(directions, "directions", R)
+    if t.numel() != R or face.numel() != R or tuple(bary.shape) != (R, 2):
+        raise ValueError(f"t, face [R] and bary [R, 2] must match the {R} rays")
+    tt = t.detach().to(torch.float32).reshape(R).contiguous()
+    ff = face.detach().to(torch.int32).reshape(R).contiguous()
+    bb = bary.detach().to(torch.float32).contiguous()
+    dep = None
+    if scene_dep is not None:
+        if scene_dep.numel() != R:
+            raise ValueError(f"scene_dep must hold {R} values; got {tuple(scene_dep.shape)}")
+        dep = scene_dep.detach().to(torch.float32).reshape(R).contiguous()
+    pos = None if probe_positions is None else _positions(obj, probe_positions, dev)
+    K = 1 if pos is None else int(pos.shape[0])
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        mask = torch.zeros(R, dtype=torch.uint8, device=dev)
+        out = dict(points=e(R, 3), normals=e(R, 3), albedo=e(R, 3), viewdirs=e(R, 3))
+        weights = e(R, K) if pos is not None else None
+        spoints = e(R, 3) if dep is not None else None
+        col = obj.albedo or (0.0, 0.0, 0.0)
+        if R:
+            _lib.call("pn_object_hits", R, o.data_ptr(), d.data_ptr(), tt.data_ptr(), ff.data_ptr(), bb.data_ptr(),
+                      _lib.ptr(dep), int(obj.vertices.shape[0]), obj.vertices.data_ptr(), int(obj.faces.shape[0]),
+                      obj.faces.data_ptr(), _lib.ptr(obj.normals), _lib.ptr(obj.vertex_albedo), *col, K, _lib.ptr(pos),
+                      mask.data_ptr(), out["points"].data_ptr(), out["normals"].data_ptr(), out["albedo"].data_ptr(),
+                      out["viewdirs"].data_ptr(), _lib.ptr(weights), _lib.ptr(spoints), _stream(dev))
+    out["mask"] = mask.bool()
+    if weights is not None:
+        out["weights"] = weights
+    if spoints is not None:
+        out["scene_points"] = spoints
+    return out
+
+
+def _frame_rays(camera, c2w, near, far, dev):
+    """(origins, directions) [H W, 3] of the rays render_view renders for this camera and pose."""
+    from . import views
+    c2ws = views._c2w_stack(c2w, single=True)
+    p, c = views._device_cams(camera, c2ws, dev)
+    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
+    rays, _ = views._sample(camera, 1, p, c, idx, near, far, None, dev)
+    return rays.origins, rays.directions
+
+
+def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, near, far, chunk_rays):
+    from . import views
+    dev = _model_device(model)
+    H, W = camera.h, camera.w
+    R = H * W
+    scene = views.render_view(model, camera, c2w, outputs=("rgb", "depth", "normal"), near=near, far=far,
+                              chunk_rays=chunk_rays)
+    rows = lambda x: x.permute(0, 2, 3, 1).reshape(R, -1)  # the [H W, C] buffer behind a render_view output
+    s_rgb, s_dep, s_nor = rows(scene["fine_rgb"]), rows(scene["fine_dep"]), rows(scene["fine_nor"])
+    with torch.no_grad(), torch.cuda.device(dev):
+        o, d = _frame_rays(camera, c2w, near, far, dev)
+        t, face, bary = trace_mesh(o, d, obj.vertices, obj.faces)
+        K = int(pos.shape[0])
+        at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None)
+        mask = at["mask"]
+        object_rgb = torch.zeros(R, 3, dtype=torch.float32, device=dev)
+        hit = torch.nonzero(mask).reshape(-1)  # the one host synchronisation: sizes the shading launch
+        if hit.numel():
+            g = lambda x: x.index_select(0, hit)
+            rgb_hit = shade(probes, g(at["albedo"]), g(at["normals"]), g(at["viewdirs"]), obj.roughness,
+                            g(at["weights"]) if K > 1 else None)[0]
+            object_rgb.index_copy_(0, hit, rgb_hit)
+        if shadow_probe is not None:
+            shadow = shadow_ratio(at["scene_points"], s_nor, shadow_probe, obj.vertices, obj.faces, shadow_bias)
+        else:
+            shadow = torch.ones(R, dtype=torch.float32, device=dev)
+        rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+        depth = torch.empty(R, dtype=torch.float32, device=dev)
+        m8 = mask.to(torch.uint8)
+        _lib.call("pn_object_composite", R, m8.data_ptr(), object_rgb.data_ptr(), t.data_ptr(), s_rgb.data_ptr(),
+                  s_dep.reshape(R).data_ptr(), shadow.data_ptr(), rgb.data_ptr(), depth.data_ptr(), _stream(dev))
+    img = lambda x: x.reshape(1, H, W, -1).permute(0, 3, 1, 2)
+    return dict(scene_rgb=scene["fine_rgb"], scene_dep=scene["fine_dep"], scene_nor=scene["fine_nor"],
+                mask=img(mask.to(torch.float32)), object_rgb=img(object_rgb), shadow=img(shadow), rgb=img(rgb),
+                depth=img(depth))
+
+
+def _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays):
+    dev = _model_device(model)
+    if not isinstance(obj, VirtualObject):
+        raise ValueError(f"obj must be a VirtualObject; got {type(obj).__name__}")
+    if obj.device != dev:
+        raise RuntimeError(f"the object is on {obj.device}, the model on {dev}")
+    pos = _positions(obj, probe_positions, dev)
+    probes = light_probes(model, pos, *probe_size, near=near, far=far, chunk_rays=chunk_rays)
+    sprobe = None
+    if shadows:
+        sprobe = light_probes(model, obj.centroid(), *shadow_probe, near=near, far=far, chunk_rays=chunk_rays)
+    return pos, probes, sprobe
+
+
+def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32, 64), shadows=True, shadow_probe=(8, 16),
+                  shadow_bias=1e-3, near=0.0, far=10.0, chunk_rays=32768):
+    """One view of the scene with `obj` in it -> dict of [1, C, H, W] fp32 tensors:
+
+        scene_rgb, scene_dep, scene_nor   render_view's fine_rgb, fine_dep, fine_nor of the frame
+        mask         1 where the object is hit in front of the scene (t < scene_dep; a NaN depth counts as behind)
+        object_rgb   shade(...) at the hit pixels, 0 elsewhere; probes = light_probes(model, probe_positions, *probe_size)
+        shadow       shadow_ratio at the scene's points outside the mask (1 inside, all 1 with shadows=False), from a
+                     light_probes of size shadow_probe at the vertex centroid
+        rgb          mask ? object_rgb : scene_rgb * shadow
+        depth        mask ? t : scene_dep
+
+    camera: views.perspective_camera(...) or views.pano_camera(h, w); the rays are the ones render_view renders.
+    probe_positions [K, 3] (K <= 8) defaults to the vertex centroid; with K > 1 each hit blends the probes by the
+    normalised inverse distances to their positions.  It is exactly light_probes -> trace_mesh -> hit_attributes ->
+    shade / shadow_ratio(hit_attributes' scene_points, scene_nor) -> the composite, all public."""
+    from . import views
+    camera, dev, _ = views._setup(model, camera, chunk_rays)
+    pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
+    return _insert(model, camera, c2w, obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays)
+
+
+def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32, 64), shadows=True, shadow_probe=(8, 16),
+                shadow_bias=1e-3, near=0.0, far=10.0, exposure=0.0, kinds=("ldr", "mask"), out_dir=None,
+                chunk_rays=32768):
+    """insert_object over poses ([n, 4, 4] or [n, 3, 4] c2ws): dict kind -> uint8 [n, H, W, 3] frames, "ldr" = to_frame of
+    rgb, "mask" = the mask as 0 / 255, "depth" = to_frame of depth.  The probes are rendered once, not per frame: the
+    object does not move.  With out_dir the frames go to out_dir/<kind>/<i:05d>.png and the returned dict is empty."""
+    from . import io_exr, views
+    camera, dev, _ = views._setup(model, camera, chunk_rays)
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in ("ldr", "mask", "depth")]
+    if bad or not kinds:
+        raise ValueError(f"kinds must be a non-empty subset of ['depth', 'ldr', 'mask']; got {kinds!r}")
+    c2ws = views._c2w_stack(poses)
+    n, H, W = c2ws.shape[0], camera.h, camera.w
+    pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
+    frames = {}
+    if out_dir is None:
+        frames = {k: torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev) for k in kinds}
+    else:
+        for k in kinds:
+            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    for i in range(n):
+        out = _insert(model, camera, c2ws[i], obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays)
+        for k in kinds:
+            if k == "ldr":
+                frame = views.to_frame(out["rgb"], "ldr", exposure=exposure)
+            elif k == "depth":
+                frame = views.to_frame(out["depth"], "depth", near, far)
+            else:
+                frame = (out["mask"][0, 0] * 255.0).to(torch.uint8)[..., None].expand(H, W, 3)
+            if out_dir is None:
+                frames[k][i].copy_(frame)
+            else:
+                io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.contiguous().cpu().numpy())
+    return frames
