@@ -566,6 +566,77 @@ int pn_object_composite(int64_t R, const uint8_t* mask, const float* object_rgb,
                         const float* scene_rgb, const float* scene_dep, const float* shadow, float* rgb, float* depth,
                         void* stream);
 
+/* ---- mesh tracing through a device-built BVH (pn_bvh.hip): opt-in, next to the brute-force tracer above ----------------
+ * The ray / triangle test is the one above (the same function, on the same tris rows).  A BVH skips triangles whose box
+ * the ray misses, and the fp32 test above is not exact (it owns a band of PN_OBJ_EDGE_EPS outside each triangle and its t
+ * is badly conditioned for grazing rays), so a BVH cannot promise the brute-force result for every input.  It promises a
+ * result that does not depend on the tree, and that is the brute-force result wherever no accepted (ray, triangle) pair
+ * falls outside the triangle's padded box:
+ * Triangle box of face f: lo / hi = the fp32 component-wise min / max of its three vertices (the vertices themselves,
+ * not v0 + e1), widened on every side by pad = fl(fl(PN_BVH_PAD_REL * ext) + fl(PN_BVH_PAD_ABS * mag)), ext = the largest
+ * of the three fl(hi - lo), mag = the largest |coordinate| of the three vertices: box = [fl(lo - pad), fl(hi + pad)].
+ * A face with an index outside [0, V) or a vertex coordinate that is not finite gets the EMPTY box (lo = +inf,
+ * hi = -inf), which no ray passes: such a face is never a candidate.
+ * Box test of ray (o, d): a ray with a component of o or d that is not finite passes nothing (the test above never
+ * accepts such a ray either); a box with lo.x > hi.x (empty) is passed by nothing.  Otherwise per axis, fp32, separate
+ * operations, inv = 1 / d: when inv is finite, a = fl(fl(lo - o) inv), b = fl(fl(hi - o) inv), near = min(a, b), far =
+ * max(a, b); when it is not (d == 0, or so small that 1 / d overflows) the axis is a slab: near = -inf, far = +inf when
+ * lo <= o <= hi, else the box is missed - so no 0 x inf is ever formed and no NaN decides anything.  tn = the largest near,
+ * tf = the smallest far, both then rounded outwards: tn (1 - 2^-21) for tn > 0, tn (1 + 2^-21) otherwise; tf (1 + 2^-21)
+ * for tf > 0, tf (1 - 2^-21) otherwise.  The box is passed when tn <= tf and tf >= 0.
+ * Candidate rule: face f counts for ray r iff the test above accepts it (t < t_max[r] exclusive included), the ray
+ * passes f's own padded box, and tn_f <= t_f.  Closest hit: the lexicographic minimum of (t, f) over the candidates
+ * (equal t: the lowest face index).  any_hit and shadow occlusion: the candidate set is not empty.
+ * The tree cannot matter: a node's box is the exact fp32 union (min / max, no arithmetic) of its children's boxes, down
+ * to the padded triangle boxes; fp32 subtraction, multiplication by a fixed inv, min / max, the slab branch and the
+ * outward rounding are all monotone, so a parent's tn is never above a child's and its tf never below.  A traversal skips
+ * a node only when the ray does not pass its box or tn_node > best (strict; best starts at t_max or +inf); a leaf's t
+ * replaces the best when t < best, or t == best with a face already held and f lower.  Hence every ancestor of the
+ * winning candidate is entered whatever the topology and the order of traversal.
+ * The constants: the edge band lies at most 2e-6 (|e1| + |e2|) <= 7e-6 ext outside the triangle, and fp32 rounding moves
+ * the point o + t d that the test accepts by a few ulp of the coordinates involved; PAD_REL = 1e-4 covers the band 14
+ * times over and PAD_ABS = 4e-6 is 64 ulp of the triangle's largest coordinate; the slab arithmetic's own relative error
+ * (2 roundings, 2^-23) sits inside the outward rounding of 2^-21.  With them no accepted pair of the test scenes
+ * (tests/test_bvh_cpu.py: closed, random, sliver, coincident and fan meshes under panoramic, pinhole, vertex- and
+ * edge-aimed, axis-aligned and inside-the-box rays) fails the candidate rule, so there BVH == brute force bit for bit;
+ * with no padding the same test counts 14 accepted pairs outside their boxes.  The pad knows the triangle only: an eye
+ * whose distance dwarfs the mesh's coordinates is outside what the constants were sized for.
+ * Build (all on `stream`, no host synchronisation): pn_bvh_boxes writes tbox [F, 2, 4] = (lo, 0), (hi, 0) per face;
+ * the caller takes their union (scene_box: 6 device floats lo, hi) and pn_bvh_keys writes one 63-bit Morton key per
+ * face (21 bits per axis of the box centre within scene_box, x the most significant of each triple; int64 >= 0; an empty
+ * box: 2^63 - 1); the caller sorts them (stable) into sorted_keys and order (order[j] = the face at sorted position j);
+ * pn_bvh_tree builds the radix tree of Karras (2012) over the sorted keys, one thread per internal node, equal keys told
+ * apart by their sorted position, and refits bottom-up: one thread per leaf climbs, the second arrival at a node (an
+ * atomicAdd on counters behind a fence) goes on with the union.  Min / max are exact, so the nodes do not depend on the
+ * arrival order: two builds give the same bytes.
+ * nodes [max(F - 1, 1), 16] fp32, row i = (lo_left, ref_left), (hi_left, ref_right), (lo_right, parent), (hi_right, 0):
+ * both children's boxes in one 64-byte row; ref, parent: int32 bits; ref >= 0 an internal node, ref < 0 the leaf of face
+ * ~ref, PN_BVH_NONE no child; the root is row 0 with parent -1.  F = 1: no internal node is built; row 0 carries the one
+ * leaf as its left child and (empty box, PN_BVH_NONE) on the right.
+ * Depth: the split position of a node is a common-prefix length of (key, sorted position) pairs, it grows strictly from
+ * parent to child, and it takes at most PN_BVH_KEY_BITS + 31 values (F < 2^31): no leaf lies under more than
+ * PN_BVH_MAX_DEPTH = 94 internal nodes, and a traversal that pushes at most one child per level holds at most that many.
+ * Work: leaf_parent [F] int32 and counters [max(F - 1, 1)] int32 (zeroed by pn_bvh_tree itself).
+ * pn_trace_mesh_bvh / pn_shadow_ratio_bvh: the outputs and conventions of pn_trace_mesh / pn_shadow_ratio with the
+ * candidate rule above; the shadow's sums, their order and its horizon / bounding-sphere early-outs are unchanged, so its
+ * ratio has the brute-force bits whenever the occlusion booleans agree.  The traversal stack lives in LDS.
+ * Errors: PN_ERR_BAD_SHAPE (a negative count, F <= 0 or F >= 2^31 where a tree is needed). */
+#define PN_BVH_PAD_REL 1e-4f
+#define PN_BVH_PAD_ABS 4e-6f
+#define PN_BVH_KEY_BITS 63
+#define PN_BVH_MAX_DEPTH 94
+#define PN_BVH_NONE (-2147483647 - 1)
+int pn_bvh_boxes(int64_t F, int64_t V, const float* vertices, const int32_t* faces, float* tbox, void* stream);
+int pn_bvh_keys(int64_t F, const float* tbox, const float* scene_box, int64_t* keys, void* stream);
+int pn_bvh_tree(int64_t F, const int64_t* sorted_keys, const int64_t* order, const float* tbox, float* nodes,
+                int32_t* leaf_parent, int32_t* counters, void* stream);
+int pn_trace_mesh_bvh(int64_t R, const float* origins, const float* directions, int64_t F, const float* tris,
+                      const float* nodes, const float* t_max, int any_hit, float* t, int32_t* face, float* bary,
+                      uint8_t* hit, void* stream);
+int pn_shadow_ratio_bvh(int64_t R, int H, int W, const float* x, int64_t cs, int64_t ps, const float* dirs,
+                        const float* omega, const float* points, const float* normals, float bias, int64_t F,
+                        const float* tris, const float* nodes, const float* bsphere, float* out, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

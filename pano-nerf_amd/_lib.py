@@ -82,6 +82,11 @@ SIGNATURES = {
     "pn_shadow_ratio": ("i", "liipllppppflppp" + "p"),
     "pn_object_hits": ("i", "lpppppp" + "lplp" + "pp" + "fff" + "ip" + "p" * 7 + "p"),
     "pn_object_composite": ("i", "l" + "p" * 8 + "p"),
+    "pn_bvh_boxes": ("i", "llpppp"),
+    "pn_bvh_keys": ("i", "lpppp"),
+    "pn_bvh_tree": ("i", "lpppppp" + "p"),
+    "pn_trace_mesh_bvh": ("i", "lpplpppi" + "pppp" + "p"),
+    "pn_shadow_ratio_bvh": ("i", "liipllppppflpppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

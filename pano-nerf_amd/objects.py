@@ -6,6 +6,7 @@ and the lighting module's entry points), under ``torch.no_grad()`` on the curren
 host fallback.  No gradients flow through any of it.
 
     trace_mesh(origins, directions, vertices, faces, t_max, any_hit)   closest hit (t, face, bary) of rays with a mesh
+    MeshBVH.build(vertices, faces)                                     a linear BVH over the triangles, built on the device
     shade(probes, albedo, normals, viewdirs, roughness, weights)       the reference's surface_rendering under light probes
     shadow_ratio(points, normals, probe, vertices, faces, bias)        share of a point's irradiance the mesh leaves
     VirtualObject(vertices, faces, normals, albedo, roughness)         a mesh with its material; from_mesh, transformed
@@ -18,6 +19,14 @@ renderer's depth; viewdirs are camera-to-surface and the BRDF sees v = -viewdirs
 band of 2e-6 barycentric units; among equal t the lowest face index wins.  Face indices outside [0, V) are not an error
 of trace_mesh / shadow_ratio (checking them would cost a device synchronisation per call): such a face is never hit.
 VirtualObject checks them once, when it is built.
+
+trace_mesh and shadow_ratio are brute force over the triangles unless told otherwise: accel=None is that path, untouched.
+accel="bvh" builds a MeshBVH for the call and walks it; accel=<a MeshBVH of the same mesh> reuses one (VirtualObject.bvh()
+builds it once and keeps it; insert_object / insert_path pass accel on and build once for all frames).  The BVH result
+does not depend on the tree and equals brute force wherever no accepted hit lies outside its triangle's padded box (the
+header's "candidate rule"): tests/test_bvh_cpu.py shows that no such hit exists on its scenes.  Measured on one MI355X
+(profiles/objects_bvh.txt): with the build inside the call the BVH is slower than brute force at 80 faces and below and
+faster from 320 on - 63 to 81 times at 81 920 faces, where the two tracers differed on no ray of either test frame.
 """
 import os
 
@@ -80,11 +89,67 @@ def _triangles(v, f, dev):
     return tris, torch.cat([centre, radius]).contiguous()
 
 
-def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False):
+class MeshBVH:
+    """A linear BVH over the triangles of one mesh, on the device: tris [F, 12] (the tracer's rows), nodes
+    [max(F - 1, 1), 16] (both children's boxes and references per row; include/panonerf_hip.h), bsphere [4], F and the
+    device.  Build it with MeshBVH.build; hand it to trace_mesh / shadow_ratio / insert_object as `accel`."""
+
+    def __init__(self, tris, nodes, bsphere, F, device):
+        self.tris, self.nodes, self.bsphere, self.F, self.device = tris, nodes, bsphere, F, device
+
+    @classmethod
+    def build(cls, vertices, faces):
+        """Padded triangle boxes -> 63-bit Morton keys -> torch.sort (stable) -> Karras' radix tree -> bottom-up refit, all
+        launched on the current stream without a host synchronisation.  Two builds of a mesh give the same bytes."""
+        dev = _cuda(("vertices", vertices), ("faces", faces))
+        v, f = _mesh(vertices, faces)
+        F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
+        if not F:
+            return cls(None, None, None, 0, dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            st = _stream(dev)
+            tris, bs = _triangles(v, f, dev)
+            tbox = torch.empty(F, 2, 4, dtype=torch.float32, device=dev)
+            _lib.call("pn_bvh_boxes", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tbox.data_ptr(), st)
+            nodes = torch.empty(max(F - 1, 1), 16, dtype=torch.float32, device=dev)
+            if F == 1:
+                _lib.call("pn_bvh_tree", F, None, None, tbox.data_ptr(), nodes.data_ptr(), None, None, st)
+                return cls(tris, nodes, bs, F, dev)
+            scene = torch.cat([tbox[:, 0, :3].amin(0), tbox[:, 1, :3].amax(0)]).contiguous()
+            keys = torch.empty(F, dtype=torch.int64, device=dev)
+            _lib.call("pn_bvh_keys", F, tbox.data_ptr(), scene.data_ptr(), keys.data_ptr(), st)
+            skeys, order = torch.sort(keys, stable=True)
+            leaf_parent = torch.empty(F, dtype=torch.int32, device=dev)
+            counters = torch.empty(F - 1, dtype=torch.int32, device=dev)
+            _lib.call("pn_bvh_tree", F, skeys.data_ptr(), order.data_ptr(), tbox.data_ptr(), nodes.data_ptr(),
+                      leaf_parent.data_ptr(), counters.data_ptr(), st)
+        return cls(tris, nodes, bs, F, dev)
+
+
+def _check_accel(accel):
+    """accel is None, "bvh" or a MeshBVH: anything else raises before a tensor is looked at."""
+    if accel is None or isinstance(accel, MeshBVH) or (isinstance(accel, str) and accel == "bvh"):
+        return
+    raise ValueError(f'accel must be None (brute force), "bvh" or a MeshBVH; got {accel!r}')
+
+
+def _bvh_for(accel, v, f, F, dev):
+    """The MeshBVH a call walks: the one handed in or one built for this call.  Of a tree handed in only the face count
+    and the device are compared with the mesh: keeping the two in step is the caller's business (VirtualObject.bvh() does)."""
+    if isinstance(accel, MeshBVH):
+        if accel.F != F or (F and accel.device != dev):
+            raise ValueError(f"accel is a MeshBVH of {accel.F} faces on {accel.device}; the mesh has {F} on {dev}")
+        return accel
+    return MeshBVH.build(v, f)
+
+
+def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False, accel=None):
     """Closest intersection of the R rays o + t d (fp32 [R, 3]; d is not normalised, t is in its units) with the F
     triangles of (vertices [V, 3], faces [F, 3] int32), two-sided: (t [R], +inf for a miss; face [R] int32, -1; bary
     [R, 2] = Moeller-Trumbore's (u, v), hit = (1 - u - v) v0 + u v1 + v v2).  A hit has t > 0 and t < t_max[r] where
-    t_max [R] is given.  any_hit=True returns only a bool [R].  Brute force over the triangles, streamed through LDS."""
+    t_max [R] is given.  any_hit=True returns only a bool [R].  accel=None: brute force over the triangles, streamed through
+    LDS.  accel="bvh" or a MeshBVH of this mesh: a BVH walk (the module docstring says what it promises)."""
+    _check_accel(accel)
     dev = _cuda(("origins", origins), ("directions", directions), ("vertices", vertices), ("faces", faces),
                 ("t_max", t_max))
     o = _rows3(origins, "origins")
@@ -106,7 +171,12 @@ def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False):
             t = torch.full((R,), float("inf"), dtype=torch.float32, device=dev)
             face = torch.full((R,), -1, dtype=torch.int32, device=dev)
             bary = torch.zeros(R, 2, dtype=torch.float32, device=dev)
-        if R and F:
+        if R and F and accel is not None:
+            bvh = _bvh_for(accel, v, f, F, dev)
+            _lib.call("pn_trace_mesh_bvh", R, o.data_ptr(), d.data_ptr(), F, bvh.tris.data_ptr(), bvh.nodes.data_ptr(),
+                      _lib.ptr(tm), int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit),
+                      _stream(dev))
+        elif R and F:
             tris, bs = _triangles(v, f, dev)
             _lib.call("pn_trace_mesh", R, o.data_ptr(), d.data_ptr(), F, tris.data_ptr(), _lib.ptr(tm), bs.data_ptr(),
                       int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit), _stream(dev))
@@ -157,11 +227,13 @@ def shade(probes, albedo, normals, viewdirs, roughness=None, weights=None):
     return rgb, diffuse, specular, shading
 
 
-def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3):
+def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3, accel=None):
     """[R] fp32 in [0, 1]: the share of the irradiance of scene points [R, 3] (unit normals [R, 3]) that the mesh leaves,
     under one probe [3, H, W] (or [1, 3, H, W]): E(unoccluded pixels) / E(all pixels), E(S) = sum over the probe pixels in
     S of mean_c L(pix) max(0, n . l_pix) omega_pix; a pixel is occluded when the ray from x + bias n along l_pix hits the
-    mesh.  1 where E(all) is 0 or the point is not finite.  One fused kernel; meant for a coarse probe (8 x 16)."""
+    mesh.  1 where E(all) is 0 or the point is not finite.  One fused kernel; meant for a coarse probe (8 x 16).
+    accel as in trace_mesh: with a BVH only the occlusion query changes, the sums and their order do not."""
+    _check_accel(accel)
     if isinstance(probe, torch.Tensor) and probe.dim() == 3:
         probe = probe[None]
     x, _, sc, sw, P, H, W = _probe_view(probe)
@@ -176,7 +248,12 @@ def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3):
     with torch.no_grad(), torch.cuda.device(dev):
         dirs, omega = _table(H, W, dev)
         out = torch.empty(R, dtype=torch.float32, device=dev)
-        if R:
+        if R and F and accel is not None:
+            bvh = _bvh_for(accel, v, f, F, dev)
+            _lib.call("pn_shadow_ratio_bvh", R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(),
+                      p.data_ptr(), n.data_ptr(), float(bias), F, bvh.tris.data_ptr(), bvh.nodes.data_ptr(),
+                      bvh.bsphere.data_ptr(), out.data_ptr(), _stream(dev))
+        elif R:
             tris, bs = _triangles(v, f, dev) if F else (None, None)
             _lib.call("pn_shadow_ratio", R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(), p.data_ptr(),
                       n.data_ptr(), float(bias), F, _lib.ptr(tris), _lib.ptr(bs), out.data_ptr(), _stream(dev))
@@ -222,6 +299,7 @@ class VirtualObject:
             self.albedo = tuple(float(c) for c in a)
         self.roughness = None if roughness is None else float(roughness)
         self.device = dev
+        self._bvh, self._bvh_stamp = None, None
 
     @classmethod
     def from_mesh(cls, mesh, albedo=None, roughness=None, device=None):
@@ -243,6 +321,15 @@ class VirtualObject:
             n = torch.nn.functional.normalize(self.normals @ it, dim=1)
         return VirtualObject(v, self.faces, n, self.vertex_albedo if self.vertex_albedo is not None else self.albedo,
                              self.roughness)
+
+    def bvh(self):
+        """The MeshBVH of this object, built on first use and kept for as long as vertices and faces are the tensors it
+        was built from, unchanged (their storage and torch's in-place version counters are compared, on the host): an
+        assignment or an in-place edit of either builds anew.  transformed() returns an object without one."""
+        stamp = tuple(x for t in (self.vertices, self.faces) for x in (t.data_ptr(), tuple(t.shape), t._version))
+        if self._bvh is None or self._bvh_stamp != stamp:
+            self._bvh, self._bvh_stamp = MeshBVH.build(self.vertices, self.faces), stamp
+        return self._bvh
 
     def centroid(self):
         """[1, 3]: the mean of the vertices."""
@@ -317,7 +404,15 @@ def _frame_rays(camera, c2w, near, far, dev):
     return rays.origins, rays.directions
 
 
-def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, near, far, chunk_rays):
+def _object_accel(obj, accel):
+    """accel of insert_object / insert_path -> what trace_mesh and shadow_ratio get: None, or one MeshBVH for every call."""
+    _check_accel(accel)
+    if accel == "bvh" and isinstance(obj, VirtualObject):
+        return obj.bvh()
+    return accel
+
+
+def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, near, far, chunk_rays, accel=None):
     from . import views
     dev = _model_device(model)
     H, W = camera.h, camera.w
@@ -328,7 +423,7 @@ def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, nea
     s_rgb, s_dep, s_nor = rows(scene["fine_rgb"]), rows(scene["fine_dep"]), rows(scene["fine_nor"])
     with torch.no_grad(), torch.cuda.device(dev):
         o, d = _frame_rays(camera, c2w, near, far, dev)
-        t, face, bary = trace_mesh(o, d, obj.vertices, obj.faces)
+        t, face, bary = trace_mesh(o, d, obj.vertices, obj.faces, accel=accel)
         K = int(pos.shape[0])
         at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None)
         mask = at["mask"]
@@ -340,7 +435,8 @@ def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, nea
                             g(at["weights"]) if K > 1 else None)[0]
             object_rgb.index_copy_(0, hit, rgb_hit)
         if shadow_probe is not None:
-            shadow = shadow_ratio(at["scene_points"], s_nor, shadow_probe, obj.vertices, obj.faces, shadow_bias)
+            shadow = shadow_ratio(at["scene_points"], s_nor, shadow_probe, obj.vertices, obj.faces, shadow_bias,
+                                  accel=accel)
         else:
             shadow = torch.ones(R, dtype=torch.float32, device=dev)
         rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
@@ -369,7 +465,7 @@ def _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near
 
 
 def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32, 64), shadows=True, shadow_probe=(8, 16),
-                  shadow_bias=1e-3, near=0.0, far=10.0, chunk_rays=32768):
+                  shadow_bias=1e-3, near=0.0, far=10.0, chunk_rays=32768, accel=None):
     """One view of the scene with `obj` in it -> dict of [1, C, H, W] fp32 tensors:
 
         scene_rgb, scene_dep, scene_nor   render_view's fine_rgb, fine_dep, fine_nor of the frame
@@ -383,20 +479,25 @@ def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32,
     camera: views.perspective_camera(...) or views.pano_camera(h, w); the rays are the ones render_view renders.
     probe_positions [K, 3] (K <= 8) defaults to the vertex centroid; with K > 1 each hit blends the probes by the
     normalised inverse distances to their positions.  It is exactly light_probes -> trace_mesh -> hit_attributes ->
-    shade / shadow_ratio(hit_attributes' scene_points, scene_nor) -> the composite, all public."""
+    shade / shadow_ratio(hit_attributes' scene_points, scene_nor) -> the composite, all public.  accel (None, "bvh" or a
+    MeshBVH of the object) goes to trace_mesh and shadow_ratio; "bvh" is obj.bvh(), built once and kept on the object."""
     from . import views
+    _check_accel(accel)
     camera, dev, _ = views._setup(model, camera, chunk_rays)
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
-    return _insert(model, camera, c2w, obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays)
+    return _insert(model, camera, c2w, obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays,
+                   _object_accel(obj, accel))
 
 
 def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32, 64), shadows=True, shadow_probe=(8, 16),
                 shadow_bias=1e-3, near=0.0, far=10.0, exposure=0.0, kinds=("ldr", "mask"), out_dir=None,
-                chunk_rays=32768):
+                chunk_rays=32768, accel=None):
     """insert_object over poses ([n, 4, 4] or [n, 3, 4] c2ws): dict kind -> uint8 [n, H, W, 3] frames, "ldr" = to_frame of
     rgb, "mask" = the mask as 0 / 255, "depth" = to_frame of depth.  The probes are rendered once, not per frame: the
-    object does not move.  With out_dir the frames go to out_dir/<kind>/<i:05d>.png and the returned dict is empty."""
+    object does not move, and neither is its BVH (accel as in insert_object: one build for all frames).  With out_dir the
+    frames go to out_dir/<kind>/<i:05d>.png and the returned dict is empty."""
     from . import io_exr, views
+    _check_accel(accel)
     camera, dev, _ = views._setup(model, camera, chunk_rays)
     kinds = tuple(kinds)
     bad = [k for k in kinds if k not in ("ldr", "mask", "depth")]
@@ -405,6 +506,7 @@ def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32,
     c2ws = views._c2w_stack(poses)
     n, H, W = c2ws.shape[0], camera.h, camera.w
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
+    accel = _object_accel(obj, accel)
     frames = {}
     if out_dir is None:
         frames = {k: torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev) for k in kinds}
@@ -412,7 +514,7 @@ def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32,
         for k in kinds:
             os.makedirs(os.path.join(out_dir, k), exist_ok=True)
     for i in range(n):
-        out = _insert(model, camera, c2ws[i], obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays)
+        out = _insert(model, camera, c2ws[i], obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays, accel)
         for k in kinds:
             if k == "ldr":
                 frame = views.to_frame(out["rgb"], "ldr", exposure=exposure)

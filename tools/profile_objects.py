@@ -5,9 +5,15 @@ median of --iters synchronised runs after a warm-up call, one process: the probe
 render_view of the same frame (rgb, depth, normal) measured in the same run, and insert_object end to end.  Also rays x
 triangles / s of the tracer and BRDF evaluations / s of shade.  One JSON line per (mesh, frame).
 
+--accel bvh (or both) adds the BVH path: MeshBVH.build as a whole and per stage, trace_mesh and shadow_ratio over a built
+tree, build + trace + shadow as one call next to brute-force trace + shadow as one call (median and spread = max - min
+of the repeats), insert_object(accel="bvh") with the build included, and the number of rays on which the two tracers
+differ.  Level 8 is 1 310 720 faces.
+
     python tools/profile_objects.py                       # both meshes, both frames
+    python tools/profile_objects.py --accel both --levels 3,6,8
     python tools/profile_objects.py --kernels              # the kernels alone, for a trace:
-    rocprofv3 --kernel-trace --stats -d OUT -- python tools/profile_objects.py --kernels --iters 2
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/profile_objects.py --kernels --iters 2 --levels 6 --frames pano
 """
 import argparse
 import json
@@ -68,16 +74,53 @@ def timed(fn, iters):
     return 1e3 * float(np.median(t)), out
 
 
+def timed_spread(fn, iters):
+    """(median ms, max - min of the repeats in ms) of fn, as timed."""
+    fn()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(t)), 1e3 * (max(t) - min(t))
+
+
+def bvh_stages(v, f, iters):
+    """MeshBVH.build stage by stage (the same calls, each synchronised): ms per stage."""
+    dev = v.device
+    F, st = int(f.shape[0]), torch.cuda.current_stream(v.device).cuda_stream
+    out = {}
+    out["bvh_tri_setup_sphere_ms"], _ = timed(lambda: objects._triangles(v, f, dev), iters)
+    tbox = torch.empty(F, 2, 4, device=dev)
+    out["bvh_boxes_ms"], _ = timed(lambda: _lib.call("pn_bvh_boxes", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(),
+                                                     tbox.data_ptr(), st), iters)
+    out["bvh_scene_box_ms"], scene = timed(lambda: torch.cat([tbox[:, 0, :3].amin(0), tbox[:, 1, :3].amax(0)]).contiguous(), iters)
+    keys = torch.empty(F, dtype=torch.int64, device=dev)
+    out["bvh_keys_ms"], _ = timed(lambda: _lib.call("pn_bvh_keys", F, tbox.data_ptr(), scene.data_ptr(), keys.data_ptr(), st), iters)
+    out["bvh_sort_ms"], (skeys, order) = timed(lambda: torch.sort(keys, stable=True), iters)
+    nodes = torch.empty(F - 1, 16, device=dev)
+    parent, counters = (torch.empty(F, dtype=torch.int32, device=dev) for _ in range(2))
+    out["bvh_tree_refit_ms"], _ = timed(lambda: _lib.call("pn_bvh_tree", F, skeys.data_ptr(), order.data_ptr(), tbox.data_ptr(),
+                                                          nodes.data_ptr(), parent.data_ptr(), counters.data_ptr(), st), iters)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--kernels", action="store_true", help="the object kernels only (no scene render, no probes from the model)")
-    ap.add_argument("--levels", default="3,6", help="icosphere subdivision levels (3: 1280 faces, 6: 81 920)")
+    ap.add_argument("--levels", default="3,6", help="icosphere subdivision levels (3: 1280 faces, 6: 81 920, 8: 1 310 720)")
+    ap.add_argument("--accel", default="none", choices=("none", "bvh", "both"),
+                    help="none: the brute-force tracer (the default path); bvh: the BVH path; both: both, side by side")
+    ap.add_argument("--frames", default="both", choices=("both", "pinhole", "pano"), help="which of the two frames to run")
     a = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
     eye, centre = (0.1, 0.05, 0.2), (0.0, -0.1, -0.9)
     c2w = views.look_at(eye, centre)
     frames = {"pinhole 480x640": views.perspective_camera(480, 640, fov_x_deg=60.0), "pano 512x1024": views.pano_camera(512, 1024)}
+    frames = {k: c for k, c in frames.items() if a.frames == "both" or k.startswith(a.frames)}
     model = None if a.kernels else setup()
     g = torch.Generator(device="cuda").manual_seed(0)
     for level in (int(s) for s in a.levels.split(",")):
@@ -100,8 +143,21 @@ def main():
                 s_dep = torch.full((R,), 2.5, device=dev)
                 s_nor = torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=1)
             o, d = objects._frame_rays(cam, c2w, 0.0, 10.0, dev)
-            out["trace_ms"], (t, face, bary) = timed(lambda: objects.trace_mesh(o, d, obj.vertices, obj.faces), a.iters)
-            out["trace_ray_triangles_per_s"] = R * F / (1e-3 * out["trace_ms"])
+            brute, fast = a.accel in ("none", "both"), a.accel in ("bvh", "both")
+            out["accel"] = a.accel
+            if fast:
+                out["bvh_build_ms"], out["bvh_build_spread_ms"] = timed_spread(
+                    lambda: objects.MeshBVH.build(obj.vertices, obj.faces), a.iters)
+                tree = objects.MeshBVH.build(obj.vertices, obj.faces)
+                out.update(bvh_stages(obj.vertices, obj.faces, a.iters))
+                out["bvh_trace_ms"], (t, face, bary) = timed(lambda: objects.trace_mesh(o, d, obj.vertices, obj.faces, accel=tree), a.iters)
+            if brute:
+                out["trace_ms"], (t, face, bary) = timed(lambda: objects.trace_mesh(o, d, obj.vertices, obj.faces), a.iters)
+                out["trace_ray_triangles_per_s"] = R * F / (1e-3 * out["trace_ms"])
+            if brute and fast:
+                t2, face2, bary2 = objects.trace_mesh(o, d, obj.vertices, obj.faces, accel=tree)
+                out["rays_bvh_differs_from_brute"] = int(((t2.view(torch.int32) != t.view(torch.int32)) | (face2 != face) |
+                                                          (bary2.view(torch.int32) != bary.view(torch.int32)).any(1)).sum())
             out["hits_ms"], at = timed(lambda: objects.hit_attributes(obj, o, d, t, face, bary, s_dep), a.iters)
             m = at["mask"]
             n_hit = int(m.sum())
@@ -110,8 +166,29 @@ def main():
             out["shade_lambert_ms"], _ = timed(lambda: objects.shade(probes, al, nr, vd), a.iters)
             out["shade_microfacet_ms"], _ = timed(lambda: objects.shade(probes, al, nr, vd, 0.4), a.iters)
             out["shade_microfacet_brdf_evals_per_s"] = n_hit * 32 * 64 / (1e-3 * out["shade_microfacet_ms"])
-            out["shadow_8x16_ms"], shadow = timed(
-                lambda: objects.shadow_ratio(at["scene_points"], s_nor, sprobe, obj.vertices, obj.faces), a.iters)
+            sp = at["scene_points"]
+            if fast:
+                out["bvh_shadow_8x16_ms"], shadow = timed(
+                    lambda: objects.shadow_ratio(sp, s_nor, sprobe, obj.vertices, obj.faces, accel=tree), a.iters)
+
+                def through_bvh():
+                    fresh = objects.MeshBVH.build(obj.vertices, obj.faces)
+                    objects.trace_mesh(o, d, obj.vertices, obj.faces, accel=fresh)
+                    return objects.shadow_ratio(sp, s_nor, sprobe, obj.vertices, obj.faces, accel=fresh)
+
+                out["bvh_build_trace_shadow_ms"], out["bvh_build_trace_shadow_spread_ms"] = timed_spread(through_bvh, a.iters)
+            if brute:
+                out["shadow_8x16_ms"], shadow_b = timed(
+                    lambda: objects.shadow_ratio(sp, s_nor, sprobe, obj.vertices, obj.faces), a.iters)
+
+                def through_brute():
+                    objects.trace_mesh(o, d, obj.vertices, obj.faces)
+                    return objects.shadow_ratio(sp, s_nor, sprobe, obj.vertices, obj.faces)
+
+                out["brute_trace_shadow_ms"], out["brute_trace_shadow_spread_ms"] = timed_spread(through_brute, a.iters)
+                if fast:
+                    out["shadow_bits_equal"] = bool(torch.equal(shadow.view(torch.int32), shadow_b.view(torch.int32)))
+                shadow = shadow_b
             out["shadow_min"] = float(shadow.min())
             rgb, dep, orgb = (torch.empty(R, k, device=dev) for k in (3, 1, 3))
             m8, srgb = m.to(torch.uint8), torch.rand(R, 3, device=dev, generator=g)
@@ -119,13 +196,24 @@ def main():
             out["composite_ms"], _ = timed(lambda: _lib.call(
                 "pn_object_composite", R, m8.data_ptr(), orgb.data_ptr(), t.data_ptr(), srgb.data_ptr(), s_dep.data_ptr(),
                 shadow.data_ptr(), rgb.data_ptr(), dep.data_ptr(), st), a.iters)
-            if model is not None:
+            if model is not None and brute:
                 out["insert_object_lambert_ms"], _ = timed(lambda: objects.insert_object(model, cam, c2w, obj), a.iters)
                 out["insert_object_microfacet_ms"], _ = timed(lambda: objects.insert_object(model, cam, c2w, rough), a.iters)
                 stages = sum(out[k] for k in ("probes_32x64_ms", "probes_8x16_ms", "trace_ms", "hits_ms", "shade_microfacet_ms",
                                               "shadow_8x16_ms", "composite_ms"))
                 out["object_stages_ms"] = stages
                 out["object_stages_over_render_view"] = stages / out["render_view_ms"]
+            if model is not None and fast:
+                def with_build():  # a fresh object per call: the build is inside
+                    return objects.insert_object(model, cam, c2w, objects.VirtualObject(obj.vertices, obj.faces), accel="bvh")
+
+                out["insert_object_lambert_bvh_ms"], _ = timed(with_build, a.iters)
+                out["insert_object_lambert_bvh_cached_ms"], _ = timed(lambda: objects.insert_object(model, cam, c2w, obj, accel="bvh"),
+                                                                      a.iters)
+                stages = sum(out[k] for k in ("probes_32x64_ms", "probes_8x16_ms", "bvh_build_ms", "bvh_trace_ms", "hits_ms",
+                                              "shade_microfacet_ms", "bvh_shadow_8x16_ms", "composite_ms"))
+                out["object_stages_bvh_ms"] = stages
+                out["object_stages_bvh_over_render_view"] = stages / out["render_view_ms"]
             print(json.dumps(out), flush=True)
 
 
