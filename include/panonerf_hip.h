@@ -484,6 +484,73 @@ enum { PN_FRAME_LDR = 0, PN_FRAME_LDR_GT = 1, PN_FRAME_DEPTH = 2, PN_FRAME_NORMA
 int pn_to_frame(int kind, int H, int W, const float* x, int64_t cs, int64_t ps, float scale, float near_, float range,
                 const float* lut, float* work, uint8_t* out, void* stream);
 
+/* ---- camera models and reprojection (pn_cameras.hip) ----------------------------------------------------------------
+ * Camera space is the pinhole's: right-handed, x right, y up, looking along -z.  A camera is (kind, H, W, params): params
+ * is a HOST array of PN_CAM_PARAMS floats, copied into the launch (unused entries are ignored).  Continuous pixel
+ * positions put the centre of pixel (x = column, y = row) at (x + 1/2, y + 1/2).
+ *   PN_CAM_PANO         the equirectangular camera of pn_raygen_pano: theta = -px 2 pi / W, phi = py pi / H,
+ *                       d = (sin phi sin theta, cos phi, sin phi cos theta).  No params.  H >= 2, W >= 3.
+ *   PN_CAM_PINHOLE      params[0..8] = pix2cam (d = pix2cam @ (px, py, 1), as pn_sample_pinhole_rays), params[9..17] =
+ *                       cam2pix = inv(pix2cam), inverted in fp64 by the caller and rounded once.  H, W >= 2.
+ *   PN_CAM_CUBE         a vertical strip of six S x S faces (W = S >= 2, H = 6 S) in the order +x, -x, +y, -y, +z, -z.
+ *                       Within a face s = 2 px / S - 1, t = 2 (py - face S) / S - 1 (t points down) and
+ *                         +x (1, -t, -s)   -x (-1, -t, s)   +y (s, 1, t)   -y (s, -1, -t)   +z (s, -t, 1)   -z (-s, -t, -1).
+ *                       This is the OpenGL cube-map table, i.e. the LOOKUP convention engines use (direction -> face,
+ *                       s, t): a face looked at as a picture is therefore mirrored relative to a pinhole view along the
+ *                       same axis in this right-handed y-up world.  No params.
+ *   PN_CAM_FISHEYE      equidistant: params[0] = f (pixels per radian, > 0), params[1] = theta_max (half the field of view,
+ *                       radians, in (0, pi]).  u = px - W / 2, v = -(py - H / 2), r = hypot(u, v), theta = r / f,
+ *                       d = (sin theta u / r, sin theta v / r, -cos theta), (0, 0, -1) at r = 0.  A position is inside the
+ *                       image circle when theta <= theta_max.  H, W >= 2.
+ *   PN_CAM_STEREO_PANO  one eye of an omnidirectional-stereo pair: params[0] = +ipd / 2 (right eye) or -ipd / 2 (left).
+ *                       Directions are PN_CAM_PANO's; column j has the heading angle theta_j = -(j + 1/2) 2 pi / W and the
+ *                       camera-space origin params[0] (-cos theta_j, 0, sin theta_j) = heading x up, so the ray is tangent
+ *                       to the viewing circle.  Not a central projection: rays only.
+ * Rays (pn_sample_camera_rays; kinds CUBE, FISHEYE, STEREO_PANO - the panorama and the pinhole keep their own entry points,
+ * PN_ERR_UNSUPPORTED here): the contract of pn_sample_pinhole_rays - batch ray b is pixel idx[b] % (H W) of camera
+ * idx[b] / (H W), an index outside the pool reads ray 0, rgb_pool / rgb_out both given or both NULL; every camera shares
+ * (kind, H, W, params), c2ws [n_cam, 16] is a device array.
+ *   CUBE, FISHEYE: directions = viewdirs = c2w[:3,:3] @ unit camera direction (3-term fp32 dot products in index order; the
+ *     cube's table direction is divided by its fp32 norm first), origins = c2w[:3, 3], noise_var = 0, lossmult = 1,
+ *     radii = |d(i, j) - d(i + 1, j)| 2 / sqrt(12) with the next row's direction, the last row reusing the one before (the
+ *     pinhole rule); for the cube "row" is the row within the face.  A fisheye pixel outside the image circle gets the
+ *     forward direction c2w[:3,:3] @ (0, 0, -1) and lossmult = 0; its radius still comes from the equidistant formula.
+ *   STEREO_PANO: every field is pn_sample_pano_rays' except origins = c2w[:3,:3] @ offset + c2w[:3, 3]; with params[0] = 0
+ *     the origin is c2w[:3, 3] itself and every field equals pn_sample_pano_rays' bit for bit (one device function).
+ * Reprojection (pn_reproject; kinds PANO, PINHOLE, CUBE, FISHEYE on either side): image [N, C, Hs, Ws] with element
+ * (n, c, pix) at image[n image_stride + c cs + pix ps] (strides in floats, so permuted views are read in place) ->
+ * out [N, C, Hd, Wd] and coverage [Hd, Wd], both contiguous.  rotation_host: 3 x 3 row-major HOST matrix taking a
+ * destination camera-space direction to a source camera-space direction (R_src_c2w^T R_dst_c2w for two posed cameras at
+ * one position).  Per destination pixel (x, y) and subsample a, b < k = samples: position (x + (a + 1/2) / k,
+ * y + (b + 1/2) / k) -> destination direction (invalid outside a fisheye's circle) -> rotated -> source position:
+ *   PANO     phi = atan2(hypot(dx, dz), dy), theta = atan2(dx, dz), t = -theta / 2 pi, px = (t - floor t) W, py = phi H / pi;
+ *            always valid.  Taps wrap in columns and clamp in rows.  At an exact pole theta = atan2(0, 0) = 0.
+ *   PINHOLE  q = cam2pix @ d; valid iff q.z > 0 and (q.x, q.y) / q.z lies in [0, W] x [0, H].  Taps clamp to the edge.
+ *   FISHEYE  theta = atan2(hypot(dx, dy), -dz), r = f theta, (px, py) = (W / 2 + r dx / rho, H / 2 - r dy / rho), rho =
+ *            hypot(dx, dy) (the centre at rho = 0); valid iff theta <= theta_max and the position lies in [0, W] x [0, H].
+ *            Taps clamp to the image.
+ *   CUBE     the component of largest magnitude picks the face, ties going to the earlier face of the order above; with m
+ *            that magnitude: +x (s, t) = (-dz, -dy) / m, -x (dz, -dy) / m, +y (dx, dz) / m, -y (dx, -dz) / m,
+ *            +z (dx, -dy) / m, -z (-dx, -dy) / m; px = (s + 1) S / 2, py = (t + 1) S / 2 within the face.  Taps clamp
+ *            within the face.
+ * then the bilinear fetch around (px - 1/2, py - 1/2): ((w00 v00 + w01 v01) + w10 v10) + w11 v11 in fp32.  The output is
+ * the sum of the valid subsamples' fetches in the order b outer, a inner, divided by their count; coverage is count / k^2;
+ * with no valid subsample every channel gets `fill`.  NaN in the source propagates (a tap of weight 0 included).  No
+ * atomics: repeated calls give the same bits.
+ * Errors: PN_ERR_UNSUPPORTED (an unknown kind; a kind the entry point does not take), PN_ERR_BAD_SHAPE (B, n_cam, N or
+ * C <= 0, a size below the kind's minimum, a cube with H != 6 W, H W >= 2^31, samples <= 0 or > PN_REPROJECT_MAX_SAMPLES,
+ * fisheye params not positive). */
+enum { PN_CAM_PANO = 0, PN_CAM_PINHOLE = 1, PN_CAM_CUBE = 2, PN_CAM_FISHEYE = 3, PN_CAM_STEREO_PANO = 4 };
+#define PN_CAM_PARAMS 20
+#define PN_REPROJECT_MAX_SAMPLES 16
+int pn_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, const float* params_host, const int64_t* idx,
+                          const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
+                          float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
+                          float* far_out, float* noise_var, float* rgb_out, void* stream);
+int pn_reproject(int N, int C, int src_kind, int Hs, int Ws, const float* src_params_host, int dst_kind, int Hd, int Wd,
+                 const float* dst_params_host, const float* rotation_host, int samples, float fill, const float* image,
+                 int64_t image_stride, int64_t cs, int64_t ps, float* out, float* coverage, void* stream);
+
 /* ---- dataset ingest (pn_data.hip) ---------------------------------------------------------------------------------
  * planes: the channel planes of one decoded scanline OpenEXR file as stored, [Hs][n_ch][Ws] (line, channel, column),
  * fp16 (is_half != 0) or fp32, on the device.  out: [Hs / factor, Ws / factor, C] fp32 interleaved, C = 1 for

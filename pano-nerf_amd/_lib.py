@@ -75,6 +75,8 @@ SIGNATURES = {
     "pn_sh_volume_irradiance": ("i", "iii" + "f" * 6 + "plppp" + "p"),
     "pn_sample_pinhole_rays": ("i", "liiipppffp" + "p" * 9 + "p"),
     "pn_to_frame": ("i", "iiipllfffppp" + "p"),
+    "pn_sample_camera_rays": ("i", "liiiipppffp" + "p" * 9 + "p"),
+    "pn_reproject": ("i", "iiiiipiiippifplllppp"),
     "pn_ingest_image": ("i", "iiiipiiiiiiffpp"),
     "pn_tri_setup": ("i", "llpppp"),
     "pn_trace_mesh": ("i", "lpplpppi" + "pppp" + "p"),

@@ -1,0 +1,375 @@
+// pn_cameras.hip — camera models beyond the panorama and the pinhole (gfx950): cube-map, equidistant fisheye and
+// stereo-panorama (ODS) ray generation from (camera, pixel), and reprojection of images between the central cameras
+// (panorama, pinhole, cube map, fisheye).  Conventions are stated in include/panonerf_hip.h.
+//
+// Rays: one thread per batch ray, as pn_sample_pinhole_rays; the stereo panorama takes its directions, radii and
+// noise variance from pano_ray (pn_pano_ray.h), the function behind pn_sample_pano_rays.  Reprojection: one thread per
+// (image, destination pixel), a gather: every subsample goes destination pixel -> direction -> rotated -> source pixel
+// once, its four bilinear taps are reused over the channels (four accumulators at a time), the mean over the valid
+// subsamples is taken in a fixed order, and consecutive lanes store consecutive pixels of a destination row.  No atomics.
+#include "pn_common.h"
+#include "pn_pano_ray.h"
+#include <math.h>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChan = 4;  // channels accumulated per pass over the subsamples
+
+#define ST(s) ((hipStream_t)(s))
+
+__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+struct CamParams {
+    float v[PN_CAM_PARAMS];
+};
+struct Rot {
+    float m[9];
+};
+
+constexpr float kPi = 3.14159265358979323846f;
+
+// ------------------------------------------------------------------------------------------------- pixel -> direction
+// camera-space direction of the continuous cube-strip position (px, py); face = the strip's face of py
+__device__ __forceinline__ void cube_dir(int S, float px, float py, float d[3]) {
+    int face = (int)floorf(py / (float)S);
+    face = face < 0 ? 0 : (face > 5 ? 5 : face);
+    const float s = 2.f * px / (float)S - 1.f;
+    const float t = 2.f * (py - (float)(face * S)) / (float)S - 1.f;
+    switch (face) {
+        case 0: d[0] = 1.f, d[1] = -t, d[2] = -s; break;
+        case 1: d[0] = -1.f, d[1] = -t, d[2] = s; break;
+        case 2: d[0] = s, d[1] = 1.f, d[2] = t; break;
+        case 3: d[0] = s, d[1] = -1.f, d[2] = -t; break;
+        case 4: d[0] = s, d[1] = -t, d[2] = 1.f; break;
+        default: d[0] = -s, d[1] = -t, d[2] = -1.f; break;
+    }
+}
+
+// equidistant fisheye: unit camera-space direction of (px, py) and its angle from the axis
+__device__ __forceinline__ float fisheye_dir(int H, int W, float f, float px, float py, float d[3]) {
+    const float u = px - 0.5f * (float)W, v = -(py - 0.5f * (float)H);
+    const float r = hypotf(u, v);
+    const float theta = r / f;
+    if (r > 0.f) {
+        float sn, cs;
+        sincosf(theta, &sn, &cs);
+        d[0] = sn * u / r;
+        d[1] = sn * v / r;
+        d[2] = -cs;
+    } else {
+        d[0] = 0.f, d[1] = 0.f, d[2] = -1.f;
+    }
+    return theta;
+}
+
+__device__ __forceinline__ void rotate(const float* m, int ld, const float c[3], float out[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = (m[ld * k] * c[0] + m[ld * k + 1] * c[1]) + m[ld * k + 2] * c[2];
+}
+
+__device__ __forceinline__ void normalize3(float d[3]) {
+    const float n = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = d[k] / n;
+}
+
+// world direction c2w[:3,:3] @ unit camera direction of pixel (i, j) of a cube or fisheye camera; returns the fisheye angle
+__device__ __forceinline__ float central_dir(int kind, int H, int W, const CamParams& p, const float* c2w, int i, int j,
+                                             float out[3]) {
+    float c[3], theta = 0.f;
+    if (kind == PN_CAM_CUBE) {
+        cube_dir(W, (float)j + 0.5f, (float)i + 0.5f, c);
+        normalize3(c);
+    } else {
+        theta = fisheye_dir(H, W, p.v[0], (float)j + 0.5f, (float)i + 0.5f, c);
+    }
+    rotate(c2w, 4, c, out);
+    return theta;
+}
+
+__global__ __launch_bounds__(kThreads) void k_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, CamParams p,
+                                                                 const int64_t* idx, const float* c2ws, float near_,
+                                                                 float far_, const float* rgb_pool, float* origins,
+                                                                 float* directions, float* viewdirs, float* radii,
+                                                                 float* lossmult, float* near_out, float* far_out,
+                                                                 float* noise_var, float* rgb_out) {
+    const int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (b >= B) return;
+    const int64_t hw = (int64_t)H * W;
+    int64_t r = idx[b];
+    r = (r >= 0 && r < hw * n_cam) ? r : 0;
+    const int cam = (int)(r / hw), pix = (int)(r % hw);
+    const int i = pix / W, j = pix % W;
+    const float* m = c2ws + 16 * (int64_t)cam;
+    if (kind == PN_CAM_STEREO_PANO) {
+        const PanoCam c{m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10], m[3], m[7], m[11]};
+        const PanoRay ray = pano_ray(H, W, c, i, j);
+        store_pano_ray(b, ray, c, near_, far_, origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var);
+        const float half = p.v[0];  // +ipd / 2 for the right eye, -ipd / 2 for the left
+        if (half != 0.f) {          // ipd = 0 keeps the panorama's origin bits
+            const float theta = -((float)j + 0.5f) / (float)W * 2.f * kPi;  // pano_ray's heading angle
+            const float off[3] = {half * -cosf(theta), 0.f, half * sinf(theta)};
+            float w[3];
+            rotate(m, 4, off, w);
+            origins[b * 3 + 0] = w[0] + m[3];
+            origins[b * 3 + 1] = w[1] + m[7];
+            origins[b * 3 + 2] = w[2] + m[11];
+        }
+    } else {
+        // cube rows count within the face: the last row of each face reuses the one before
+        const int rows = kind == PN_CAM_CUBE ? W : H;
+        const int top = kind == PN_CAM_CUBE ? (i / W) * W : 0;
+        const int y = i - top;
+        const int yy = y < rows - 1 ? y : rows - 2;
+        float d[3], a[3], n[3];
+        const float theta = central_dir(kind, H, W, p, m, i, j, d);
+        central_dir(kind, H, W, p, m, top + yy, j, a);
+        central_dir(kind, H, W, p, m, top + yy + 1, j, n);
+        const float dx = sqrtf((a[0] - n[0]) * (a[0] - n[0]) + (a[1] - n[1]) * (a[1] - n[1]) + (a[2] - n[2]) * (a[2] - n[2]));
+        const bool inside = kind == PN_CAM_CUBE || theta <= p.v[1];
+        if (!inside) {  // outside the image circle: the forward direction, no loss
+            const float fwd[3] = {0.f, 0.f, -1.f};
+            rotate(m, 4, fwd, d);
+        }
+        origins[b * 3 + 0] = m[3];
+        origins[b * 3 + 1] = m[7];
+        origins[b * 3 + 2] = m[11];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            directions[b * 3 + k] = d[k];
+            viewdirs[b * 3 + k] = d[k];
+        }
+        radii[b] = (float)((double)dx * 2.0 / sqrt(12.0));
+        lossmult[b] = inside ? 1.f : 0.f;
+        near_out[b] = near_;
+        far_out[b] = far_;
+        noise_var[b] = 0.f;
+    }
+    if (rgb_pool) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rgb_out[b * 3 + k] = rgb_pool[r * 3 + k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ reprojection
+// destination position (px, py) -> camera-space direction (not normalised); false outside the camera's coverage
+__device__ __forceinline__ bool dst_dir(int kind, int H, int W, const CamParams& p, float px, float py, float d[3]) {
+    if (kind == PN_CAM_PANO) {
+        const float theta = -(px / (float)W) * (2.f * kPi), phi = (py / (float)H) * kPi;
+        float st, ct, sp, cp;
+        sincosf(theta, &st, &ct);
+        sincosf(phi, &sp, &cp);
+        d[0] = sp * st, d[1] = cp, d[2] = sp * ct;
+        return true;
+    }
+    if (kind == PN_CAM_PINHOLE) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = (p.v[3 * k] * px + p.v[3 * k + 1] * py) + p.v[3 * k + 2];
+        return true;
+    }
+    if (kind == PN_CAM_CUBE) {
+        cube_dir(W, px, py, d);
+        return true;
+    }
+    return fisheye_dir(H, W, p.v[0], px, py, d) <= p.v[1];
+}
+
+// source direction -> continuous source pixel position; false where the source camera does not see it
+__device__ __forceinline__ bool src_pos(int kind, int H, int W, const CamParams& p, const float d[3], float& px, float& py,
+                                        int& face) {
+    face = 0;
+    if (kind == PN_CAM_PANO) {
+        const float phi = atan2f(hypotf(d[0], d[2]), d[1]), theta = atan2f(d[0], d[2]);
+        float t = -theta / (2.f * kPi);
+        t = t - floorf(t);
+        px = t * (float)W;
+        py = phi / kPi * (float)H;
+        return true;
+    }
+    if (kind == PN_CAM_PINHOLE) {
+        float q[3];
+        rotate(p.v + 9, 3, d, q);
+        if (!(q[2] > 0.f)) return false;
+        px = q[0] / q[2];
+        py = q[1] / q[2];
+        return px >= 0.f && px <= (float)W && py >= 0.f && py <= (float)H;
+    }
+    if (kind == PN_CAM_FISHEYE) {
+        const float rho = hypotf(d[0], d[1]);
+        const float theta = atan2f(rho, -d[2]);
+        if (!(theta <= p.v[1])) return false;
+        const float r = p.v[0] * theta;
+        px = 0.5f * (float)W, py = 0.5f * (float)H;
+        if (rho > 0.f) {
+            px = px + r * d[0] / rho;
+            py = py - r * d[1] / rho;
+        }
+        return px >= 0.f && px <= (float)W && py >= 0.f && py <= (float)H;
+    }
+    // cube: the major axis picks the face, ties to the earlier face of +x -x +y -y +z -z
+    const float ax = fabsf(d[0]), ay = fabsf(d[1]), az = fabsf(d[2]);
+    float s, t, mj;
+    if (ax >= ay && ax >= az) {
+        mj = ax;
+        if (d[0] > 0.f) face = 0, s = -d[2] / mj, t = -d[1] / mj;
+        else face = 1, s = d[2] / mj, t = -d[1] / mj;
+    } else if (ay >= az) {
+        mj = ay;
+        if (d[1] > 0.f) face = 2, s = d[0] / mj, t = d[2] / mj;
+        else face = 3, s = d[0] / mj, t = -d[2] / mj;
+    } else {
+        mj = az;
+        if (d[2] > 0.f) face = 4, s = d[0] / mj, t = -d[1] / mj;
+        else face = 5, s = -d[0] / mj, t = -d[1] / mj;
+    }
+    if (!(mj > 0.f)) return false;
+    px = (s + 1.f) * (0.5f * (float)W);
+    py = (t + 1.f) * (0.5f * (float)W);  // within the face
+    return true;
+}
+
+struct Taps {
+    int o[4];  // pixel index (row * Ws + column) of the four taps: (y0, x0) (y0, x1) (y1, x0) (y1, x1)
+    float w[4];
+};
+
+// bilinear taps of the continuous position (px, py) (pixel centres at k + 1/2): columns wrap for a panorama and clamp
+// otherwise, rows clamp; a cube's taps clamp within its face
+__device__ __forceinline__ Taps make_taps(int kind, int H, int W, float px, float py, int face) {
+    const float gx = px - 0.5f, gy = py - 0.5f;
+    const float fx = floorf(gx), fy = floorf(gy);
+    const float wx = gx - fx, wy = gy - fy;
+    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+    const int rows = kind == PN_CAM_CUBE ? W : H;
+    if (kind == PN_CAM_PANO) {
+        x0 = ((x0 % W) + W) % W;
+        x1 = ((x1 % W) + W) % W;
+    } else {
+        x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0);
+        x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
+    }
+    y0 = y0 < 0 ? 0 : (y0 > rows - 1 ? rows - 1 : y0);
+    y1 = y1 < 0 ? 0 : (y1 > rows - 1 ? rows - 1 : y1);
+    const int top = kind == PN_CAM_CUBE ? face * W : 0;
+    Taps t;
+    t.o[0] = (top + y0) * W + x0;
+    t.o[1] = (top + y0) * W + x1;
+    t.o[2] = (top + y1) * W + x0;
+    t.o[3] = (top + y1) * W + x1;
+    t.w[0] = (1.f - wy) * (1.f - wx);
+    t.w[1] = (1.f - wy) * wx;
+    t.w[2] = wy * (1.f - wx);
+    t.w[3] = wy * wx;
+    return t;
+}
+
+__global__ __launch_bounds__(kThreads) void k_reproject(int N, int C, int sk, int Hs, int Ws, CamParams sp, int dk, int Hd,
+                                                        int Wd, CamParams dp, Rot rot, int samples, float fill,
+                                                        const float* image, int64_t ns, int64_t cs, int64_t ps, float* out,
+                                                        float* coverage) {
+    const int64_t hw = (int64_t)Hd * Wd;
+    const int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (pix >= hw) return;
+    const int y = (int)(pix / Wd), x = (int)(pix % Wd);
+    const float inv_k = 1.f / (float)samples;
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const float* img = image + (int64_t)n * ns;
+        float* o = out + (int64_t)n * C * hw + pix;
+        for (int c0 = 0; c0 < C; c0 += kChan) {
+            float acc[kChan];
+#pragma unroll
+            for (int c = 0; c < kChan; ++c) acc[c] = 0.f;
+            int valid = 0;
+            for (int b = 0; b < samples; ++b) {
+                for (int a = 0; a < samples; ++a) {
+                    const float px = (float)x + ((float)a + 0.5f) * inv_k, py = (float)y + ((float)b + 0.5f) * inv_k;
+                    float d[3], e[3], qx, qy;
+                    int face;
+                    if (!dst_dir(dk, Hd, Wd, dp, px, py, d)) continue;
+                    rotate(rot.m, 3, d, e);
+                    if (!src_pos(sk, Hs, Ws, sp, e, qx, qy, face)) continue;
+                    const Taps t = make_taps(sk, Hs, Ws, qx, qy, face);
+                    ++valid;
+#pragma unroll
+                    for (int c = 0; c < kChan; ++c) {
+                        if (c0 + c < C) {
+                            const float* ch = img + (int64_t)(c0 + c) * cs;
+                            const float v = ((t.w[0] * ch[t.o[0] * ps] + t.w[1] * ch[t.o[1] * ps]) + t.w[2] * ch[t.o[2] * ps]) +
+                                            t.w[3] * ch[t.o[3] * ps];
+                            acc[c] = acc[c] + v;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < kChan; ++c) {
+                if (c0 + c < C) o[(int64_t)(c0 + c) * hw] = valid ? acc[c] / (float)valid : fill;
+            }
+            if (n == 0 && c0 == 0) coverage[pix] = (float)valid / (float)(samples * samples);
+        }
+    }
+}
+
+// minimum image size of a camera kind; false for an unknown kind
+bool min_size(int kind, int H, int W, bool& ok) {
+    switch (kind) {
+        case PN_CAM_PANO: ok = H >= 2 && W >= 3; return true;
+        case PN_CAM_STEREO_PANO: ok = H >= 2 && W >= 3; return true;
+        case PN_CAM_PINHOLE: ok = H >= 2 && W >= 2; return true;
+        case PN_CAM_FISHEYE: ok = H >= 2 && W >= 2; return true;
+        case PN_CAM_CUBE: ok = W >= 2 && (int64_t)H == 6 * (int64_t)W; return true;
+        default: return false;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, const float* params_host, const int64_t* idx,
+                          const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
+                          float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
+                          float* far_out, float* noise_var, float* rgb_out, void* stream) {
+    if (kind != PN_CAM_CUBE && kind != PN_CAM_FISHEYE && kind != PN_CAM_STEREO_PANO) return PN_ERR_UNSUPPORTED;
+    bool ok = false;
+    min_size(kind, H, W, ok);
+    if (B <= 0 || n_cam <= 0 || !ok || (int64_t)H * W >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
+    if (!params_host || !idx || !c2ws || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out ||
+        !far_out || !noise_var)
+        return PN_ERR_NULL;
+    if ((rgb_pool == nullptr) != (rgb_out == nullptr)) return PN_ERR_NULL;  // target colours: both or neither
+    if (kind == PN_CAM_FISHEYE && !(params_host[0] > 0.f && params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    CamParams p;
+    for (int k = 0; k < PN_CAM_PARAMS; ++k) p.v[k] = params_host[k];
+    hipLaunchKernelGGL(k_sample_camera_rays, dim3(nblk(B, kThreads)), dim3(kThreads), 0, ST(stream), B, n_cam, kind, H, W,
+                       p, idx, c2ws, near_, far_, rgb_pool, origins, directions, viewdirs, radii, lossmult, near_out,
+                       far_out, noise_var, rgb_out);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_reproject(int N, int C, int src_kind, int Hs, int Ws, const float* src_params_host, int dst_kind, int Hd, int Wd,
+                 const float* dst_params_host, const float* rotation_host, int samples, float fill, const float* image,
+                 int64_t image_stride, int64_t cs, int64_t ps, float* out, float* coverage, void* stream) {
+    bool oks = false, okd = false;
+    if (!min_size(src_kind, Hs, Ws, oks) || !min_size(dst_kind, Hd, Wd, okd)) return PN_ERR_UNSUPPORTED;
+    if (src_kind == PN_CAM_STEREO_PANO || dst_kind == PN_CAM_STEREO_PANO) return PN_ERR_UNSUPPORTED;  // not central
+    if (N <= 0 || C <= 0 || !oks || !okd || samples <= 0 || samples > PN_REPROJECT_MAX_SAMPLES ||
+        (int64_t)Hs * Ws >= ((int64_t)1 << 31) || (int64_t)Hd * Wd >= ((int64_t)1 << 31))
+        return PN_ERR_BAD_SHAPE;
+    if (!src_params_host || !dst_params_host || !rotation_host || !image || !out || !coverage) return PN_ERR_NULL;
+    if (src_kind == PN_CAM_FISHEYE && !(src_params_host[0] > 0.f && src_params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    if (dst_kind == PN_CAM_FISHEYE && !(dst_params_host[0] > 0.f && dst_params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    CamParams sp, dp;
+    Rot rot;
+    for (int k = 0; k < PN_CAM_PARAMS; ++k) sp.v[k] = src_params_host[k], dp.v[k] = dst_params_host[k];
+    for (int k = 0; k < 9; ++k) rot.m[k] = rotation_host[k];
+    const dim3 grid(nblk((int64_t)Hd * Wd, kThreads), (unsigned)(N < 65535 ? N : 65535));
+    hipLaunchKernelGGL(k_reproject, grid, dim3(kThreads), 0, ST(stream), N, C, src_kind, Hs, Ws, sp, dst_kind, Hd, Wd, dp,
+                       rot, samples, fill, image, image_stride, cs, ps, out, coverage);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+}  // extern "C"

@@ -14,6 +14,7 @@ raise: there is no host fallback.
     field_irradiance(model, points, normals, env_rays)  [M, 3] the renderer's own shading estimate at arbitrary points
     irradiance_volume(model, bounds, resolution, ...)   IrradianceVolume(sh [nx, ny, nz, 9, 3], lo, step)
     sample_irradiance(volume, points, normals)  [M, 3] trilinear SH interpolation, then irradiance
+    probes_to_cubemaps(probes, size, samples)   [P, 3, 6 size, size] cube-map strips of [P, 3, H, W] probes
 
 Conventions (pixel directions, solid angles, SH order and constants) are stated in include/panonerf_hip.h.  Normals are
 taken as given: pass unit vectors.  A probe is a plain HDR image: io_exr.write_exr writes one.
@@ -293,3 +294,13 @@ def sample_irradiance(volume, points, normals):
         _lib.call("pn_sh_volume_irradiance", *(int(v) for v in sh.shape[:3]), *(float(v) for v in lo),
                   *(float(v) for v in step), s.data_ptr(), M, p.data_ptr(), n.data_ptr(), out.data_ptr(), _stream(dev))
     return out
+
+
+def probes_to_cubemaps(probes, size, samples=4):
+    """[P, 3, 6 size, size] fp32: each [3, H, W] probe as a cube map (a vertical strip of the faces +x, -x, +y, -y, +z,
+    -z in the lookup convention engines use; views.cubemap_camera), every texel the mean of samples x samples bilinear
+    fetches: views.reproject(probes, pano_camera(H, W), cubemap_camera(size), samples=samples)[0]."""
+    from . import views
+    _probe_view(probes)
+    H, W = int(probes.shape[2]), int(probes.shape[3])
+    return views.reproject(probes, views.pano_camera(H, W), views.cubemap_camera(size), samples=samples)[0]

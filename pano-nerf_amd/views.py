@@ -1,13 +1,21 @@
-"""Novel views of a trained model: perspective (pinhole) cameras, camera paths and viewable frames.
+"""Novel views of a trained model: cameras (pinhole, panorama, cube map, fisheye, stereo panorama), camera paths, viewable
+frames and reprojection of images between cameras.
 
 Pano-NeRF's models are trained on panoramas, but what a user renders from a trained model is a new view.  This module
 renders one (or a whole path of them) and turns the renderer's outputs into the uint8 images the reference's validation
 writes.  Ray generation and frames run on the HIP device through ``pn_views.hip`` (the renderer's own entry points do the
-rest), under ``torch.no_grad()`` on the current stream; CPU tensors raise, there is no host fallback.  Cameras and paths
-are host-side numpy.
+rest) and ``pn_cameras.hip`` (cube-map, fisheye and stereo-panorama rays, reprojection), under ``torch.no_grad()`` on the
+current stream; CPU tensors raise, there is no host fallback.  Cameras and paths are host-side numpy.
 
     perspective_camera(h, w, focal | fov_x_deg | pix2cam)   PinholeCamera(h, w, pix2cam [3, 3] fp32)
     pano_camera(h, w)                           PanoCamera(h, w): the equirectangular camera of generate_pano_rays
+    cubemap_camera(size)                        CubeCamera(h = 6 size, w = size): faces +x -x +y -y +z -z as a vertical strip
+    fisheye_camera(h, w, fov_deg | focal)       FisheyeCamera(h, w, focal, fov_deg): equidistant, looking along -z
+    stereo_pano_camera(h, w, ipd, eye)          StereoPanoCamera(h, w, ipd, eye): one eye of an omnidirectional-stereo pair
+    camera_mask(camera)                         bool [H, W]: inside the fisheye's image circle (all true otherwise)
+    cube_faces(x)                               [.., C, 6 S, S] -> [.., 6, C, S, S]
+    cube_solid_angles(size)                     float64 [6 S, S] exact texel solid angles (sum 4 pi)
+    generate_camera_rays(camera, c2w, ...)      Rays of [H W, C] device tensors for any camera
     generate_perspective_rays(camera, c2w, ...) Rays of [H W, C] device tensors (datasets/base_datasets.py:118-265)
     PerspectiveRayPool(camera, c2ws, images)    the pinhole counterpart of DeviceRayPool: take / sample / rays / len
     interpolate_path(c2ws, n_views)             gen_render_path (utils/vis.py:136-165), numpy only
@@ -17,8 +25,11 @@ are host-side numpy.
     to_frame(image, kind, near, far, exposure)  uint8 [H, W, 3] of one render_image output (utils/vis.py:13-41)
     render_view(model, camera, c2w, ...)        dict of [1, C, H, W] outputs named as render_image's
     render_path(model, camera, poses, ...)      dict kind -> uint8 [n, H, W, 3] frames (or PNG / EXR files)
+    render_stereo_pano(model, h, w, ipd, c2w, ...)  render_view's dict, the left eye stacked on the right: [1, C, 2 H, W]
+    reproject(image, src_camera, dst_camera, ...)   (out [N, C, Hd, Wd], coverage [Hd, Wd]): resample between cameras
 
-Conventions (pixel directions, radii, frame bytes) are stated in include/panonerf_hip.h.
+Conventions (pixel directions, radii, frame bytes, the cube-map table, the inverse projections) are stated in
+include/panonerf_hip.h.
 """
 import collections
 import math
@@ -33,6 +44,13 @@ from .rays import Rays, _DIMS
 
 PinholeCamera = collections.namedtuple("PinholeCamera", ["h", "w", "pix2cam"])
 PanoCamera = collections.namedtuple("PanoCamera", ["h", "w"])
+CubeCamera = collections.namedtuple("CubeCamera", ["h", "w"])
+FisheyeCamera = collections.namedtuple("FisheyeCamera", ["h", "w", "focal", "fov_deg"])
+StereoPanoCamera = collections.namedtuple("StereoPanoCamera", ["h", "w", "ipd", "eye"])
+# camera kinds of pn_cameras.hip (include/panonerf_hip.h)
+_CAM_PANO, _CAM_PINHOLE, _CAM_CUBE, _CAM_FISHEYE, _CAM_STEREO_PANO = range(5)
+_CAM_PARAMS = 20
+_MAX_SAMPLES = 16
 
 _FRAME_KINDS = {"ldr": 0, "ldr_gt": 1, "depth": 2, "normal": 3, "albedo": 4}
 # render_view outputs -> the render_image names they fill
@@ -99,14 +117,129 @@ def pano_camera(height, width):
     return PanoCamera(*_hw(height, width, 3))
 
 
+def cubemap_camera(size):
+    """CubeCamera(h = 6 size, w = size), size >= 2: a cube map as a vertical strip of faces in the order +x, -x, +y, -y,
+    +z, -z.  Face texel (x, y) has s = 2 (x + 1/2) / size - 1, t = 2 (y + 1/2) / size - 1 (t points down) and looks along
+    +x (1, -t, -s), -x (-1, -t, s), +y (s, 1, t), -y (s, -1, -t), +z (s, -t, 1), -z (-s, -t, -1): the OpenGL cube-map
+    table, i.e. the lookup convention of engines (a face viewed as a picture is mirrored relative to a pinhole view)."""
+    s = int(size)
+    if s != size or s < 2:
+        raise ValueError(f"a cube map needs an integer size >= 2; got {size!r}")
+    return CubeCamera(6 * s, s)
+
+
+def fisheye_camera(height, width, fov_deg=180.0, focal=None):
+    """FisheyeCamera(h, w, focal, fov_deg): an equidistant fisheye looking along -z like the pinhole, 0 < fov_deg <= 360.
+    With u = x + 1/2 - w/2, v = -(y + 1/2 - h/2), r = hypot(u, v), the pixel looks theta = r / focal away from the axis
+    along (sin theta u / r, sin theta v / r, -cos theta).  focal (pixels per radian) defaults to (min(h, w) / 2) /
+    radians(fov_deg / 2): the image circle touches the shorter side.  A pixel is inside when theta <= radians(fov_deg / 2);
+    outside pixels get the forward direction and lossmult = 0, and render_view / render_path return 0 in every channel
+    there.  They are still rendered: up to 1 - pi / 4 of the frame's rays for a full circle in a square are spent on
+    pixels that end up 0 (there is no compaction of the inside rays)."""
+    h, w = _hw(height, width)
+    fov = float(fov_deg)
+    if not 0.0 < fov <= 360.0:
+        raise ValueError(f"fov_deg must lie in (0, 360]; got {fov_deg!r}")
+    if focal is None:
+        focal = 0.5 * min(h, w) / math.radians(0.5 * fov)
+    f = float(focal)
+    if not (f > 0.0 and math.isfinite(f)):
+        raise ValueError(f"focal must be positive and finite; got {focal!r}")
+    return FisheyeCamera(h, w, f, fov)
+
+
+def stereo_pano_camera(height, width, ipd, eye):
+    """StereoPanoCamera(h, w, ipd, eye), eye "left" or "right": one eye of an omnidirectional-stereo (ODS) pair.  Every
+    pixel looks along the panorama camera's direction; column j (heading angle theta_j = -(j + 1/2) 2 pi / w) starts at
+    the camera-space origin +-(ipd / 2) (-cos theta_j, 0, sin theta_j), + for the right eye: heading x up, so the ray is
+    tangent to the viewing circle of diameter ipd.  radii and noise_var are the panorama camera's; with ipd = 0 the rays
+    are the panorama camera's bit for bit."""
+    h, w = _hw(height, width, 3)
+    d = float(ipd)
+    if not (d >= 0.0 and math.isfinite(d)):
+        raise ValueError(f"ipd must be finite and >= 0; got {ipd!r}")
+    if eye not in ("left", "right"):
+        raise ValueError(f"eye must be 'left' or 'right'; got {eye!r}")
+    return StereoPanoCamera(h, w, d, eye)
+
+
+_CAMERAS = (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, StereoPanoCamera)
+
+
 def _camera(camera):
     if isinstance(camera, PinholeCamera):
         if np.asarray(camera.pix2cam).shape != (3, 3):
             raise ValueError("PinholeCamera.pix2cam must be 3x3")
         return camera
+    if isinstance(camera, CubeCamera):
+        if camera.w < 2 or camera.h != 6 * camera.w:
+            raise ValueError(f"a CubeCamera is 6 size x size with size >= 2; got {camera.h} x {camera.w}")
+        return camera
+    if isinstance(camera, FisheyeCamera):
+        if not (camera.focal > 0.0 and 0.0 < camera.fov_deg <= 360.0):
+            raise ValueError("a FisheyeCamera needs focal > 0 and 0 < fov_deg <= 360")
+        return camera
+    if isinstance(camera, StereoPanoCamera):
+        if camera.eye not in ("left", "right") or not camera.ipd >= 0.0:
+            raise ValueError("a StereoPanoCamera needs ipd >= 0 and eye 'left' or 'right'")
+        return camera
     if isinstance(camera, PanoCamera):
         return camera
-    raise ValueError(f"camera must come from perspective_camera or pano_camera; got {type(camera).__name__}")
+    raise ValueError("camera must come from perspective_camera, pano_camera, cubemap_camera, fisheye_camera or "
+                     f"stereo_pano_camera; got {type(camera).__name__}")
+
+
+def _kind_params(camera):
+    """(kind, params float32 [_CAM_PARAMS]) of a camera for pn_cameras.hip (the layout of include/panonerf_hip.h)."""
+    p = np.zeros(_CAM_PARAMS, np.float32)
+    if isinstance(camera, PinholeCamera):
+        m = np.asarray(camera.pix2cam, np.float32).reshape(3, 3)
+        p[:9] = m.reshape(9)
+        p[9:18] = np.linalg.inv(m.astype(np.float64)).reshape(9)  # cam2pix: inverted in fp64, rounded once
+        return _CAM_PINHOLE, p
+    if isinstance(camera, CubeCamera):
+        return _CAM_CUBE, p
+    if isinstance(camera, FisheyeCamera):
+        p[0], p[1] = camera.focal, math.radians(0.5 * camera.fov_deg)
+        return _CAM_FISHEYE, p
+    if isinstance(camera, StereoPanoCamera):
+        p[0] = (0.5 if camera.eye == "right" else -0.5) * camera.ipd
+        return _CAM_STEREO_PANO, p
+    return _CAM_PANO, p
+
+
+def camera_mask(camera):
+    """bool [H, W] numpy: the pixels a camera sees.  For a fisheye, the pixels whose centre lies inside the image circle
+    (theta <= radians(fov_deg / 2), evaluated in float64); all true for every other camera."""
+    camera = _camera(camera)
+    if not isinstance(camera, FisheyeCamera):
+        return np.ones((camera.h, camera.w), bool)
+    u = np.arange(camera.w) + 0.5 - 0.5 * camera.w
+    v = -(np.arange(camera.h) + 0.5 - 0.5 * camera.h)
+    return np.hypot(u[None, :], v[:, None]) / camera.focal <= math.radians(0.5 * camera.fov_deg)
+
+
+def cube_faces(x):
+    """[.., C, 6 S, S] -> [.., 6, C, S, S]: the faces (+x, -x, +y, -y, +z, -z) of cube-map strips, as a view where the
+    layout allows (torch tensor or numpy array)."""
+    shape = tuple(x.shape)
+    if len(shape) < 3 or shape[-1] < 1 or shape[-2] != 6 * shape[-1]:
+        raise ValueError(f"a cube-map strip is [.., C, 6 S, S]; got {shape}")
+    S = shape[-1]
+    y = x.reshape(*shape[:-2], 6, S, S)
+    return y.movedim(-3, -4) if isinstance(y, torch.Tensor) else np.moveaxis(y, -3, -4)
+
+
+def cube_solid_angles(size):
+    """float64 [6 size, size]: the exact solid angle of every texel of cubemap_camera(size), from the corner function
+    A(x, y) = atan2(x y, sqrt(x^2 + y^2 + 1)) of the face plane at distance 1: A(x1, y1) - A(x0, y1) - A(x1, y0) +
+    A(x0, y0) over the texel's edges in (s, t).  The sum is 4 pi."""
+    S = cubemap_camera(size).w
+    e = 2.0 * np.arange(S + 1, dtype=np.float64) / S - 1.0
+    x, y = e[None, :], e[:, None]
+    a = np.arctan2(x * y, np.sqrt(x * x + y * y + 1.0))
+    face = a[1:, 1:] - a[1:, :-1] - a[:-1, 1:] + a[:-1, :-1]
+    return np.tile(face, (6, 1))
 
 
 def _c2w_stack(c2ws, single=False):
@@ -125,11 +258,14 @@ def _c2w_stack(c2ws, single=False):
 
 
 def _device_cams(camera, c2ws, dev):
-    """(pix2cams [n, 9] or None, c2ws [n, 16]) fp32 device arrays for the ray kernels."""
+    """(pix2cams [n, 9] or None, c2ws [n, 16]) fp32 device arrays for the ray kernels.  For a cube, fisheye or
+    stereo-panorama camera the first entry is the host parameter block of pn_sample_camera_rays instead."""
     n = c2ws.shape[0]
     c = torch.from_numpy(np.ascontiguousarray(c2ws.astype(np.float32).reshape(n, 16))).to(dev)
     if isinstance(camera, PanoCamera):
         return None, c
+    if isinstance(camera, (CubeCamera, FisheyeCamera, StereoPanoCamera)):
+        return _kind_params(camera)[1], c
     p = np.tile(np.asarray(camera.pix2cam, np.float32).reshape(1, 9), (n, 1))
     return torch.from_numpy(p).to(dev), c
 
@@ -144,10 +280,26 @@ def _sample(camera, n_cam, pix2cams, c2ws, idx, near, far, rgb_pool, dev):
         if isinstance(camera, PanoCamera):
             _lib.call("pn_sample_pano_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), c2ws.data_ptr(), float(near),
                       float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
+        elif isinstance(camera, (CubeCamera, FisheyeCamera, StereoPanoCamera)):
+            _lib.call("pn_sample_camera_rays", B, n_cam, _kind_params(camera)[0], camera.h, camera.w, pix2cams.ctypes.data,
+                      idx.data_ptr(), c2ws.data_ptr(), float(near), float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb),
+                      _stream(dev))
         else:
             _lib.call("pn_sample_pinhole_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), pix2cams.data_ptr(),
                       c2ws.data_ptr(), float(near), float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
     return Rays(*outs), rgb
+
+
+def generate_camera_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
+    """One camera of any model -> Rays of [H W, C] fp32 device tensors (row-major pixels): the rays render_view renders
+    for it (pn_sample_pano_rays, pn_sample_pinhole_rays or pn_sample_camera_rays over idx = arange(H W))."""
+    camera = _camera(camera)
+    c2ws = _c2w_stack(c2w, single=True)
+    dev = _cuda_device(device)
+    p, c = _device_cams(camera, c2ws, dev)
+    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        return _sample(camera, 1, p, c, idx, near, far, None, dev)[0]
 
 
 def generate_perspective_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
@@ -449,6 +601,11 @@ def _render_rows(model, camera, pix2cams, c2ws, n_cam, first, count, env_rays, s
                 comp0, dist0, comp1, dist1, _, normal, albedo, surface, _, shading = outs
                 got = dict(coarse_rgb=comp0, fine_rgb=comp1, coarse_dep=dist0, fine_dep=dist1, fine_nor=normal,
                            albedo=albedo, surface_rgb=surface, shading=shading)
+                if isinstance(camera, FisheyeCamera):  # 0 in every channel outside the image circle
+                    seen = rays.lossmult > 0
+                    for name, buf in bufs.items():
+                        buf[s:s + n].copy_(torch.where(seen, got[name].reshape(n, -1), 0.0))
+                    continue
                 for name, buf in bufs.items():
                     buf[s:s + n].copy_(got[name].reshape(n, -1))
     finally:
@@ -476,8 +633,9 @@ _WIDTH = dict(coarse_rgb=3, fine_rgb=3, coarse_dep=1, fine_dep=1, fine_nor=3, al
 def render_view(model, camera, c2w, env_rays=None, outputs=("rgb", "depth", "normal"), near=0.0, far=10.0,
                 chunk_rays=32768):
     """One view -> dict of [1, C, H, W] fp32 tensors named as render_image's (coarse_rgb, fine_rgb for "rgb"; coarse_dep,
-    fine_dep for "depth"; fine_nor for "normal"; albedo, surface_rgb, shading).  camera: perspective_camera(...) or
-    pano_camera(h, w).  Runs the least renderer configuration the outputs need: rgb and depth take the two levels only,
+    fine_dep for "depth"; fine_nor for "normal"; albedo, surface_rgb, shading).  camera: perspective_camera(...),
+    pano_camera(h, w), cubemap_camera(size) (a 6 size x size strip), fisheye_camera(...) (0 outside the image circle) or
+    stereo_pano_camera(...).  Runs the least renderer configuration the outputs need: rgb and depth take the two levels only,
     "normal" adds the density-gradient sweep, albedo / surface / shading add the light gather (a PanoMipNeRF and env_rays
     required).  PanoMipNeRF and MipNeRF both work."""
     camera, dev, chunk = _setup(model, camera, chunk_rays)
@@ -542,3 +700,65 @@ def render_path(model, camera, poses, env_rays=None, kinds=("ldr", "depth", "nor
                     else:
                         io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
     return frames
+
+
+def render_stereo_pano(model, height, width, ipd, c2w, env_rays=None, outputs=("rgb", "depth", "normal"), near=0.0,
+                       far=10.0, chunk_rays=32768):
+    """An omnidirectional-stereo pair -> render_view's dict with the left eye stacked on top of the right: [1, C, 2 H, W]
+    (the top-bottom layout headsets take).  Exactly render_view of stereo_pano_camera(height, width, ipd, "left") and
+    (..., "right"), concatenated along the rows."""
+    eyes = [render_view(model, stereo_pano_camera(height, width, ipd, eye), c2w, env_rays, outputs, near, far, chunk_rays)
+            for eye in ("left", "right")]
+    return {k: torch.cat([eyes[0][k], eyes[1][k]], 2) for k in eyes[0]}
+
+
+# ----------------------------------------------------------------------------------------------------- reprojection
+def reproject(image, src_camera, dst_camera, rotation=None, samples=1, fill=0.0):
+    """Resample image ([C, Hs, Ws] or [N, C, Hs, Ws] fp32 device tensor, any C, seen by src_camera) into dst_camera's
+    pixels: -> (out [N, C, Hd, Wd] fp32, coverage [Hd, Wd] fp32), one fused kernel (pn_reproject).  Either camera may be
+    a panorama, pinhole, cube-map or fisheye camera; a stereo-panorama camera is not a central projection and raises
+    ValueError.  rotation: 3x3 matrix taking a dst camera-space direction to a src camera-space direction (identity by
+    default); for two posed cameras at one position it is R_src_c2w^T R_dst_c2w.
+
+    Every destination pixel takes samples x samples positions (x + (a + 1/2) / samples, y + (b + 1/2) / samples), sends
+    each through the dst camera to a direction, rotates it, projects it with the src camera and fetches bilinearly (a
+    panorama wraps in columns; everything else clamps; a cube clamps within the face).  out is the mean of the valid
+    subsamples (fp32, fixed order), coverage their fraction; with none, every channel is `fill`.  NaN in the source
+    propagates.  Repeated calls give the same bits.  Permuted views (e.g. [N, H, W, C] buffers) are read in place."""
+    src, dst = _camera(src_camera), _camera(dst_camera)
+    if isinstance(src, StereoPanoCamera) or isinstance(dst, StereoPanoCamera):
+        raise ValueError("a stereo-panorama camera is not a central projection: it cannot be reprojected")
+    k = int(samples)
+    if k != samples or not 1 <= k <= _MAX_SAMPLES:
+        raise ValueError(f"samples must be an integer in [1, {_MAX_SAMPLES}]; got {samples!r}")
+    rot = np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64)
+    if rot.shape != (3, 3) or not np.isfinite(rot).all():
+        raise ValueError(f"rotation must be a finite 3x3 matrix; got shape {rot.shape}")
+    if not isinstance(image, torch.Tensor) or image.dim() not in (3, 4):
+        raise ValueError(f"image must be a [C, Hs, Ws] or [N, C, Hs, Ws] tensor; got {getattr(image, 'shape', type(image))}")
+    x = image.detach()
+    if x.dim() == 3:
+        x = x[None]
+    N, C, Hs, Ws = (int(v) for v in x.shape)
+    if N < 1 or C < 1:
+        raise ValueError("image is empty")
+    if (Hs, Ws) != (src.h, src.w):
+        raise ValueError(f"image is {Hs} x {Ws} but src_camera is {src.h} x {src.w}")
+    if x.device.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (the image is on %s); there is no CPU fallback"
+                           % x.device)
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    sn, sc, sh, sw = x.stride()
+    if sh != Ws * sw or min(sn, sc, sw) < 0:  # rows are not evenly spaced pixels: read a copy
+        x = x.contiguous()
+        sn, sc, sh, sw = x.stride()
+    dev = x.device
+    (sk, sp), (dk, dp) = _kind_params(src), _kind_params(dst)
+    r32 = np.ascontiguousarray(rot.astype(np.float32).reshape(9))
+    out = torch.empty(N, C, dst.h, dst.w, dtype=torch.float32, device=dev)
+    cov = torch.empty(dst.h, dst.w, dtype=torch.float32, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        _lib.call("pn_reproject", N, C, sk, src.h, src.w, sp.ctypes.data, dk, dst.h, dst.w, dp.ctypes.data, r32.ctypes.data,
+                  k, float(fill), x.data_ptr(), sn, sc, sw, out.data_ptr(), cov.data_ptr(), _stream(dev))
+    return out, cov

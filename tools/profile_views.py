@@ -8,7 +8,13 @@ the spread (max - min) of each are printed as one JSON line.
 --what kernels: the two new kernels alone (pn_sample_pinhole_rays over every ray of the path, pn_to_frame for each kind
 at --size) with their bytes moved.  Run it under rocprofv3 for the kernel trace:
 
+--what cameras: render_view of a 6 x 256 cube map and of a 512 x 1024 stereo-panorama pair next to the panorama
+render_view of the same run (rays/s: the renderer is the same, so should the rate be), and views.reproject of a
+512 x 1024 x 3 panorama to a 6 x 512 cube at samples 1 and 4 and of 64 probes of 32 x 64 to cubes of 16, each as device
+time and as bytes moved (source read once + output and coverage written) over that time, next to the HBM copy rate.
+
     python tools/profile_views.py --what path --size 480x640
+    python tools/profile_views.py --what cameras
     python tools/profile_views.py --what path --size 120x160
     python tools/profile_views.py --what kernels --size 480x640
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/profile_views.py --what kernels --size 480x640
@@ -66,13 +72,53 @@ def event_ms(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+HBM_COPY_TB_S = 6.29  # measured float4 copy rate of one MI355X (8.0 TB/s spec)
+
+
+def cameras(repeats):
+    out = dict(what="cameras", hbm_copy_tb_per_s=HBM_COPY_TB_S, repeats=repeats)
+    model = setup()
+    c2w = views.look_at([0.2, 0.1, 0.3], [0.0, 0.0, -1.0])
+    out.update(mlp_mode=model.mlp_mode, num_samples=model.num_samples)
+    ipd = 0.064
+    legs = {"render_view_pano_512x1024": (512 * 1024, lambda: views.render_view(model, views.pano_camera(512, 1024), c2w)),
+            "render_view_cube_6x256": (6 * 256 * 256, lambda: views.render_view(model, views.cubemap_camera(256), c2w)),
+            "render_stereo_pano_512x1024": (2 * 512 * 1024, lambda: views.render_stereo_pano(model, 512, 1024, ipd, c2w))}
+    views.render_view(model, views.pano_camera(64, 128), c2w)  # warm-up: allocator, packed weights
+    times = {k: [] for k in legs}
+    for _ in range(repeats):
+        for k, (_, fn) in legs.items():
+            times[k].append(timed(fn))
+    for k, t in times.items():
+        med = float(np.median(t))
+        out[k] = dict(rays=legs[k][0], seconds=t, median_s=med, spread_s=float(max(t) - min(t)), rays_per_s=legs[k][0] / med)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    pano = torch.rand(1, 3, 512, 1024, device="cuda", generator=g) * 4.0
+    probes = (torch.rand(64, 32, 64, 3, device="cuda", generator=g) * 4.0).permute(0, 3, 1, 2)  # as light_probes returns them
+    res = {}
+    for name, x, src, dst, k in (("pano_512x1024x3_to_cube_512_s1", pano, views.pano_camera(512, 1024), views.cubemap_camera(512), 1),
+                                 ("pano_512x1024x3_to_cube_512_s4", pano, views.pano_camera(512, 1024), views.cubemap_camera(512), 4),
+                                 ("64_probes_32x64_to_cube_16_s4", probes, views.pano_camera(32, 64), views.cubemap_camera(16), 4)):
+        ms = event_ms(lambda: views.reproject(x, src, dst, samples=k), 50)
+        N, C = int(x.shape[0]), int(x.shape[1])
+        byts = 4 * (N * C * src.h * src.w + N * C * dst.h * dst.w + dst.h * dst.w)
+        res[name] = dict(call_ms=ms, bytes=byts, tb_per_s=byts / (ms * 1e-3) / 1e12,
+                         share_of_hbm_copy=byts / (ms * 1e-3) / 1e12 / HBM_COPY_TB_S,
+                         subsamples_per_s=N * dst.h * dst.w * k * k / (ms * 1e-3))
+    out["reproject"] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=("path", "kernels"), required=True)
+    ap.add_argument("--what", choices=("path", "kernels", "cameras"), required=True)
     ap.add_argument("--size", default="480x640")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.what == "cameras":
+        print(json.dumps(cameras(a.repeats)))
+        return
     H, W = (int(s) for s in a.size.split("x"))
     cam = views.perspective_camera(H, W, fov_x_deg=60.0)
     path = poses(a.frames)
