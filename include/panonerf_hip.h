@@ -704,6 +704,54 @@ int pn_shadow_ratio_bvh(int64_t R, int H, int W, const float* x, int64_t cs, int
                         const float* omega, const float* points, const float* normals, float bias, int64_t F,
                         const float* tris, const float* nodes, const float* bsphere, float* out, void* stream);
 
+/* ---- texture-mapped materials for inserted objects (pn_textures.hip): runs after pn_object_hits, which is untouched ------
+ * Storage: a texture of H x W texels (1 <= H, W <= PN_TEX_MAX_SIZE) is one fp32 device buffer of float4 texels (16-byte
+ * aligned), all mip levels concatenated: level l has h_l = max(1, H >> l) rows of w_l = max(1, W >> l) texels, row-major,
+ * L = 1 + floor(log2(max(H, W))) levels, level 0 first.  pn_tex_floats(H, W) = 4 sum_l h_l w_l is the size in floats.
+ * pn_tex_ingest writes level 0 from a device image [H, W, C] (1 <= C <= 4), uint8 (is_u8 != 0) or fp32: channels past C
+ * are 0 and alpha (channel 3) is 1.  A uint8 channel 0 .. 2 is table[byte] (256 device floats the caller built: i / 255
+ * or the sRGB EOTF, rounded once from fp64), a uint8 alpha is fl(i / 255); fp32 is copied.
+ * pn_tex_pyramid fills levels 1 .. L-1 on `stream`, one launch per level: texel (y, x) of level l+1 is
+ * ((a + b) + (c + d)) * 0.25f in fp32, a = (r0, c0), b = (r0, c1), c = (r1, c0), d = (r1, c1) of level l with rows
+ * r0 = min(2y, h_l - 1), r1 = min(2y + 1, h_l - 1) and columns c0 = min(2x, w_l - 1), c1 = min(2x + 1, w_l - 1).
+ * pn_texture_hits, per row r of the outputs of pn_object_hits (mask, and the face, bary, directions, t it was given;
+ * normals_in = its shading normals, already flipped towards the eye), with uv [T, 2] and face_uv [F, 3] int32 (NULL: the
+ * UVs are per vertex and indexed by faces), radii [R] or NULL, and up to three textures (NULL: no such map) - albedo,
+ * roughness (channel 0) and a tangent-space normal map: writes albedo [R, 3], roughness [R], normals [R, 3] (normals may
+ * alias normals_in) and, when not NULL, lod [R, 3] = the level of detail used per texture (0 for a NULL one).  An output
+ * whose texture is NULL is not touched and may be NULL.  Rows outside the mask (or whose face / vertex index is out of
+ * range) get zeros.  For a masked row, all in fp64 on the fp32 inputs, rounded once per output:
+ *   UV: (U, V) = w0 uv0 + u uv1 + v uv2, (u, v) = bary, w0 = 1 - u - v.  A non-finite U or V gives sample 0; a face_uv
+ *     index outside [0, T) reads as a non-finite UV.
+ *   Footprint (ray cone; Akenine-Moeller et al., Ray Tracing Gems ch. 20): e1 = v1 - v0, e2 = v2 - v0, A_w = |e1 x e2|,
+ *     A_uv = |du1 dv2 - du2 dv1| (du_i = u_i - u_0, ...), c = |n_g . d| / |d| with n_g = (e1 x e2) / A_w, width = 2 radii[r]
+ *     t[r] (the renderer's cone radius at o + t d is t radii; radii NULL: width 0).  Per texture
+ *     lambda = 0.5 log2(W H A_uv / A_w) + log2(width) - log2(c), clamped to [0, L - 1], NaN -> 0: a zero footprint samples
+ *     level 0 and a grazing ray the top level; no epsilon is involved.
+ *   Bilinear at level l: x = U w_l - 0.5, y = (flip_v ? 1 - V : V) h_l - 0.5, x0 = floor(x), fx = x - x0 (likewise y); the
+ *     indices x0, x0 + 1 are wrapped by a non-negative modulo (wrap = 0, repeat) or clamped to [0, w_l - 1] (wrap = 1);
+ *     value = (1 - fy) ((1 - fx) a00 + fx a01) + fy ((1 - fx) a10 + fx a11).
+ *   Trilinear: l0 = floor(lambda), f = lambda - l0, l1 = min(l0 + 1, L - 1), out = (1 - f) s(l0) + f s(l1) (f == 0 reads
+ *     level l0 only).  Roughness is channel 0, unclamped.
+ *   Normal map: m = 2 s - 1, det = du1 dv2 - du2 dv1, T = (e1 dv2 - e2 dv1) / det, B = (e2 du1 - e1 du2) / det, N =
+ *     normals_in[r]; T' = normalize(T - N (N . T)), B' = normalize(B - N (N . B) - T' (T' . B)) (Gram-Schmidt, no cross
+ *     product: the handedness follows the UVs), n = normalize(m.x T' + m.y B' + m.z N).  The output is N, bit for bit,
+ *     when det == 0, when a norm before normalising is < 1e-12, when anything is non-finite (a non-finite UV included),
+ *     or when n . d >= 0 (the perturbed normal faces away from the eye).
+ * One thread per row or texel, no LDS, no atomics: repeated calls give the same bits, whatever R.  R = 0 launches nothing.
+ * Errors: PN_ERR_BAD_SHAPE (a size outside [1, PN_TEX_MAX_SIZE], C outside [1, 4], a negative count, wrap not 0 or 1),
+ * PN_ERR_NULL (a required pointer, or the output of a texture that is given). */
+#define PN_TEX_MAX_SIZE 16384
+int64_t pn_tex_floats(int H, int W);
+int pn_tex_ingest(int H, int W, int C, int is_u8, const void* image, const float* table, float* tex, void* stream);
+int pn_tex_pyramid(int H, int W, float* tex, void* stream);
+int pn_texture_hits(int64_t R, const uint8_t* mask, const int32_t* face, const float* bary, const float* directions,
+                    const float* t, const float* normals_in, const float* radii, int64_t V, const float* vertices,
+                    int64_t F, const int32_t* faces, int64_t T, const float* uv, const int32_t* face_uv,
+                    const float* albedo_tex, int albedo_h, int albedo_w, const float* roughness_tex, int roughness_h,
+                    int roughness_w, const float* normal_tex, int normal_h, int normal_w, int wrap, int flip_v,
+                    float* albedo, float* roughness, float* normals, float* lod, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -89,6 +89,10 @@ SIGNATURES = {
     "pn_bvh_tree": ("i", "lpppppp" + "p"),
     "pn_trace_mesh_bvh": ("i", "lpplpppi" + "pppp" + "p"),
     "pn_shadow_ratio_bvh": ("i", "liipllppppflpppp" + "p"),
+    "pn_tex_floats": ("l", "ii"),
+    "pn_tex_ingest": ("i", "iiiipppp"),
+    "pn_tex_pyramid": ("i", "iipp"),
+    "pn_texture_hits": ("i", "l" + "p" * 7 + "lplp" + "lpp" + "pii" * 3 + "ii" + "pppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

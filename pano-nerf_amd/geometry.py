@@ -11,10 +11,12 @@ fallback.  The only host synchronisation is the copy of the two mesh totals that
     extract_mesh(model, bounds, resolution, level)  Mesh(vertices, faces, normals, colors)
     write_ply(path, vertices, faces, normals, colors)  binary little-endian PLY
     read_ply(path)                              Mesh of host numpy arrays from such a file (binary or ASCII)
+    read_obj(path)                              ObjMesh of host numpy arrays from a Wavefront OBJ (+ MTL) file
 
 The mesh contract (edge ids, vertex and face order, winding) is stated in include/panonerf_hip.h.
 """
 import collections
+import os
 
 import numpy as np
 import torch
@@ -23,6 +25,7 @@ from . import _lib
 from .render import _Eval, _mlp_forward, _planes_of, _tfmt_of
 
 Mesh = collections.namedtuple("Mesh", ["vertices", "faces", "normals", "colors"])
+ObjMesh = collections.namedtuple("ObjMesh", ["vertices", "faces", "uv", "face_uv", "normals", "face_material", "materials"])
 
 FIELD_OUTPUTS = ("sigma", "albedo", "rgb", "normal", "grad")
 
@@ -418,3 +421,145 @@ def read_ply(path):
         c = (np.stack([vrec["red"], vrec["green"], vrec["blue"]], 1).astype(np.float32) / np.float32(255.0)) if has_c else None
         f = np.ascontiguousarray(frec["i"], dtype=np.int32)
     return Mesh(v.reshape(nv, 3), f.reshape(nf, 3), n, c)
+
+
+_MTL_MAPS = {"map_kd": "map_Kd", "map_pr": "map_Pr", "norm": "norm", "map_bump": "norm", "bump": "norm"}
+_MTL_OPTIONS = {"-blendu": 1, "-blendv": 1, "-boost": 1, "-bm": 1, "-cc": 1, "-clamp": 1, "-imfchan": 1, "-texres": 1,
+                "-type": 1, "-mm": 2, "-o": 3, "-s": 3, "-t": 3}
+
+
+def _map_name(words):
+    """the file name of an MTL map statement: options (and their arguments) before it are skipped"""
+    i = 0
+    while i < len(words) and words[i] in _MTL_OPTIONS:
+        i += 1 + _MTL_OPTIONS[words[i]]
+    if i >= len(words):
+        raise ValueError(f"no file name in map statement {' '.join(words)!r}")
+    return " ".join(words[i:])
+
+
+def read_mtl(path):
+    """Ordered dict name -> dict(Kd=(r, g, b) | None, Pr=float | None, map_Kd, map_Pr, norm = path | None) of an MTL
+    file; norm is what `norm`, `map_Bump` or `bump` names.  Map paths are made relative to the MTL file's directory.
+    Other keys are ignored."""
+    base = os.path.dirname(os.path.abspath(path))
+    mats, cur = collections.OrderedDict(), None
+    with open(path, "r", errors="replace") as fh:
+        for ln, line in enumerate(fh, 1):
+            w = line.split("#", 1)[0].split()
+            if not w:
+                continue
+            key = w[0]
+            if key == "newmtl":
+                if len(w) < 2:
+                    raise ValueError(f"{path}:{ln}: newmtl without a name")
+                cur = dict(Kd=None, Pr=None, map_Kd=None, map_Pr=None, norm=None)
+                mats[" ".join(w[1:])] = cur
+                continue
+            if cur is None:
+                continue
+            try:
+                if key == "Kd":
+                    k = [float(x) for x in w[1:4]]
+                    cur["Kd"] = tuple(k * 3 if len(k) == 1 else k)
+                    if len(cur["Kd"]) != 3:
+                        raise ValueError("Kd takes 1 or 3 values")
+                elif key == "Pr":
+                    cur["Pr"] = float(w[1])
+                elif key.lower() in _MTL_MAPS:
+                    cur[_MTL_MAPS[key.lower()]] = os.path.join(base, _map_name(w[1:]).replace("\\", "/"))
+            except (ValueError, IndexError) as e:
+                raise ValueError(f"{path}:{ln}: unreadable line {line.strip()!r} ({e})") from None
+    return mats
+
+
+def read_obj(path):
+    """ObjMesh(vertices [V, 3] fp32, faces [F, 3] int32, uv [T, 2] fp32 | None, face_uv [F, 3] int32 | None, normals [V, 3]
+    fp32, face_material [F] int32, materials) of a Wavefront OBJ file, as HOST numpy arrays.
+
+    Read: v, vt, vn, f (corners `v`, `v/vt`, `v//vn`, `v/vt/vn`; 1-based or negative = relative to the end so far; polygons
+    are fan-triangulated around their first corner), mtllib and usemtl.  Everything else (o, g, s, l, ...) is ignored.
+    uv / face_uv are None unless every corner has a vt.  normals: the file's vn when every corner's vn index equals its
+    v index (and there are as many vn as v); otherwise area-weighted vertex normals (the sum of e1 x e2 over a vertex's
+    faces, normalised; 0 for a vertex no face uses).  materials: the ordered dict of read_mtl over every mtllib, plus an
+    entry (all None) for a usemtl name no library defines; face_material indexes it, -1 for faces before any usemtl.  A
+    mtllib file that does not exist raises FileNotFoundError naming it."""
+    base = os.path.dirname(os.path.abspath(path))
+    v, vt, vn = [], [], []
+    fv, ft, fn, fm = [], [], [], []
+    materials, cur = collections.OrderedDict(), -1
+
+    def index(tok, n, what, ln):
+        i = int(tok)
+        j = i - 1 if i > 0 else n + i
+        if i == 0 or not 0 <= j < n:
+            raise ValueError(f"{path}:{ln}: {what} index {i} outside the {n} read so far")
+        return j
+
+    with open(path, "r", errors="replace") as fh:
+        for ln, line in enumerate(fh, 1):
+            w = line.split("#", 1)[0].split()
+            if not w:
+                continue
+            key = w[0]
+            try:
+                if key == "v":
+                    v.append([float(x) for x in w[1:4]])
+                    if len(v[-1]) != 3:
+                        raise ValueError("v takes 3 coordinates")
+                elif key == "vt":
+                    vt.append([float(x) for x in w[1:3]] if len(w) > 2 else [float(w[1]), 0.0])
+                elif key == "vn":
+                    vn.append([float(x) for x in w[1:4]])
+                    if len(vn[-1]) != 3:
+                        raise ValueError("vn takes 3 coordinates")
+                elif key == "f":
+                    if len(w) < 4:
+                        raise ValueError("a face needs 3 corners")
+                    cv, ct, cn = [], [], []
+                    for tok in w[1:]:
+                        parts = tok.split("/")
+                        if len(parts) > 3:
+                            raise ValueError(f"corner {tok!r}")
+                        cv.append(index(parts[0], len(v), "v", ln))
+                        ct.append(index(parts[1], len(vt), "vt", ln) if len(parts) > 1 and parts[1] else -1)
+                        cn.append(index(parts[2], len(vn), "vn", ln) if len(parts) > 2 and parts[2] else -1)
+                    for k in range(1, len(cv) - 1):
+                        fv.append([cv[0], cv[k], cv[k + 1]])
+                        ft.append([ct[0], ct[k], ct[k + 1]])
+                        fn.append([cn[0], cn[k], cn[k + 1]])
+                        fm.append(cur)
+                elif key == "mtllib":
+                    for name in w[1:]:
+                        lib = os.path.join(base, name.replace("\\", "/"))
+                        if not os.path.isfile(lib):
+                            raise FileNotFoundError(f"{path}:{ln}: mtllib {name!r} not found at {lib}")
+                        for k, m in read_mtl(lib).items():
+                            materials[k] = m
+                elif key == "usemtl":
+                    name = " ".join(w[1:])
+                    if name not in materials:
+                        materials[name] = dict(Kd=None, Pr=None, map_Kd=None, map_Pr=None, norm=None)
+                    cur = list(materials).index(name)
+            except ValueError as e:
+                if str(e).startswith(f"{path}:"):
+                    raise
+                raise ValueError(f"{path}:{ln}: unreadable line {line.strip()!r} ({e})") from None
+    verts = np.asarray(v, np.float32).reshape(-1, 3)
+    faces = np.asarray(fv, np.int32).reshape(-1, 3)
+    fuv = np.asarray(ft, np.int32).reshape(-1, 3)
+    fnn = np.asarray(fn, np.int32).reshape(-1, 3)
+    uv = face_uv = None
+    if len(vt) and faces.shape[0] and (fuv >= 0).all():
+        uv, face_uv = np.asarray(vt, np.float32).reshape(-1, 2), fuv
+    if len(vn) == len(v) and faces.shape[0] and np.array_equal(fnn, faces):
+        normals = np.asarray(vn, np.float32).reshape(-1, 3)
+    else:
+        p = verts.astype(np.float64)
+        g = np.cross(p[faces[:, 1]] - p[faces[:, 0]], p[faces[:, 2]] - p[faces[:, 0]])  # length = twice the area
+        acc = np.zeros_like(p)
+        for k in range(3):
+            np.add.at(acc, faces[:, k], g)
+        n = np.linalg.norm(acc, axis=1, keepdims=True)
+        normals = np.where(n > 0, acc / np.where(n > 0, n, 1.0), 0.0).astype(np.float32)
+    return ObjMesh(verts, faces, uv, face_uv, normals, np.asarray(fm, np.int32), materials)

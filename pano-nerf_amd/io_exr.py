@@ -1,4 +1,5 @@
-"""OpenEXR reader / writer and 8-bit PNG writer for datasets and validation dumps, with no third-party codec.
+"""OpenEXR reader / writer and 8-bit PNG writer / reader for datasets, textures and validation dumps, with no third-party
+codec.
 
 `utils/io_exr.py:30-47` writes an RGB float32 scanline OpenEXR through the OpenEXR python binding and
 `utils/io_exr.py:6-27` reads one back; the binding is not available here, so this module emits / parses the
@@ -198,3 +199,77 @@ def write_png(filename, img):
     with open(filename, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) +
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+_PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}  # colour type -> samples per pixel
+_PNG_COLOUR = {0: "greyscale", 2: "RGB", 3: "palette", 4: "grey + alpha", 6: "RGBA"}
+
+
+def read_png(path):
+    """8-bit, non-interlaced PNG (greyscale, grey + alpha, RGB or RGBA; all five filter types; any number of IDAT chunks)
+    -> uint8 [H, W] for greyscale, [H, W, C] otherwise (C = 2, 3, 4), with zlib and numpy only.  16-bit (or 1 / 2 / 4-bit),
+    palette and interlaced files raise NotImplementedError naming what was found; a file that is no PNG, or whose data ends
+    early, raises ValueError.  Ancillary chunks (gAMA, sRGB, tEXt, ...) are skipped and CRCs are not checked."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    pos, idat, hdr = 8, [], None
+    while pos + 8 <= len(data):
+        (n,), tag = struct.unpack_from(">I", data, pos), data[pos + 4:pos + 8]
+        body = data[pos + 8:pos + 8 + n]
+        pos += 12 + n
+        if tag == b"IHDR":
+            hdr = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            break
+    if hdr is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    w, h, depth, ctype, _, _, interlace = hdr
+    if ctype == 3:
+        raise NotImplementedError(f"{path}: palette PNG files are not read here (8-bit greyscale, grey + alpha, RGB, RGBA only)")
+    if ctype not in _PNG_CHANNELS:
+        raise ValueError(f"{path}: unknown PNG colour type {ctype}")
+    if depth != 8:
+        raise NotImplementedError(f"{path}: {depth}-bit {_PNG_COLOUR[ctype]} PNG files are not read here (8-bit only)")
+    if interlace:
+        raise NotImplementedError(f"{path}: interlaced (Adam7) PNG files are not read here")
+    c = _PNG_CHANNELS[ctype]
+    stride = w * c
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
+    if raw.size < h * (stride + 1):
+        raise ValueError(f"{path}: the image data holds {raw.size} bytes, {h * (stride + 1)} expected")
+    rows = raw[:h * (stride + 1)].reshape(h, stride + 1)
+    out = np.zeros((h, stride), np.uint8)
+    prev = np.zeros(stride, np.uint8)
+    for y in range(h):
+        ft, line = int(rows[y, 0]), rows[y, 1:]
+        if ft == 0:
+            cur = line.copy()
+        elif ft == 1:  # Sub: each channel is a running sum along the row (uint8 arithmetic wraps mod 256)
+            cur = np.cumsum(line.reshape(w, c), axis=0, dtype=np.uint8).reshape(stride)
+        elif ft == 2:  # Up
+            cur = line + prev
+        elif ft in (3, 4):  # Average, Paeth: the left neighbour is the value just decoded
+            cur = np.empty(stride, np.uint8)
+            x_, up = line.astype(np.int32), prev.astype(np.int32)
+            dec = [0] * stride
+            for i in range(stride):
+                a = dec[i - c] if i >= c else 0
+                b = int(up[i])
+                if ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    cc = int(up[i - c]) if i >= c else 0
+                    p = a + b - cc
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - cc)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else cc)
+                dec[i] = (int(x_[i]) + pred) & 255
+            cur[:] = dec
+        else:
+            raise ValueError(f"{path}: unknown filter type {ft} on row {y}")
+        out[y] = cur
+        prev = cur
+    return out.reshape(h, w) if c == 1 else out.reshape(h, w, c)

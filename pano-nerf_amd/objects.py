@@ -9,8 +9,13 @@ host fallback.  No gradients flow through any of it.
     MeshBVH.build(vertices, faces)                                     a linear BVH over the triangles, built on the device
     shade(probes, albedo, normals, viewdirs, roughness, weights)       the reference's surface_rendering under light probes
     shadow_ratio(points, normals, probe, vertices, faces, bias)        share of a point's irradiance the mesh leaves
-    VirtualObject(vertices, faces, normals, albedo, roughness)         a mesh with its material; from_mesh, transformed
+    Texture(image, srgb) / Texture.from_file(path, srgb)               a mip-mapped texture on the device (PNG or EXR)
+    VirtualObject(vertices, faces, normals, albedo, roughness, ...)    a mesh with its material; from_mesh, from_obj,
+                                                                       transformed; uv, face_uv and albedo / roughness /
+                                                                       normal maps
     hit_attributes(obj, origins, directions, t, face, bary, ...)       mask, points, normals, albedo, viewdirs, weights
+                                                                       (+ roughness with a roughness map)
+    sample_textures(obj, mask, face, bary, directions, t, normals)     the texture sampler alone, with the levels it used
     insert_object(model, camera, c2w, obj, ...)                        dict of [1, C, H, W]: the composited frame
     insert_path(model, camera, poses, obj, ...)                        frames of a pose stack (or PNG files)
 
@@ -27,6 +32,20 @@ does not depend on the tree and equals brute force wherever no accepted hit lies
 header's "candidate rule"): tests/test_bvh_cpu.py shows that no such hit exists on its scenes.  Measured on one MI355X
 (profiles/objects_bvh.txt): with the build inside the call the BVH is slower than brute force at 80 faces and below and
 faster from 320 on - 63 to 81 times at 81 920 faces, where the two tracers differed on no ray of either test frame.
+
+Texture maps (pn_textures.hip; include/panonerf_hip.h states every formula).  A Texture is one fp32 buffer of float4
+texels holding all mip levels (level l is max(1, H >> l) x max(1, W >> l), a 2 x 2 box filter of the level below, clamped
+at odd edges); uint8 images are decoded through a 256-entry table (i / 255, or the exact sRGB EOTF with srgb=True).  An
+object with uv [T, 2] (and face_uv [F, 3] when the UVs are indexed per corner, as in OBJ files; without it they are per
+vertex) takes an albedo_map, a roughness_map (channel 0; needs roughness not None, i.e. the microfacet branch) and a
+tangent-space normal_map.  hit_attributes then runs the sampler after the untextured kernel: UV = the barycentric blend;
+level of detail = the ray-cone footprint lambda = 0.5 log2(W H A_uv / A_w) + log2(2 radii t) - log2(|n_g . d| / |d|),
+clamped to the pyramid (radii=None: level 0), trilinear between the two levels, bilinear within one; wrap="repeat" or
+"clamp"; flip_v=True puts V = 0 at the image's last row (the OBJ convention), flip_v=False at its first.  The normal map
+perturbs the shading normal N in the frame (T', B', N) that Gram-Schmidt makes of the UV gradients, and keeps N where
+that frame does not exist or the result would face away from the eye.  insert_object / insert_path hand the frame rays'
+radii on, so a distant or grazing surface reads a coarser level.  An object without maps calls exactly what it called
+before.  Out of scope: anisotropic filtering, several materials per object, emissive / metallic maps, texture compression.
 """
 import os
 
@@ -260,15 +279,110 @@ def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3, accel=None)
     return out
 
 
+def _decode_table(srgb):
+    """256 fp32 values: i / 255 or the sRGB EOTF of it, built in fp64 and rounded once."""
+    c = np.arange(256, dtype=np.float64) / 255.0
+    if srgb:
+        c = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+    return c.astype(np.float32)
+
+
+class Texture:
+    """A mip-mapped texture on the device: `data` [sum_l h_l w_l, 4] fp32 (every level, level 0 first; unused channels 0,
+    alpha 1), H, W, L = 1 + floor(log2(max(H, W))) and C, the channels of the image it was made from.
+
+    image: uint8 or floating [H, W] / [H, W, C] (C = 1, 3 or 4; 1 <= H, W <= 16384), a host array or a device tensor.
+    srgb=True decodes uint8 colour channels with the sRGB EOTF (albedo images); False is i / 255 (roughness and normal
+    maps).  A floating image is linear: srgb=True raises.  Built by pn_tex_ingest and pn_tex_pyramid on the current
+    stream."""
+
+    def __init__(self, image, srgb=False, device=None):
+        if isinstance(image, torch.Tensor):
+            dev = image.device
+            img = image.detach()
+        else:
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+            a = np.asarray(image)
+            if a.dtype != np.uint8:
+                if a.dtype.kind != "f":
+                    raise ValueError(f"a texture image must be uint8 or floating; got {a.dtype}")
+                a = a.astype(np.float32)
+            img = torch.from_numpy(np.ascontiguousarray(a))
+        if dev.type != "cuda":
+            raise RuntimeError(f"pano_nerf_amd.objects runs on a HIP device only (the texture is on {dev}); there is no CPU "
+                               "fallback")
+        if img.dim() == 2:
+            img = img[:, :, None]
+        if img.dim() != 3 or img.shape[2] not in (1, 3, 4) or not (1 <= img.shape[0] <= 16384 and 1 <= img.shape[1] <= 16384):
+            raise ValueError(f"a texture image must be [H, W] or [H, W, C] with C in (1, 3, 4) and 1 <= H, W <= 16384; got "
+                             f"{tuple(img.shape)}")
+        is_u8 = img.dtype == torch.uint8
+        if not is_u8 and not img.dtype.is_floating_point:
+            raise ValueError(f"a texture image must be uint8 or floating; got {img.dtype}")
+        if srgb and not is_u8:
+            raise ValueError("srgb=True decodes uint8 images; a floating image is taken as linear")
+        img = (img if is_u8 else img.to(torch.float32)).to(dev).contiguous()
+        self.H, self.W, self.C = (int(x) for x in img.shape)
+        self.L = 1 + int(max(self.H, self.W)).bit_length() - 1
+        self.srgb, self.device = bool(srgb), dev
+        with torch.no_grad(), torch.cuda.device(dev):
+            n = _lib.load().pn_tex_floats(self.H, self.W)
+            if n < 0:
+                _lib.check(int(n), "pn_tex_floats")
+            self.data = torch.empty(n // 4, 4, dtype=torch.float32, device=dev)
+            table = torch.from_numpy(_decode_table(srgb)).to(dev) if is_u8 else None
+            _lib.call("pn_tex_ingest", self.H, self.W, self.C, int(is_u8), img.data_ptr(), _lib.ptr(table),
+                      self.data.data_ptr(), _stream(dev))
+            _lib.call("pn_tex_pyramid", self.H, self.W, self.data.data_ptr(), _stream(dev))
+            for x in (img, table):  # the launches above read them on this stream
+                if x is not None:
+                    x.record_stream(torch.cuda.current_stream(dev))
+
+    @classmethod
+    def from_file(cls, path, srgb=False, device=None):
+        """A .png (io_exr.read_png; a grey + alpha file keeps its grey channel) or .exr (io_exr.read_exr: RGB, always
+        linear, whatever srgb says) file."""
+        from . import io_exr
+        ext = os.path.splitext(path)[1].lower()
+        if ext == ".png":
+            img = io_exr.read_png(path)
+            if img.ndim == 3 and img.shape[2] == 2:
+                img = img[:, :, 0]
+            return cls(img, srgb=srgb, device=device)
+        if ext == ".exr":
+            return cls(io_exr.read_exr(path), srgb=False, device=device)
+        raise ValueError(f"{path}: textures are read from .png and .exr files; got {ext!r}")
+
+    def level_shape(self, l):
+        """(texel offset, h_l, w_l) of level l"""
+        if not 0 <= l < self.L:
+            raise ValueError(f"level {l} outside the {self.L} levels of a {self.H} x {self.W} texture")
+        off = sum(max(1, self.H >> i) * max(1, self.W >> i) for i in range(l))
+        return off, max(1, self.H >> l), max(1, self.W >> l)
+
+    def level(self, l):
+        """A view [h_l, w_l, 4] of level l."""
+        off, h, w = self.level_shape(l)
+        return self.data[off:off + h * w].view(h, w, 4)
+
+
+_WRAP = {"repeat": 0, "clamp": 1}
+
+
 class VirtualObject:
     """A triangle mesh with its material, on the device.  vertices [V, 3], faces [F, 3] int32 (device tensors or arrays
     on the host, which are copied to `device`); normals: per vertex (interpolated with the barycentrics and renormalised)
     or None (the geometric normalize(e1 x e2)); albedo: one colour or [V, 3] (e.g. Mesh.colors); roughness: None
-    (Lambertian) or a float (microfacet).  The shading normal is flipped towards the eye.  Face indices are checked here."""
+    (Lambertian) or a float (microfacet).  The shading normal is flipped towards the eye.  Face indices are checked here.
+    Texture maps (the module docstring has the conventions): uv [T, 2]; face_uv [F, 3] int32 indexes it per corner (None:
+    T = V and faces index it); albedo_map replaces the albedo, roughness_map (channel 0; needs roughness not None, which
+    selects the microfacet branch) the roughness per hit, normal_map perturbs the shading normal; wrap "repeat" or "clamp";
+    flip_v=True (OBJ's convention) puts V = 0 at the image's last row.  A map without uv raises; face_uv is checked here."""
 
-    def __init__(self, vertices, faces, normals=None, albedo=(0.8, 0.8, 0.8), roughness=None, device=None):
+    def __init__(self, vertices, faces, normals=None, albedo=(0.8, 0.8, 0.8), roughness=None, device=None, uv=None,
+                 face_uv=None, albedo_map=None, roughness_map=None, normal_map=None, wrap="repeat", flip_v=True):
         dev = None
-        for t in (vertices, faces, normals, albedo):
+        for t in (vertices, faces, normals, albedo, uv, face_uv):
             if isinstance(t, torch.Tensor):
                 dev = t.device
                 break
@@ -300,6 +414,85 @@ class VirtualObject:
         self.roughness = None if roughness is None else float(roughness)
         self.device = dev
         self._bvh, self._bvh_stamp = None, None
+        self.uv, self.face_uv = None, None
+        if uv is not None:
+            self.uv = to(uv, torch.float32).contiguous()
+            if self.uv.dim() != 2 or self.uv.shape[1] != 2:
+                raise ValueError(f"uv must be [T, 2]; got {tuple(self.uv.shape)}")
+            T = int(self.uv.shape[0])
+            if face_uv is None:
+                if T != V:
+                    raise ValueError(f"uv without face_uv is per vertex: it must be [{V}, 2]; got {tuple(self.uv.shape)}")
+            else:
+                fu = to(face_uv, torch.int64)
+                if tuple(fu.shape) != tuple(self.faces.shape):
+                    raise ValueError(f"face_uv must be [F, 3] like the faces; got {tuple(fu.shape)}")
+                if fu.numel() and (int(fu.min()) < 0 or int(fu.max()) >= T):
+                    raise ValueError(f"face_uv index outside the {T} uv rows")
+                self.face_uv = fu.to(torch.int32).contiguous()
+        elif face_uv is not None:
+            raise ValueError("face_uv needs uv")
+        if wrap not in _WRAP:
+            raise ValueError(f'wrap must be "repeat" or "clamp"; got {wrap!r}')
+        self.wrap, self.flip_v = wrap, bool(flip_v)
+        self.albedo_map, self.roughness_map, self.normal_map = albedo_map, roughness_map, normal_map
+        for name, tex, need in (("albedo_map", albedo_map, 3), ("roughness_map", roughness_map, 1),
+                                ("normal_map", normal_map, 3)):
+            if tex is None:
+                continue
+            if not isinstance(tex, Texture):
+                raise ValueError(f"{name} must be a Texture; got {type(tex).__name__}")
+            if self.uv is None:
+                raise ValueError(f"{name} needs uv")
+            if tex.device != dev:
+                raise RuntimeError(f"{name} is on {tex.device}, the object on {dev}")
+            if tex.C < need:
+                raise ValueError(f"{name} needs {need} channels; the texture has {tex.C}")
+        if roughness_map is not None and self.roughness is None:
+            raise ValueError("roughness_map needs roughness not None: a float selects the microfacet branch, in which the "
+                             "map gives the per-hit values")
+
+    @property
+    def textured(self):
+        return self.albedo_map is not None or self.roughness_map is not None or self.normal_map is not None
+
+    def _texture_kw(self):
+        return dict(uv=self.uv, face_uv=self.face_uv, albedo_map=self.albedo_map, roughness_map=self.roughness_map,
+                    normal_map=self.normal_map, wrap=self.wrap, flip_v=self.flip_v)
+
+    @classmethod
+    def from_obj(cls, path, material=None, device=None):
+        """The object of a Wavefront OBJ file (geometry.read_obj): the faces of one material, with its Kd as the albedo
+        (0.8 grey without one), its Pr as the roughness (with a map_Pr but no Pr: 1.0, so the map gives the values as
+        they are), and its maps - map_Kd (decoded as sRGB when it is a PNG), map_Pr, and norm / map_Bump / bump as the
+        normal map - loaded relative to the MTL file.  material=None takes the only material (or all faces when the file
+        names none); with several it raises, naming them.  UVs keep OBJ's convention (flip_v=True, wrap="repeat")."""
+        from .geometry import read_obj
+        m = read_obj(path)
+        names = list(m.materials)
+        used = sorted(set(int(i) for i in m.face_material))
+        if material is None:
+            if len(used) > 1:
+                raise ValueError(f"{path} uses {len(used)} materials "
+                                 f"({', '.join(repr(names[i]) if i >= 0 else '<none>' for i in used)}): pass material=")
+            pick = used[0] if used else -1
+        else:
+            if material not in names:
+                raise ValueError(f"{path} has no material {material!r}; it has {names}")
+            pick = names.index(material)
+        keep = m.face_material == pick
+        if not keep.any():
+            raise ValueError(f"{path}: no face uses material {material!r}")
+        mat = m.materials[names[pick]] if pick >= 0 else dict(Kd=None, Pr=None, map_Kd=None, map_Pr=None, norm=None)
+        rough = mat["Pr"] if mat["Pr"] is not None else (1.0 if mat["map_Pr"] else None)
+        tex = lambda p, srgb: None if p is None else Texture.from_file(p, srgb=srgb, device=device)
+        has_uv = m.uv is not None
+        for key in ("map_Kd", "map_Pr", "norm"):
+            if mat[key] and not has_uv:
+                raise ValueError(f"{path}: material {names[pick]!r} has {key} but the faces carry no vt")
+        return cls(m.vertices, m.faces[keep], m.normals, mat["Kd"] or (0.8, 0.8, 0.8), rough, device,
+                   uv=m.uv, face_uv=m.face_uv[keep] if has_uv else None, albedo_map=tex(mat["map_Kd"], True),
+                   roughness_map=tex(mat["map_Pr"], False), normal_map=tex(mat["norm"], False))
 
     @classmethod
     def from_mesh(cls, mesh, albedo=None, roughness=None, device=None):
@@ -309,7 +502,8 @@ class VirtualObject:
         return cls(mesh.vertices, mesh.faces, mesh.normals, albedo, roughness, device)
 
     def transformed(self, matrix):
-        """The object moved by a 4x4 matrix (points: M x; normals: the inverse transpose of its 3x3 part, renormalised)."""
+        """The object moved by a 4x4 matrix (points: M x; normals: the inverse transpose of its 3x3 part, renormalised).
+        UVs and texture maps come along (the Texture objects are shared, not copied)."""
         m = np.asarray(matrix, dtype=np.float64)
         if m.shape != (4, 4) or not np.isfinite(m).all():
             raise ValueError(f"matrix must be a finite 4x4 matrix; got shape {m.shape}")
@@ -320,7 +514,7 @@ class VirtualObject:
             it = torch.from_numpy(np.linalg.inv(m[:3, :3]).astype(np.float32)).to(self.device)  # (M^-T n)^T = n^T M^-1
             n = torch.nn.functional.normalize(self.normals @ it, dim=1)
         return VirtualObject(v, self.faces, n, self.vertex_albedo if self.vertex_albedo is not None else self.albedo,
-                             self.roughness)
+                             self.roughness, **self._texture_kw())
 
     def bvh(self):
         """The MeshBVH of this object, built on first use and kept for as long as vertices and faces are the tensors it
@@ -347,17 +541,73 @@ def _positions(obj, probe_positions, dev):
     return probe_positions.detach().to(torch.float32).contiguous()
 
 
-def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, probe_positions=None):
+def _texture_hits(obj, R, mask, face, bary, d, t, normals_in, radii, albedo, roughness, normals, lod, dev):
+    """pn_texture_hits on prepared (fp32 / int32 / uint8, contiguous) tensors; outputs of absent maps are not touched"""
+    if not R:
+        return
+    tex = []
+    for m in (obj.albedo_map, obj.roughness_map, obj.normal_map):
+        tex += [None, 0, 0] if m is None else [m.data.data_ptr(), m.H, m.W]
+    _lib.call("pn_texture_hits", R, mask.data_ptr(), face.data_ptr(), bary.data_ptr(), d.data_ptr(), t.data_ptr(),
+              normals_in.data_ptr(), _lib.ptr(radii), int(obj.vertices.shape[0]), obj.vertices.data_ptr(),
+              int(obj.faces.shape[0]), obj.faces.data_ptr(), int(obj.uv.shape[0]), obj.uv.data_ptr(),
+              _lib.ptr(obj.face_uv), *tex, _WRAP[obj.wrap], int(obj.flip_v), _lib.ptr(albedo), _lib.ptr(roughness),
+              _lib.ptr(normals), _lib.ptr(lod), _stream(dev))
+
+
+def sample_textures(obj, mask, face, bary, directions, t, normals, radii=None):
+    """The texture sampler on its own, at hits given by hand: mask [R] bool, face [R] int32, bary [R, 2], directions
+    [R, 3], t [R], normals [R, 3] (the shading normals, facing the eye), radii [R] / [R, 1] or None.  Returns a dict with
+    albedo [R, 3], roughness [R, 1] and normals [R, 3] - each only when the object has that map - and lod [R, 3], the level
+    of detail used per map (albedo, roughness, normal; 0 for an absent one).  Rows outside the mask are 0.
+    hit_attributes runs exactly this after the untextured attributes."""
+    if not isinstance(obj, VirtualObject) or not obj.textured:
+        raise ValueError("sample_textures needs a VirtualObject with at least one texture map")
+    dev = _cuda(("mask", mask), ("face", face), ("bary", bary), ("directions", directions), ("t", t), ("normals", normals),
+                ("radii", radii), ("vertices", obj.vertices))
+    d = _rows3(directions, "directions")
+    R = int(d.shape[0])
+    n = _rows3(normals, "normals", R)
+    if mask.numel() != R or t.numel() != R or face.numel() != R or tuple(bary.shape) != (R, 2):
+        raise ValueError(f"mask, t, face [R] and bary [R, 2] must match the {R} rows")
+    rad = None
+    if radii is not None:
+        if radii.numel() != R or radii.dim() > 2:
+            raise ValueError(f"radii must be [R] or [R, 1] with R = {R}; got {tuple(radii.shape)}")
+        rad = radii.detach().to(torch.float32).reshape(R).contiguous()
+    m8 = mask.detach().reshape(R).to(torch.uint8).contiguous()
+    ff = face.detach().to(torch.int32).reshape(R).contiguous()
+    bb = bary.detach().to(torch.float32).contiguous()
+    tt = t.detach().to(torch.float32).reshape(R).contiguous()
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = dict(lod=e(R, 3))
+        if obj.albedo_map is not None:
+            out["albedo"] = e(R, 3)
+        if obj.roughness_map is not None:
+            out["roughness"] = e(R, 1)
+        if obj.normal_map is not None:
+            out["normals"] = e(R, 3)
+        _texture_hits(obj, R, m8, ff, bb, d, tt, n, rad, out.get("albedo"), out.get("roughness"), out.get("normals"),
+                      out["lod"], dev)
+    return out
+
+
+def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, probe_positions=None, radii=None):
     """What shade needs at the hits trace_mesh found, as a dict of per-ray tensors: mask [R] bool (hit, and not
     t >= scene_dep where scene_dep [R] is given: a NaN depth counts as behind), points = o + t d, normals (interpolated
     or geometric, flipped towards the eye), albedo, viewdirs = d / |d| [R, 3] and weights [R, K] (normalised inverse
     distances of the point to probe_positions [K, 3]; a point within 1e-6 of a position takes that probe alone); rows
     outside the mask are 0.  With scene_dep also scene_points [R, 3] = o + scene_dep d outside the mask and NaN inside:
-    the points insert_object hands to shadow_ratio (a NaN point's ratio is 1)."""
+    the points insert_object hands to shadow_ratio (a NaN point's ratio is 1).
+    An object with texture maps: the same call, then the sampler (pn_texture_hits) on its outputs - an albedo_map replaces
+    the albedo rows, a normal_map the normals rows, a roughness_map adds roughness [R, 1].  radii ([R] or [R, 1], the
+    renderer's per-ray cone radii: the footprint at the hit is 2 radii t wide) picks the mip level; None samples level 0.
+    An object without maps ignores radii."""
     if not isinstance(obj, VirtualObject):
         raise ValueError(f"obj must be a VirtualObject; got {type(obj).__name__}")
     dev = _cuda(("origins", origins), ("directions", directions), ("t", t), ("face", face), ("bary", bary),
-                ("scene_dep", scene_dep), ("vertices", obj.vertices))
+                ("scene_dep", scene_dep), ("vertices", obj.vertices), ("radii", radii))
     o = _rows3(origins, "origins")
     R = int(o.shape[0])
     d = _rows3(directions, "directions", R)
@@ -371,6 +621,11 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
         if scene_dep.numel() != R:
             raise ValueError(f"scene_dep must hold {R} values; got {tuple(scene_dep.shape)}")
         dep = scene_dep.detach().to(torch.float32).reshape(R).contiguous()
+    rad = None
+    if radii is not None:
+        if radii.numel() != R or radii.dim() > 2:
+            raise ValueError(f"radii must be [R] or [R, 1] with R = {R}; got {tuple(radii.shape)}")
+        rad = radii.detach().to(torch.float32).reshape(R).contiguous()
     pos = None if probe_positions is None else _positions(obj, probe_positions, dev)
     K = 1 if pos is None else int(pos.shape[0])
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -386,6 +641,11 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
                       obj.faces.data_ptr(), _lib.ptr(obj.normals), _lib.ptr(obj.vertex_albedo), *col, K, _lib.ptr(pos),
                       mask.data_ptr(), out["points"].data_ptr(), out["normals"].data_ptr(), out["albedo"].data_ptr(),
                       out["viewdirs"].data_ptr(), _lib.ptr(weights), _lib.ptr(spoints), _stream(dev))
+        if obj.textured:
+            rough = e(R) if obj.roughness_map is not None else None
+            _texture_hits(obj, R, mask, ff, bb, d, tt, out["normals"], rad, out["albedo"], rough, out["normals"], None, dev)
+            if rough is not None:
+                out["roughness"] = rough.reshape(R, 1)
     out["mask"] = mask.bool()
     if weights is not None:
         out["weights"] = weights
@@ -394,14 +654,15 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
     return out
 
 
-def _frame_rays(camera, c2w, near, far, dev):
-    """(origins, directions) [H W, 3] of the rays render_view renders for this camera and pose."""
+def _frame_rays(camera, c2w, near, far, dev, radii=False):
+    """(origins, directions) [H W, 3] of the rays render_view renders for this camera and pose; radii=True adds their cone
+    radii [H W, 1]."""
     from . import views
     c2ws = views._c2w_stack(c2w, single=True)
     p, c = views._device_cams(camera, c2ws, dev)
     idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
     rays, _ = views._sample(camera, 1, p, c, idx, near, far, None, dev)
-    return rays.origins, rays.directions
+    return (rays.origins, rays.directions, rays.radii) if radii else (rays.origins, rays.directions)
 
 
 def _object_accel(obj, accel):
@@ -422,16 +683,20 @@ def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, nea
     rows = lambda x: x.permute(0, 2, 3, 1).reshape(R, -1)  # the [H W, C] buffer behind a render_view output
     s_rgb, s_dep, s_nor = rows(scene["fine_rgb"]), rows(scene["fine_dep"]), rows(scene["fine_nor"])
     with torch.no_grad(), torch.cuda.device(dev):
-        o, d = _frame_rays(camera, c2w, near, far, dev)
+        o, d, radii = _frame_rays(camera, c2w, near, far, dev, radii=True)
         t, face, bary = trace_mesh(o, d, obj.vertices, obj.faces, accel=accel)
         K = int(pos.shape[0])
-        at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None)
+        if obj.textured:
+            at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None, radii=radii)
+        else:
+            at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None)
         mask = at["mask"]
         object_rgb = torch.zeros(R, 3, dtype=torch.float32, device=dev)
         hit = torch.nonzero(mask).reshape(-1)  # the one host synchronisation: sizes the shading launch
         if hit.numel():
             g = lambda x: x.index_select(0, hit)
-            rgb_hit = shade(probes, g(at["albedo"]), g(at["normals"]), g(at["viewdirs"]), obj.roughness,
+            rough = g(at["roughness"]) if "roughness" in at else obj.roughness
+            rgb_hit = shade(probes, g(at["albedo"]), g(at["normals"]), g(at["viewdirs"]), rough,
                             g(at["weights"]) if K > 1 else None)[0]
             object_rgb.index_copy_(0, hit, rgb_hit)
         if shadow_probe is not None:
@@ -477,7 +742,8 @@ def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32,
         depth        mask ? t : scene_dep
 
     camera: views.perspective_camera(...) or views.pano_camera(h, w); the rays are the ones render_view renders.
-    probe_positions [K, 3] (K <= 8) defaults to the vertex centroid; with K > 1 each hit blends the probes by the
+    An object with texture maps gets the frame rays' radii in hit_attributes(radii=...) and, with a roughness_map,
+    shade(roughness=the per-hit rows).  probe_positions [K, 3] (K <= 8) defaults to the vertex centroid; with K > 1 each hit blends the probes by the
     normalised inverse distances to their positions.  It is exactly light_probes -> trace_mesh -> hit_attributes ->
     shade / shadow_ratio(hit_attributes' scene_points, scene_nor) -> the composite, all public.  accel (None, "bvh" or a
     MeshBVH of the object) goes to trace_mesh and shadow_ratio; "bvh" is obj.bvh(), built once and kept on the object."""
