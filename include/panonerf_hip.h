@@ -453,7 +453,7 @@ int pn_sh_volume_irradiance(int nx, int ny, int nz, float x0, float y0, float z0
                             const float* sh, int64_t M, const float* points, const float* normals, float* out,
                             void* stream);
 
-/* ---- novel views: pinhole rays and viewable frames (pn_views.hip) -----------------------------------------------
+/* ---- novel views: pinhole rays (pn_cameras.hip) and viewable frames (pn_views.hip) -------------------------------
  * Pinhole camera: pix2cam [3, 3] fp32 row-major maps pixel (x + 1/2, y + 1/2, 1) (x = column, y = row) to a camera-space
  * direction; the Blender form is ((x + 1/2 - W/2) / f, -(y + 1/2 - H/2) / f, -1): x right, y up, looking along -z
  * (datasets/base_datasets.py:216-265; Multicam passes its own pix2cam, :118-170).  Per ray, each product a 3-term fp32

@@ -5,7 +5,7 @@ cd "$(dirname "$0")"
 OUT=../libpanonerf_hip.so
 FLAGS="$PN_EXTRA --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 for f in pn_gemm pn_render pn_mlp pn_chain pn_metrics pn_geometry pn_lighting pn_views pn_cameras pn_data pn_objects pn_bvh pn_textures; do
-  if [ ! -f "$f.o" ] || [ "$f.hip" -nt "$f.o" ] || [ pn_common.h -nt "$f.o" ] || [ pn_tri.h -nt "$f.o" ] || [ pn_pano_ray.h -nt "$f.o" ] || [ ../../include/panonerf_hip.h -nt "$f.o" ]; then
+  if [ ! -f "$f.o" ] || [ "$f.hip" -nt "$f.o" ] || [ pn_common.h -nt "$f.o" ] || [ pn_tri.h -nt "$f.o" ] || [ pn_rays.h -nt "$f.o" ] || [ ../../include/panonerf_hip.h -nt "$f.o" ]; then
     /opt/rocm/bin/hipcc $FLAGS -c "$f.hip" -o "$f.o"
   fi
 done

@@ -21,9 +21,6 @@ constexpr int kTile = 256;                    // probe pixels staged per LDS til
 constexpr float kShrink = 1.f - 4.76837158203125e-07f;  // 1 - 2^-21
 constexpr float kGrow = 1.f + 4.76837158203125e-07f;    // 1 + 2^-21
 
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 

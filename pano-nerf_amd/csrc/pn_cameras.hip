@@ -1,24 +1,21 @@
-// pn_cameras.hip — camera models beyond the panorama and the pinhole (gfx950): cube-map, equidistant fisheye and
-// stereo-panorama (ODS) ray generation from (camera, pixel), and reprojection of images between the central cameras
-// (panorama, pinhole, cube map, fisheye).  Conventions are stated in include/panonerf_hip.h.
+// pn_cameras.hip — cameras (gfx950): ray generation from (camera, pixel) for every camera model (panorama, pinhole,
+// cube map, equidistant fisheye, stereo panorama (ODS)), the panorama pool generator, and reprojection of images between
+// the central cameras (panorama, pinhole, cube map, fisheye).  Conventions are stated in include/panonerf_hip.h.
 //
-// Rays: one thread per batch ray, as pn_sample_pinhole_rays; the stereo panorama takes its directions, radii and
-// noise variance from pano_ray (pn_pano_ray.h), the function behind pn_sample_pano_rays.  Reprojection: one thread per
-// (image, destination pixel), a gather: every subsample goes destination pixel -> direction -> rotated -> source pixel
-// once, its four bilinear taps are reused over the channels (four accumulators at a time), the mean over the valid
-// subsamples is taken in a fixed order, and consecutive lanes store consecutive pixels of a destination row.  No atomics.
-#include "pn_common.h"
-#include "pn_pano_ray.h"
+// Rays: one thread per batch ray regenerates it from the camera matrices, the cone radius included (the neighbour's
+// direction is recomputed in the thread), so no 56-byte-per-ray pool is stored or read; only the 12-byte
+// target colour is gathered.  One kernel template, k_sample_rays, instantiated per camera kind of pn_rays.h.
+// Reprojection: one thread per (image, destination pixel), a gather: every subsample goes destination pixel ->
+// direction -> rotated -> source pixel once, its four bilinear taps are reused over the channels (four accumulators at a
+// time), the mean over the valid subsamples is taken in a fixed order, and consecutive lanes store consecutive pixels of
+// a destination row.  No atomics.
+#include "pn_rays.h"
 #include <math.h>
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChan = 4;  // channels accumulated per pass over the subsamples
-
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
 struct CamParams {
     float v[PN_CAM_PARAMS];
@@ -29,127 +26,43 @@ struct Rot {
 
 constexpr float kPi = 3.14159265358979323846f;
 
-// ------------------------------------------------------------------------------------------------- pixel -> direction
-// camera-space direction of the continuous cube-strip position (px, py); face = the strip's face of py
-__device__ __forceinline__ void cube_dir(int S, float px, float py, float d[3]) {
-    int face = (int)floorf(py / (float)S);
-    face = face < 0 ? 0 : (face > 5 ? 5 : face);
-    const float s = 2.f * px / (float)S - 1.f;
-    const float t = 2.f * (py - (float)(face * S)) / (float)S - 1.f;
-    switch (face) {
-        case 0: d[0] = 1.f, d[1] = -t, d[2] = -s; break;
-        case 1: d[0] = -1.f, d[1] = -t, d[2] = s; break;
-        case 2: d[0] = s, d[1] = 1.f, d[2] = t; break;
-        case 3: d[0] = s, d[1] = -1.f, d[2] = -t; break;
-        case 4: d[0] = s, d[1] = -t, d[2] = 1.f; break;
-        default: d[0] = -s, d[1] = -t, d[2] = -1.f; break;
-    }
+// ---------------------------------------------------------------------------------------------------- ray generation
+// the pool of one panorama camera, row-major pixels
+__global__ __launch_bounds__(kThreads) void k_raygen_pano(int H, int W, PanoCam c, float near_, float far_, RayOut out) {
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= H * W) return;
+    store_ray(idx, pano_ray(H, W, c, idx / W, idx % W), near_, far_, out);
 }
 
-// equidistant fisheye: unit camera-space direction of (px, py) and its angle from the axis
-__device__ __forceinline__ float fisheye_dir(int H, int W, float f, float px, float py, float d[3]) {
-    const float u = px - 0.5f * (float)W, v = -(py - 0.5f * (float)H);
-    const float r = hypotf(u, v);
-    const float theta = r / f;
-    if (r > 0.f) {
-        float sn, cs;
-        sincosf(theta, &sn, &cs);
-        d[0] = sn * u / r;
-        d[1] = sn * v / r;
-        d[2] = -cs;
-    } else {
-        d[0] = 0.f, d[1] = 0.f, d[2] = -1.f;
-    }
-    return theta;
-}
-
-__device__ __forceinline__ void rotate(const float* m, int ld, const float c[3], float out[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = (m[ld * k] * c[0] + m[ld * k + 1] * c[1]) + m[ld * k + 2] * c[2];
-}
-
-__device__ __forceinline__ void normalize3(float d[3]) {
-    const float n = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = d[k] / n;
-}
-
-// world direction c2w[:3,:3] @ unit camera direction of pixel (i, j) of a cube or fisheye camera; returns the fisheye angle
-__device__ __forceinline__ float central_dir(int kind, int H, int W, const CamParams& p, const float* c2w, int i, int j,
-                                             float out[3]) {
-    float c[3], theta = 0.f;
-    if (kind == PN_CAM_CUBE) {
-        cube_dir(W, (float)j + 0.5f, (float)i + 0.5f, c);
-        normalize3(c);
-    } else {
-        theta = fisheye_dir(H, W, p.v[0], (float)j + 0.5f, (float)i + 0.5f, c);
-    }
-    rotate(c2w, 4, c, out);
-    return theta;
-}
-
-__global__ __launch_bounds__(kThreads) void k_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, CamParams p,
-                                                                 const int64_t* idx, const float* c2ws, float near_,
-                                                                 float far_, const float* rgb_pool, float* origins,
-                                                                 float* directions, float* viewdirs, float* radii,
-                                                                 float* lossmult, float* near_out, float* far_out,
-                                                                 float* noise_var, float* rgb_out) {
-    const int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+// batch ray b is pixel idx[b] % (H W) of camera idx[b] / (H W), with the target colour of that pool row
+template <class Cam, int kBlock>
+__global__ __launch_bounds__(kBlock) void k_sample_rays(int64_t B, int n_cam, Cam cam, const int64_t* idx, float near_,
+                                                        float far_, const float* rgb_pool, RayOut out) {
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (b >= B) return;
-    const int64_t hw = (int64_t)H * W;
-    int64_t r = idx[b];
-    r = (r >= 0 && r < hw * n_cam) ? r : 0;
-    const int cam = (int)(r / hw), pix = (int)(r % hw);
-    const int i = pix / W, j = pix % W;
-    const float* m = c2ws + 16 * (int64_t)cam;
-    if (kind == PN_CAM_STEREO_PANO) {
-        const PanoCam c{m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10], m[3], m[7], m[11]};
-        const PanoRay ray = pano_ray(H, W, c, i, j);
-        store_pano_ray(b, ray, c, near_, far_, origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var);
-        const float half = p.v[0];  // +ipd / 2 for the right eye, -ipd / 2 for the left
-        if (half != 0.f) {          // ipd = 0 keeps the panorama's origin bits
-            const float theta = -((float)j + 0.5f) / (float)W * 2.f * kPi;  // pano_ray's heading angle
-            const float off[3] = {half * -cosf(theta), 0.f, half * sinf(theta)};
-            float w[3];
-            rotate(m, 4, off, w);
-            origins[b * 3 + 0] = w[0] + m[3];
-            origins[b * 3 + 1] = w[1] + m[7];
-            origins[b * 3 + 2] = w[2] + m[11];
-        }
-    } else {
-        // cube rows count within the face: the last row of each face reuses the one before
-        const int rows = kind == PN_CAM_CUBE ? W : H;
-        const int top = kind == PN_CAM_CUBE ? (i / W) * W : 0;
-        const int y = i - top;
-        const int yy = y < rows - 1 ? y : rows - 2;
-        float d[3], a[3], n[3];
-        const float theta = central_dir(kind, H, W, p, m, i, j, d);
-        central_dir(kind, H, W, p, m, top + yy, j, a);
-        central_dir(kind, H, W, p, m, top + yy + 1, j, n);
-        const float dx = sqrtf((a[0] - n[0]) * (a[0] - n[0]) + (a[1] - n[1]) * (a[1] - n[1]) + (a[2] - n[2]) * (a[2] - n[2]));
-        const bool inside = kind == PN_CAM_CUBE || theta <= p.v[1];
-        if (!inside) {  // outside the image circle: the forward direction, no loss
-            const float fwd[3] = {0.f, 0.f, -1.f};
-            rotate(m, 4, fwd, d);
-        }
-        origins[b * 3 + 0] = m[3];
-        origins[b * 3 + 1] = m[7];
-        origins[b * 3 + 2] = m[11];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            directions[b * 3 + k] = d[k];
-            viewdirs[b * 3 + k] = d[k];
-        }
-        radii[b] = (float)((double)dx * 2.0 / sqrt(12.0));
-        lossmult[b] = inside ? 1.f : 0.f;
-        near_out[b] = near_;
-        far_out[b] = far_;
-        noise_var[b] = 0.f;
-    }
+    const RowId r = decode_row(idx[b], (int64_t)cam.H * cam.W, n_cam);
+    store_ray(b, cam.ray(r.cam, r.pix / cam.W, r.pix % cam.W), near_, far_, out);
     if (rgb_pool) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) rgb_out[b * 3 + k] = rgb_pool[r * 3 + k];
+        for (int k = 0; k < 3; ++k) out.rgb_out[b * 3 + k] = rgb_pool[r.row * 3 + k];
     }
+}
+
+// the pointer checks every ray entry point makes: the eight fields are mandatory, target colours come both or neither
+bool ray_ptrs_ok(const int64_t* idx, const float* c2ws, const float* rgb_pool, const RayOut& o) {
+    if (!idx || !c2ws || !o.origins || !o.directions || !o.viewdirs || !o.radii || !o.lossmult || !o.near_out || !o.far_out ||
+        !o.noise_var)
+        return false;
+    return (rgb_pool == nullptr) == (o.rgb_out == nullptr);
+}
+
+template <int kBlock, class Cam>
+int launch_sample_rays(int64_t B, int n_cam, const Cam& cam, const int64_t* idx, float near_, float far_,
+                       const float* rgb_pool, const RayOut& out, void* stream) {
+    hipLaunchKernelGGL((k_sample_rays<Cam, kBlock>), dim3(nblk(B, kBlock)), dim3(kBlock), 0, ST(stream), B, n_cam, cam, idx,
+                       near_, far_, rgb_pool, out);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------ reprojection
@@ -189,7 +102,7 @@ __device__ __forceinline__ bool src_pos(int kind, int H, int W, const CamParams&
     }
     if (kind == PN_CAM_PINHOLE) {
         float q[3];
-        rotate(p.v + 9, 3, d, q);
+        rotate3(p.v + 9, 3, d, q);
         if (!(q[2] > 0.f)) return false;
         px = q[0] / q[2];
         py = q[1] / q[2];
@@ -287,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void k_reproject(int N, int C, int sk, in
                     float d[3], e[3], qx, qy;
                     int face;
                     if (!dst_dir(dk, Hd, Wd, dp, px, py, d)) continue;
-                    rotate(rot.m, 3, d, e);
+                    rotate3(rot.m, 3, d, e);
                     if (!src_pos(sk, Hs, Ws, sp, e, qx, qy, face)) continue;
                     const Taps t = make_taps(sk, Hs, Ws, qx, qy, face);
                     ++valid;
@@ -327,6 +240,38 @@ bool min_size(int kind, int H, int W, bool& ok) {
 
 extern "C" {
 
+int pn_raygen_pano(int H, int W, const float* c, float near_, float far_, float* origins, float* directions,
+                   float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out, float* noise_var,
+                   void* stream) {
+    if (H <= 0 || W < 3) return PN_ERR_BAD_SHAPE;
+    if (!c || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out || !far_out || !noise_var)
+        return PN_ERR_NULL;
+    const RayOut out{origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var, nullptr};
+    hipLaunchKernelGGL(k_raygen_pano, dim3(nblk((int64_t)H * W, kThreads)), dim3(kThreads), 0, ST(stream), H, W, pano_cam(c), near_,
+                       far_, out);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_sample_pano_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* c2ws, float near_, float far_,
+                        const float* rgb_pool, float* origins, float* directions, float* viewdirs, float* radii,
+                        float* lossmult, float* near_out, float* far_out, float* noise_var, float* rgb_out, void* stream) {
+    if (B <= 0 || n_cam <= 0 || H <= 0 || W < 3) return PN_ERR_BAD_SHAPE;
+    const RayOut out{origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var, rgb_out};
+    if (!ray_ptrs_ok(idx, c2ws, rgb_pool, out)) return PN_ERR_NULL;
+    return launch_sample_rays<128>(B, n_cam, PanoCams{H, W, c2ws}, idx, near_, far_, rgb_pool, out, stream);
+}
+
+int pn_sample_pinhole_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* pix2cams,
+                           const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
+                           float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
+                           float* far_out, float* noise_var, float* rgb_out, void* stream) {
+    if (B <= 0 || n_cam <= 0 || H < 2 || W < 2 || (int64_t)H * W >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
+    const RayOut out{origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var, rgb_out};
+    if (!pix2cams || !ray_ptrs_ok(idx, c2ws, rgb_pool, out)) return PN_ERR_NULL;
+    return launch_sample_rays<kThreads>(B, n_cam, PinholeCams{H, W, pix2cams, c2ws}, idx, near_, far_, rgb_pool, out, stream);
+}
+
 int pn_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, const float* params_host, const int64_t* idx,
                           const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
                           float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
@@ -335,18 +280,20 @@ int pn_sample_camera_rays(int64_t B, int n_cam, int kind, int H, int W, const fl
     bool ok = false;
     min_size(kind, H, W, ok);
     if (B <= 0 || n_cam <= 0 || !ok || (int64_t)H * W >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
-    if (!params_host || !idx || !c2ws || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out ||
-        !far_out || !noise_var)
-        return PN_ERR_NULL;
-    if ((rgb_pool == nullptr) != (rgb_out == nullptr)) return PN_ERR_NULL;  // target colours: both or neither
-    if (kind == PN_CAM_FISHEYE && !(params_host[0] > 0.f && params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
-    CamParams p;
-    for (int k = 0; k < PN_CAM_PARAMS; ++k) p.v[k] = params_host[k];
-    hipLaunchKernelGGL(k_sample_camera_rays, dim3(nblk(B, kThreads)), dim3(kThreads), 0, ST(stream), B, n_cam, kind, H, W,
-                       p, idx, c2ws, near_, far_, rgb_pool, origins, directions, viewdirs, radii, lossmult, near_out,
-                       far_out, noise_var, rgb_out);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
+    const RayOut out{origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var, rgb_out};
+    if (!params_host || !ray_ptrs_ok(idx, c2ws, rgb_pool, out)) return PN_ERR_NULL;
+    const float* p = params_host;
+    if (kind == PN_CAM_FISHEYE && !(p[0] > 0.f && p[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    switch (kind) {
+        case PN_CAM_CUBE:
+            return launch_sample_rays<kThreads>(B, n_cam, CubeCams{H, W, c2ws}, idx, near_, far_, rgb_pool, out, stream);
+        case PN_CAM_FISHEYE:
+            return launch_sample_rays<kThreads>(B, n_cam, FisheyeCams{H, W, c2ws, p[0], p[1]}, idx, near_, far_, rgb_pool,
+                                                out, stream);
+        default:
+            return launch_sample_rays<kThreads>(B, n_cam, StereoPanoCams{H, W, c2ws, p[0]}, idx, near_, far_, rgb_pool, out,
+                                                stream);
+    }
 }
 
 int pn_reproject(int N, int C, int src_kind, int Hs, int Ws, const float* src_params_host, int dst_kind, int Hd, int Wd,

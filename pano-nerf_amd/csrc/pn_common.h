@@ -12,6 +12,10 @@
         if (hipGetLastError() != hipSuccess) return PN_ERR_HIP; \
     } while (0)
 
+// host-side launch arithmetic: the stream of an entry point's void*, and ceil(n / t) workgroups
+#define ST(s) ((hipStream_t)(s))
+__host__ __device__ inline unsigned nblk(int64_t n, int64_t t) { return (unsigned)((n + t - 1) / t); }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

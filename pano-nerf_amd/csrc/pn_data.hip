@@ -15,8 +15,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-#define ST(s) ((hipStream_t)(s))
-
 template <typename T, int V>
 struct Pack {
     T v[V];

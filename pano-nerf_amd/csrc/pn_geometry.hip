@@ -18,8 +18,6 @@ constexpr int kPer = 4;                    // elements per thread in the classif
 constexpr int kItems = kThreads * kPer;    // elements per block
 constexpr int kScanThreads = 1024;
 
-#define ST(s) ((hipStream_t)(s))
-inline unsigned nblk(int64_t n, int64_t t) { return (unsigned)((n + t - 1) / t); }
 inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // edge offsets from the lower endpoint, in edge-id order: 3 axes, 3 face diagonals, the body diagonal

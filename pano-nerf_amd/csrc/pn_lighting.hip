@@ -19,10 +19,6 @@ constexpr int kPixPerBlock = 2048;  // pixels one projection workgroup covers at
 constexpr int kMaxShBlocks = 64;    // projection workgroups per probe at most
 constexpr int kTile = 256;          // pixels staged per LDS tile of the quadrature
 
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // projection workgroups per probe: a function of the pixel count only, so a probe's sums do not depend on P
 inline int sh_blocks(int64_t hw) {
     int64_t b = (hw + kPixPerBlock - 1) / kPixPerBlock;

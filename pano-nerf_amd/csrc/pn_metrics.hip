@@ -25,12 +25,10 @@ struct Img {
     int tone;  // 0 none, 1 hdr_to_ldr float, 2 hdr_to_ldr uint8
 };
 
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 inline unsigned elem_grid(int64_t n) {
     unsigned g = nblk(n, kThreads);
     return g < (unsigned)kMaxBlocks ? g : (unsigned)kMaxBlocks;
 }
-#define ST(s) ((hipStream_t)(s))
 
 // clamp01 and tonemap (hdr_to_ldr) live in pn_common.h: pn_views.hip's LDR frames use the same arithmetic
 

@@ -18,7 +18,6 @@
 #include <mutex>
 #include <vector>
 
-#define ST(s) ((hipStream_t)(s))
 // PN_DEBUG_SYNC=1: synchronise the device after every step of the MLP entry points and name the step on stderr, so
 // an asynchronous fault is attributed to the launch that caused it (debugging aid; never set in production)
 static bool debug_sync() {
@@ -34,7 +33,6 @@ static bool debug_sync() {
             if (hipDeviceSynchronize() != hipSuccess) return PN_ERR_HIP;       \
         }                                                                      \
     } while (0)
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
 // -------------------------------------------------------------------------------- layouts
 PnLayout pn_layout(int nc) {

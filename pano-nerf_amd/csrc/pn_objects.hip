@@ -18,10 +18,6 @@ constexpr int kTile = 256;     // probe pixels staged per LDS tile
 constexpr int kTriTile = 256;  // triangles staged per LDS tile (3 float4 each: 12 KB)
 constexpr int kMaxProbes = PN_OBJ_MAX_PROBES;
 
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 struct Probes {
     const float* x;
     int64_t probe_stride, cs, ps;  // element (k, c, pix) at x[k * probe_stride + c * cs + pix * ps]

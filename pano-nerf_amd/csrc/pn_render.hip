@@ -1,4 +1,4 @@
-// pn_render.hip — HBM-bound stages of the Pano-NeRF hot path (gfx950): ray generation, cone
+// pn_render.hip — HBM-bound stages of the Pano-NeRF hot path (gfx950): light rays, cone
 // sampling, integrated positional encoding, per-ray alpha-composite scans (forward + adjoint),
 // hierarchical PDF resampling, normal/albedo gathers, Lambertian shading, tone-mapped loss, Adam.
 //
@@ -7,7 +7,6 @@
 // consecutive samples, does its run serially in registers and the group combines the runs with
 // __shfl_up / __shfl_xor — no LDS, no atomics, one pass over HBM.
 #include "pn_common.h"
-#include "pn_pano_ray.h"
 #include <math.h>
 
 #define HALF_PI_F 1.5707964f /* fl32(0.5 * fl32(pi)), models/mip.py:428,437 */
@@ -66,40 +65,7 @@ __device__ __forceinline__ float group_excl_scan(float v, int gl) {
     return inc - v;
 }
 
-// --------------------------------------------------------------------------- ray generation
-// One pixel of an equirectangular camera: pano_ray / store_pano_ray of pn_pano_ray.h (shared with pn_cameras.hip)
-
-__global__ void k_raygen_pano(int H, int W, PanoCam c, float near_, float far_,
-                              float* origins, float* directions, float* viewdirs, float* radii, float* lossmult,
-                              float* near_out, float* far_out, float* noise_var) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= H * W) return;
-    const PanoRay r = pano_ray(H, W, c, idx / W, idx % W);
-    store_pano_ray(idx, r, c, near_, far_, origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var);
-}
-
-// Training-batch sampler that REGENERATES the rays: batch ray b is pixel idx[b] % (H W) of camera idx[b] / (H W); only the
-// 12-byte target colour is read from a stored pool (no 56-byte-per-ray pool in HBM, no pool reads).
-__global__ void k_sample_pano_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* c2ws, float near_,
-                                   float far_, const float* rgb_pool, float* origins, float* directions, float* viewdirs,
-                                   float* radii, float* lossmult, float* near_out, float* far_out, float* noise_var,
-                                   float* rgb_out) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int64_t hw = (int64_t)H * W;
-    int64_t r = idx[b];
-    r = (r >= 0 && r < hw * n_cam) ? r : 0;
-    const int cam = (int)(r / hw), pix = (int)(r % hw);
-    const float* m = c2ws + 16 * cam;
-    const PanoCam c{m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10], m[3], m[7], m[11]};
-    const PanoRay ray = pano_ray(H, W, c, pix / W, pix % W);
-    store_pano_ray(b, ray, c, near_, far_, origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var);
-    if (rgb_pool) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rgb_out[b * 3 + k] = rgb_pool[r * 3 + k];
-    }
-}
-
+// ------------------------------------------------------------------------------- light rays
 __device__ __forceinline__ uint16_t f64_to_half_bits(double x) {
     _Float16 h = (_Float16)x;  // round-to-nearest-even, single rounding from fp64
     uint16_t u;
@@ -964,8 +930,6 @@ __global__ void k_adam_dev(int64_t n, float* p, const float* g, float* m, float*
 }
 
 // ============================================================================ C entry points
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-#define ST(s) ((hipStream_t)(s))
 
 int pn_launch_ipe_backward(int64_t M, const float* mean, const float* cov, const float* d_enc, float* d_mean,
                            hipStream_t s) {
@@ -1013,32 +977,6 @@ __global__ void k_gather_rays(int64_t B, int64_t pool_rays, const int64_t* idx, 
 }
 
 extern "C" {
-
-int pn_raygen_pano(int H, int W, const float* c, float near_, float far_, float* origins, float* directions,
-                   float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out, float* noise_var,
-                   void* stream) {
-    if (H <= 0 || W < 3) return PN_ERR_BAD_SHAPE;
-    if (!c || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out || !far_out || !noise_var)
-        return PN_ERR_NULL;
-    const PanoCam cam{c[0], c[1], c[2], c[4], c[5], c[6], c[8], c[9], c[10], c[3], c[7], c[11]};
-    hipLaunchKernelGGL(k_raygen_pano, dim3(nblk((int64_t)H * W, 256)), dim3(256), 0, ST(stream), H, W, cam, near_, far_,
-                       origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
-}
-
-int pn_sample_pano_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* c2ws, float near_, float far_,
-                        const float* rgb_pool, float* origins, float* directions, float* viewdirs, float* radii,
-                        float* lossmult, float* near_out, float* far_out, float* noise_var, float* rgb_out, void* stream) {
-    if (B <= 0 || n_cam <= 0 || H <= 0 || W < 3) return PN_ERR_BAD_SHAPE;
-    if (!idx || !c2ws || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out || !far_out || !noise_var)
-        return PN_ERR_NULL;
-    if ((rgb_pool == nullptr) != (rgb_out == nullptr)) return PN_ERR_NULL;  // target colours: both or neither
-    hipLaunchKernelGGL(k_sample_pano_rays, dim3(nblk(B, 128)), dim3(128), 0, ST(stream), B, n_cam, H, W, idx, c2ws, near_,
-                       far_, rgb_pool, origins, directions, viewdirs, radii, lossmult, near_out, far_out, noise_var, rgb_out);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
-}
 
 int pn_gather_rays(int64_t B, int64_t pool_rays, const int64_t* idx, const float* const* pool_host, float* const* out_host,
                    void* stream) {

@@ -15,9 +15,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxSize = PN_TEX_MAX_SIZE;
 
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 __host__ __device__ inline int lvl(int n, int l) { return (n >> l) > 1 ? (n >> l) : 1; }  // max(1, n >> l)
 __host__ __device__ inline int levels(int H, int W) {
     int L = 1;

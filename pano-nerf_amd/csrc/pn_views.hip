@@ -1,12 +1,10 @@
-// pn_views.hip — novel views (gfx950): pinhole (perspective) ray generation from (camera, pixel) and the viewable
-// uint8 frames the reference's validation writes (tone-mapped LDR, hotmap depth, (n + 1) / 2 normals, albedo).
-// Conventions are stated in include/panonerf_hip.h.
+// pn_views.hip — novel views (gfx950): the viewable uint8 frames the reference's validation writes (tone-mapped LDR,
+// hotmap depth, (n + 1) / 2 normals, albedo).  The rays of a view come from pn_cameras.hip.  Conventions are stated in
+// include/panonerf_hip.h.
 //
-// Rays: one thread per batch ray regenerates it from the camera's pix2cam and c2w, the mip-NeRF cone radius included
-// (the neighbour's direction is recomputed in the thread, so no ray pool is stored).  Frames: one thread per pixel;
-// the depth kind first reduces (min, max) of the normalised depth over the image in one workgroup, in a fixed order and
-// without atomics, so that repeated calls give the same bytes.  Images are read in place through (channel, pixel) strides,
-// as pn_metrics.hip reads them.
+// Frames: one thread per pixel; the depth kind first reduces (min, max) of the normalised depth over the image in one
+// workgroup, in a fixed order and without atomics, so that repeated calls give the same bytes.  Images are read in place
+// through (channel, pixel) strides, as pn_metrics.hip reads them.
 #include "pn_common.h"
 #include <math.h>
 
@@ -14,64 +12,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMinMaxThreads = 1024;
-
-#define ST(s) ((hipStream_t)(s))
-
-__host__ __device__ inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
-// c2w[:3,:3] @ (pix2cam @ (px, py, 1)), each a 3-term fp32 dot product in index order
-__device__ __forceinline__ void pinhole_dir(const float* p2c, const float* c2w, float px, float py, float out[3]) {
-    float cam[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cam[k] = (p2c[3 * k] * px + p2c[3 * k + 1] * py) + p2c[3 * k + 2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = (c2w[4 * k] * cam[0] + c2w[4 * k + 1] * cam[1]) + c2w[4 * k + 2] * cam[2];
-}
-
-// batch ray b is pixel idx[b] % (H W) of camera idx[b] / (H W) (an index outside the pool reads ray 0, as
-// k_sample_pano_rays does).  radius = |d(i, j) - d(i + 1, j)| * 2 / sqrt(12); the last row reuses row H - 2's value
-__global__ __launch_bounds__(kThreads) void k_sample_pinhole_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx,
-                                                                  const float* pix2cams, const float* c2ws, float near_,
-                                                                  float far_, const float* rgb_pool, float* origins,
-                                                                  float* directions, float* viewdirs, float* radii,
-                                                                  float* lossmult, float* near_out, float* far_out,
-                                                                  float* noise_var, float* rgb_out) {
-    const int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (b >= B) return;
-    const int64_t hw = (int64_t)H * W;
-    int64_t r = idx[b];
-    r = (r >= 0 && r < hw * n_cam) ? r : 0;
-    const int cam = (int)(r / hw);
-    const int pix = (int)(r % hw);
-    const int i = pix / W, j = pix % W;
-    const float* p2c = pix2cams + 9 * (int64_t)cam;
-    const float* m = c2ws + 16 * (int64_t)cam;
-    const float px = (float)j + 0.5f;
-    float d[3], a[3], n[3];
-    pinhole_dir(p2c, m, px, (float)i + 0.5f, d);
-    const int ii = i < H - 1 ? i : H - 2;
-    pinhole_dir(p2c, m, px, (float)ii + 0.5f, a);
-    pinhole_dir(p2c, m, px, (float)(ii + 1) + 0.5f, n);
-    const float dx = sqrtf((a[0] - n[0]) * (a[0] - n[0]) + (a[1] - n[1]) * (a[1] - n[1]) + (a[2] - n[2]) * (a[2] - n[2]));
-    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    origins[b * 3 + 0] = m[3];
-    origins[b * 3 + 1] = m[7];
-    origins[b * 3 + 2] = m[11];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        directions[b * 3 + k] = d[k];
-        viewdirs[b * 3 + k] = d[k] / nrm;
-    }
-    radii[b] = (float)((double)dx * 2.0 / sqrt(12.0));
-    lossmult[b] = 1.f;
-    near_out[b] = near_;
-    far_out[b] = far_;
-    noise_var[b] = 0.f;
-    if (rgb_pool) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rgb_out[b * 3 + k] = rgb_pool[r * 3 + k];
-    }
-}
 
 struct Src {
     const float* p;
@@ -168,22 +108,6 @@ __global__ __launch_bounds__(kThreads) void k_frame(int kind, int64_t HW, Src s,
 }  // namespace
 
 extern "C" {
-
-int pn_sample_pinhole_rays(int64_t B, int n_cam, int H, int W, const int64_t* idx, const float* pix2cams,
-                           const float* c2ws, float near_, float far_, const float* rgb_pool, float* origins,
-                           float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
-                           float* far_out, float* noise_var, float* rgb_out, void* stream) {
-    if (B <= 0 || n_cam <= 0 || H < 2 || W < 2 || (int64_t)H * W >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
-    if (!idx || !pix2cams || !c2ws || !origins || !directions || !viewdirs || !radii || !lossmult || !near_out ||
-        !far_out || !noise_var)
-        return PN_ERR_NULL;
-    if ((rgb_pool == nullptr) != (rgb_out == nullptr)) return PN_ERR_NULL;  // target colours: both or neither
-    hipLaunchKernelGGL(k_sample_pinhole_rays, dim3(nblk(B, kThreads)), dim3(kThreads), 0, ST(stream), B, n_cam, H, W, idx,
-                       pix2cams, c2ws, near_, far_, rgb_pool, origins, directions, viewdirs, radii, lossmult, near_out,
-                       far_out, noise_var, rgb_out);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
-}
 
 int pn_to_frame(int kind, int H, int W, const float* x, int64_t cs, int64_t ps, float scale, float near_, float range,
                 const float* lut, float* work, uint8_t* out, void* stream) {

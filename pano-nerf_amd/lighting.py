@@ -27,7 +27,8 @@ import torch
 
 from . import _lib
 from .geometry import _model_device, _placement, _resolution, grid_points
-from .rays import Rays
+from .cameras import PanoCamera
+from .rays import CameraRig, Rays
 from .render import _Cfg, _light_gather, _planes_of, _tfmt_of
 
 IrradianceVolume = collections.namedtuple("IrradianceVolume", ["sh", "lo", "step"])
@@ -139,17 +140,13 @@ def light_probes(model, positions, height=32, width=64, near=0.0, far=10.0, chun
     P, HW = int(positions.shape[0]), H * W
     out = torch.empty(P * HW, 3, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        st = _stream(dev)
         c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
         c2ws[:, :3, 3] = positions.detach().to(torch.float32)
-        c2ws = c2ws.reshape(P, 16).contiguous()
+        rig = CameraRig(PanoCamera(H, W), c2ws, dev)
         for first in range(0, P * HW, chunk):
             n = min(chunk, P * HW - first)
             idx = torch.arange(first, first + n, dtype=torch.int64, device=dev)
-            rays = [torch.empty(n, k, dtype=torch.float32, device=dev) for k in (3, 3, 3, 1, 1, 1, 1, 1)]
-            _lib.call("pn_sample_pano_rays", n, P, H, W, idx.data_ptr(), c2ws.data_ptr(), float(near), float(far), None,
-                      *[r.data_ptr() for r in rays], None, st)
-            outs, _ = model._run(Rays(*rays), None, False, False, False, False, False)
+            outs, _ = model._run(rig.sample(idx, near, far)[0], None, False, False, False, False, False)
             out[first:first + n].copy_(outs[2])
     return out.view(P, H, W, 3).permute(0, 3, 1, 2)
 

@@ -658,10 +658,7 @@ def _frame_rays(camera, c2w, near, far, dev, radii=False):
     """(origins, directions) [H W, 3] of the rays render_view renders for this camera and pose; radii=True adds their cone
     radii [H W, 1]."""
     from . import views
-    c2ws = views._c2w_stack(c2w, single=True)
-    p, c = views._device_cams(camera, c2ws, dev)
-    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
-    rays, _ = views._sample(camera, 1, p, c, idx, near, far, None, dev)
+    rays = views.generate_camera_rays(camera, c2w, near, far, dev)
     return (rays.origins, rays.directions, rays.radii) if radii else (rays.origins, rays.directions)
 
 

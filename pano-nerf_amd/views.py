@@ -3,9 +3,9 @@ frames and reprojection of images between cameras.
 
 Pano-NeRF's models are trained on panoramas, but what a user renders from a trained model is a new view.  This module
 renders one (or a whole path of them) and turns the renderer's outputs into the uint8 images the reference's validation
-writes.  Ray generation and frames run on the HIP device through ``pn_views.hip`` (the renderer's own entry points do the
-rest) and ``pn_cameras.hip`` (cube-map, fisheye and stereo-panorama rays, reprojection), under ``torch.no_grad()`` on the
-current stream; CPU tensors raise, there is no host fallback.  Cameras and paths are host-side numpy.
+writes.  Frames run on the HIP device through ``pn_views.hip``, rays (``rays.CameraRig``) and reprojection through
+``pn_cameras.hip`` (the renderer's own entry points do the rest), under ``torch.no_grad()`` on the current stream; CPU
+tensors raise, there is no host fallback.  Cameras (``cameras.py``, re-exported here) and paths are host-side numpy.
 
     perspective_camera(h, w, focal | fov_x_deg | pix2cam)   PinholeCamera(h, w, pix2cam [3, 3] fp32)
     pano_camera(h, w)                           PanoCamera(h, w): the equirectangular camera of generate_pano_rays
@@ -17,7 +17,7 @@ current stream; CPU tensors raise, there is no host fallback.  Cameras and paths
     cube_solid_angles(size)                     float64 [6 S, S] exact texel solid angles (sum 4 pi)
     generate_camera_rays(camera, c2w, ...)      Rays of [H W, C] device tensors for any camera
     generate_perspective_rays(camera, c2w, ...) Rays of [H W, C] device tensors (datasets/base_datasets.py:118-265)
-    PerspectiveRayPool(camera, c2ws, images)    the pinhole counterpart of DeviceRayPool: take / sample / rays / len
+    PerspectiveRayPool(camera, c2ws, images)    the pinhole counterpart of DeviceRayPool (rays.py): take / sample / rays / len
     interpolate_path(c2ws, n_views)             gen_render_path (utils/vis.py:136-165), numpy only
     spiral_path(radii, focus_depth, n_poses)    create_spiral_poses (utils/vis.py:168-200), as 4x4 matrices
     spheric_path(radius, n_poses)               create_spheric_poses (utils/vis.py:203-242), as 4x4 matrices
@@ -31,7 +31,6 @@ current stream; CPU tensors raise, there is no host fallback.  Cameras and paths
 Conventions (pixel directions, radii, frame bytes, the cube-map table, the inverse projections) are stated in
 include/panonerf_hip.h.
 """
-import collections
 import math
 import os
 
@@ -40,16 +39,11 @@ import torch
 
 from . import _lib
 from .geometry import _model_device
-from .rays import Rays, _DIMS
+from .cameras import (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, StereoPanoCamera, perspective_camera,  # noqa
+                      pano_camera, cubemap_camera, fisheye_camera, stereo_pano_camera, camera_mask, cube_faces,
+                      cube_solid_angles, _camera, _kind_params, _c2w_stack)
+from .rays import Rays, CameraRig, PerspectiveRayPool, _stream  # noqa
 
-PinholeCamera = collections.namedtuple("PinholeCamera", ["h", "w", "pix2cam"])
-PanoCamera = collections.namedtuple("PanoCamera", ["h", "w"])
-CubeCamera = collections.namedtuple("CubeCamera", ["h", "w"])
-FisheyeCamera = collections.namedtuple("FisheyeCamera", ["h", "w", "focal", "fov_deg"])
-StereoPanoCamera = collections.namedtuple("StereoPanoCamera", ["h", "w", "ipd", "eye"])
-# camera kinds of pn_cameras.hip (include/panonerf_hip.h)
-_CAM_PANO, _CAM_PINHOLE, _CAM_CUBE, _CAM_FISHEYE, _CAM_STEREO_PANO = range(5)
-_CAM_PARAMS = 20
 _MAX_SAMPLES = 16
 
 _FRAME_KINDS = {"ldr": 0, "ldr_gt": 1, "depth": 2, "normal": 3, "albedo": 4}
@@ -64,242 +58,12 @@ _PATH_KINDS = {"ldr": ("rgb", "fine_rgb", "ldr"), "ldr_surf": ("surface", "surfa
 _PATH_GROUP_RAYS = 1 << 22  # rays rendered per group of frames in render_path (~220 MB of outputs at most)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _cuda_device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (got %s); there is no CPU fallback" % dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
-# ---------------------------------------------------------------------------------------------------------- cameras
-def _hw(height, width, min_w=2):
-    h, w = int(height), int(width)
-    if h < 2 or w < min_w:
-        raise ValueError(f"a camera needs height >= 2 and width >= {min_w}; got {height} x {width}")
-    return h, w
-
-
-def perspective_camera(height, width, focal=None, fov_x_deg=None, pix2cam=None):
-    """PinholeCamera(h, w, pix2cam [3, 3] fp32).  With a focal length (pixels) or a horizontal field of view (degrees) the
-    Blender matrix: pixel (x + 1/2, y + 1/2, 1) -> ((x + 1/2 - w/2) / f, -(y + 1/2 - h/2) / f, -1), x right, y up, looking
-    along -z (datasets/base_datasets.py:216-265; focal = w / 2 / tan(fov / 2) as :212-213).  With pix2cam, that matrix as
-    given (the Multicam form, :118-170).  h, w >= 2: the cone radius takes the next row's direction."""
-    h, w = _hw(height, width)
-    if pix2cam is not None:
-        if focal is not None or fov_x_deg is not None:
-            raise ValueError("give pix2cam, or one of focal and fov_x_deg, not both")
-        m = np.asarray(pix2cam, dtype=np.float32)
-        if m.shape != (3, 3) or not np.isfinite(m).all():
-            raise ValueError(f"pix2cam must be a finite 3x3 matrix; got shape {m.shape}")
-        return PinholeCamera(h, w, np.ascontiguousarray(m))
-    if (focal is None) == (fov_x_deg is None):
-        raise ValueError("give exactly one of focal and fov_x_deg (or pix2cam)")
-    if focal is None:
-        fov = float(fov_x_deg)
-        if not 0.0 < fov < 180.0:
-            raise ValueError(f"fov_x_deg must lie in (0, 180); got {fov_x_deg!r}")
-        focal = 0.5 * w / math.tan(0.5 * math.radians(fov))
-    f = float(focal)
-    if not (f > 0.0 and math.isfinite(f)):
-        raise ValueError(f"focal must be positive and finite; got {focal!r}")
-    m = np.array([[1.0 / f, 0.0, -0.5 * w / f], [0.0, -1.0 / f, 0.5 * h / f], [0.0, 0.0, -1.0]])
-    return PinholeCamera(h, w, m.astype(np.float32))
-
-
-def pano_camera(height, width):
-    """PanoCamera(h, w): the equirectangular camera of generate_pano_rays (pn_raygen_pano), for render_view / render_path."""
-    return PanoCamera(*_hw(height, width, 3))
-
-
-def cubemap_camera(size):
-    """CubeCamera(h = 6 size, w = size), size >= 2: a cube map as a vertical strip of faces in the order +x, -x, +y, -y,
-    +z, -z.  Face texel (x, y) has s = 2 (x + 1/2) / size - 1, t = 2 (y + 1/2) / size - 1 (t points down) and looks along
-    +x (1, -t, -s), -x (-1, -t, s), +y (s, 1, t), -y (s, -1, -t), +z (s, -t, 1), -z (-s, -t, -1): the OpenGL cube-map
-    table, i.e. the lookup convention of engines (a face viewed as a picture is mirrored relative to a pinhole view)."""
-    s = int(size)
-    if s != size or s < 2:
-        raise ValueError(f"a cube map needs an integer size >= 2; got {size!r}")
-    return CubeCamera(6 * s, s)
-
-
-def fisheye_camera(height, width, fov_deg=180.0, focal=None):
-    """FisheyeCamera(h, w, focal, fov_deg): an equidistant fisheye looking along -z like the pinhole, 0 < fov_deg <= 360.
-    With u = x + 1/2 - w/2, v = -(y + 1/2 - h/2), r = hypot(u, v), the pixel looks theta = r / focal away from the axis
-    along (sin theta u / r, sin theta v / r, -cos theta).  focal (pixels per radian) defaults to (min(h, w) / 2) /
-    radians(fov_deg / 2): the image circle touches the shorter side.  A pixel is inside when theta <= radians(fov_deg / 2);
-    outside pixels get the forward direction and lossmult = 0, and render_view / render_path return 0 in every channel
-    there.  They are still rendered: up to 1 - pi / 4 of the frame's rays for a full circle in a square are spent on
-    pixels that end up 0 (there is no compaction of the inside rays)."""
-    h, w = _hw(height, width)
-    fov = float(fov_deg)
-    if not 0.0 < fov <= 360.0:
-        raise ValueError(f"fov_deg must lie in (0, 360]; got {fov_deg!r}")
-    if focal is None:
-        focal = 0.5 * min(h, w) / math.radians(0.5 * fov)
-    f = float(focal)
-    if not (f > 0.0 and math.isfinite(f)):
-        raise ValueError(f"focal must be positive and finite; got {focal!r}")
-    return FisheyeCamera(h, w, f, fov)
-
-
-def stereo_pano_camera(height, width, ipd, eye):
-    """StereoPanoCamera(h, w, ipd, eye), eye "left" or "right": one eye of an omnidirectional-stereo (ODS) pair.  Every
-    pixel looks along the panorama camera's direction; column j (heading angle theta_j = -(j + 1/2) 2 pi / w) starts at
-    the camera-space origin +-(ipd / 2) (-cos theta_j, 0, sin theta_j), + for the right eye: heading x up, so the ray is
-    tangent to the viewing circle of diameter ipd.  radii and noise_var are the panorama camera's; with ipd = 0 the rays
-    are the panorama camera's bit for bit."""
-    h, w = _hw(height, width, 3)
-    d = float(ipd)
-    if not (d >= 0.0 and math.isfinite(d)):
-        raise ValueError(f"ipd must be finite and >= 0; got {ipd!r}")
-    if eye not in ("left", "right"):
-        raise ValueError(f"eye must be 'left' or 'right'; got {eye!r}")
-    return StereoPanoCamera(h, w, d, eye)
-
-
-_CAMERAS = (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, StereoPanoCamera)
-
-
-def _camera(camera):
-    if isinstance(camera, PinholeCamera):
-        if np.asarray(camera.pix2cam).shape != (3, 3):
-            raise ValueError("PinholeCamera.pix2cam must be 3x3")
-        return camera
-    if isinstance(camera, CubeCamera):
-        if camera.w < 2 or camera.h != 6 * camera.w:
-            raise ValueError(f"a CubeCamera is 6 size x size with size >= 2; got {camera.h} x {camera.w}")
-        return camera
-    if isinstance(camera, FisheyeCamera):
-        if not (camera.focal > 0.0 and 0.0 < camera.fov_deg <= 360.0):
-            raise ValueError("a FisheyeCamera needs focal > 0 and 0 < fov_deg <= 360")
-        return camera
-    if isinstance(camera, StereoPanoCamera):
-        if camera.eye not in ("left", "right") or not camera.ipd >= 0.0:
-            raise ValueError("a StereoPanoCamera needs ipd >= 0 and eye 'left' or 'right'")
-        return camera
-    if isinstance(camera, PanoCamera):
-        return camera
-    raise ValueError("camera must come from perspective_camera, pano_camera, cubemap_camera, fisheye_camera or "
-                     f"stereo_pano_camera; got {type(camera).__name__}")
-
-
-def _kind_params(camera):
-    """(kind, params float32 [_CAM_PARAMS]) of a camera for pn_cameras.hip (the layout of include/panonerf_hip.h)."""
-    p = np.zeros(_CAM_PARAMS, np.float32)
-    if isinstance(camera, PinholeCamera):
-        m = np.asarray(camera.pix2cam, np.float32).reshape(3, 3)
-        p[:9] = m.reshape(9)
-        p[9:18] = np.linalg.inv(m.astype(np.float64)).reshape(9)  # cam2pix: inverted in fp64, rounded once
-        return _CAM_PINHOLE, p
-    if isinstance(camera, CubeCamera):
-        return _CAM_CUBE, p
-    if isinstance(camera, FisheyeCamera):
-        p[0], p[1] = camera.focal, math.radians(0.5 * camera.fov_deg)
-        return _CAM_FISHEYE, p
-    if isinstance(camera, StereoPanoCamera):
-        p[0] = (0.5 if camera.eye == "right" else -0.5) * camera.ipd
-        return _CAM_STEREO_PANO, p
-    return _CAM_PANO, p
-
-
-def camera_mask(camera):
-    """bool [H, W] numpy: the pixels a camera sees.  For a fisheye, the pixels whose centre lies inside the image circle
-    (theta <= radians(fov_deg / 2), evaluated in float64); all true for every other camera."""
-    camera = _camera(camera)
-    if not isinstance(camera, FisheyeCamera):
-        return np.ones((camera.h, camera.w), bool)
-    u = np.arange(camera.w) + 0.5 - 0.5 * camera.w
-    v = -(np.arange(camera.h) + 0.5 - 0.5 * camera.h)
-    return np.hypot(u[None, :], v[:, None]) / camera.focal <= math.radians(0.5 * camera.fov_deg)
-
-
-def cube_faces(x):
-    """[.., C, 6 S, S] -> [.., 6, C, S, S]: the faces (+x, -x, +y, -y, +z, -z) of cube-map strips, as a view where the
-    layout allows (torch tensor or numpy array)."""
-    shape = tuple(x.shape)
-    if len(shape) < 3 or shape[-1] < 1 or shape[-2] != 6 * shape[-1]:
-        raise ValueError(f"a cube-map strip is [.., C, 6 S, S]; got {shape}")
-    S = shape[-1]
-    y = x.reshape(*shape[:-2], 6, S, S)
-    return y.movedim(-3, -4) if isinstance(y, torch.Tensor) else np.moveaxis(y, -3, -4)
-
-
-def cube_solid_angles(size):
-    """float64 [6 size, size]: the exact solid angle of every texel of cubemap_camera(size), from the corner function
-    A(x, y) = atan2(x y, sqrt(x^2 + y^2 + 1)) of the face plane at distance 1: A(x1, y1) - A(x0, y1) - A(x1, y0) +
-    A(x0, y0) over the texel's edges in (s, t).  The sum is 4 pi."""
-    S = cubemap_camera(size).w
-    e = 2.0 * np.arange(S + 1, dtype=np.float64) / S - 1.0
-    x, y = e[None, :], e[:, None]
-    a = np.arctan2(x * y, np.sqrt(x * x + y * y + 1.0))
-    face = a[1:, 1:] - a[1:, :-1] - a[:-1, 1:] + a[:-1, :-1]
-    return np.tile(face, (6, 1))
-
-
-def _c2w_stack(c2ws, single=False):
-    """[n, 4, 4] float64 of one c2w ([4, 4] or [3, 4]) or a sequence of them; ValueError on any other shape."""
-    a = np.asarray(c2ws, dtype=np.float64)
-    if single:
-        a = a[None]
-    if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] not in ((4, 4), (3, 4)):
-        raise ValueError("a c2w must be a 4x4 or 3x4 matrix" + ("" if single else " (c2ws: [n, 4, 4] or [n, 3, 4])")
-                         + f"; got shape {np.shape(c2ws)}")
-    if not np.isfinite(a).all():
-        raise ValueError("c2w holds a non-finite value")
-    out = np.tile(np.eye(4), (a.shape[0], 1, 1))
-    out[:, :3, :] = a[:, :3, :]
-    return out
-
-
-def _device_cams(camera, c2ws, dev):
-    """(pix2cams [n, 9] or None, c2ws [n, 16]) fp32 device arrays for the ray kernels.  For a cube, fisheye or
-    stereo-panorama camera the first entry is the host parameter block of pn_sample_camera_rays instead."""
-    n = c2ws.shape[0]
-    c = torch.from_numpy(np.ascontiguousarray(c2ws.astype(np.float32).reshape(n, 16))).to(dev)
-    if isinstance(camera, PanoCamera):
-        return None, c
-    if isinstance(camera, (CubeCamera, FisheyeCamera, StereoPanoCamera)):
-        return _kind_params(camera)[1], c
-    p = np.tile(np.asarray(camera.pix2cam, np.float32).reshape(1, 9), (n, 1))
-    return torch.from_numpy(p).to(dev), c
-
-
-def _sample(camera, n_cam, pix2cams, c2ws, idx, near, far, rgb_pool, dev):
-    """Rays (and gathered colours) of the (camera, pixel) rows idx [B] int64 (device)."""
-    B = int(idx.numel())
-    outs = [torch.empty(B, d, dtype=torch.float32, device=dev) for d in _DIMS]
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if rgb_pool is not None else None
-    ptrs = [x.data_ptr() for x in outs]
-    with torch.cuda.device(dev):
-        if isinstance(camera, PanoCamera):
-            _lib.call("pn_sample_pano_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), c2ws.data_ptr(), float(near),
-                      float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
-        elif isinstance(camera, (CubeCamera, FisheyeCamera, StereoPanoCamera)):
-            _lib.call("pn_sample_camera_rays", B, n_cam, _kind_params(camera)[0], camera.h, camera.w, pix2cams.ctypes.data,
-                      idx.data_ptr(), c2ws.data_ptr(), float(near), float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb),
-                      _stream(dev))
-        else:
-            _lib.call("pn_sample_pinhole_rays", B, n_cam, camera.h, camera.w, idx.data_ptr(), pix2cams.data_ptr(),
-                      c2ws.data_ptr(), float(near), float(far), _lib.ptr(rgb_pool), *ptrs, _lib.ptr(rgb), _stream(dev))
-    return Rays(*outs), rgb
-
-
 def generate_camera_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
     """One camera of any model -> Rays of [H W, C] fp32 device tensors (row-major pixels): the rays render_view renders
     for it (pn_sample_pano_rays, pn_sample_pinhole_rays or pn_sample_camera_rays over idx = arange(H W))."""
-    camera = _camera(camera)
-    c2ws = _c2w_stack(c2w, single=True)
-    dev = _cuda_device(device)
-    p, c = _device_cams(camera, c2ws, dev)
-    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
-    with torch.no_grad():
-        return _sample(camera, 1, p, c, idx, near, far, None, dev)[0]
+    rig = CameraRig(camera, _c2w_stack(c2w, single=True), device)
+    idx = torch.arange(rig.h * rig.w, dtype=torch.int64, device=rig.device)
+    return rig.sample(idx, near, far)[0]
 
 
 def generate_perspective_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
@@ -307,53 +71,7 @@ def generate_perspective_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
     idx = arange(H W), the arithmetic every pinhole ray of this module comes from."""
     if not isinstance(camera, PinholeCamera):
         raise ValueError("camera must come from perspective_camera")
-    _camera(camera)
-    c2ws = _c2w_stack(c2w, single=True)
-    dev = _cuda_device(device)
-    p, c = _device_cams(camera, c2ws, dev)
-    idx = torch.arange(camera.h * camera.w, dtype=torch.int64, device=dev)
-    return _sample(camera, 1, p, c, idx, near, far, None, dev)[0]
-
-
-class PerspectiveRayPool:
-    """Batch sampler over the pixels of a set of pinhole cameras sharing one PinholeCamera: the counterpart of
-    DeviceRayPool for Blender- or Multicam-style data.  No ray pool is stored: a batch is one kernel
-    (pn_sample_pinhole_rays) that regenerates the drawn rows' rays from the camera matrices.  Only the target colours
-    (``images`` = [H, W, 3] arrays per camera, optional) are kept and gathered."""
-
-    def __init__(self, camera, c2ws, images=None, near=0.0, far=10.0, device="cuda"):
-        if not isinstance(camera, PinholeCamera):
-            raise ValueError("camera must come from perspective_camera")
-        self.camera = _camera(camera)
-        self.h, self.w = camera.h, camera.w
-        self.near, self.far = float(near), float(far)
-        self.c2ws_host = _c2w_stack(c2ws).astype(np.float32)
-        self.device = _cuda_device(device)
-        self.n_cam = self.c2ws_host.shape[0]
-        self.pix2cams, self.c2ws = _device_cams(camera, self.c2ws_host, self.device)
-        self.rgbs = None
-        if images is not None:
-            self.rgbs = torch.cat([torch.as_tensor(im, dtype=torch.float32).reshape(-1, 3) for im in images], 0).to(self.device)
-            if self.rgbs.shape[0] != len(self):
-                raise ValueError("images must be [H, W, 3] per camera")
-
-    def __len__(self):
-        return self.n_cam * self.h * self.w
-
-    @property
-    def rays(self):
-        """The materialised pool (camera-major, row-major pixels) - for tests and one-off uses; NOT cached."""
-        return self.take(torch.arange(len(self), dtype=torch.int64, device=self.device))[0]
-
-    def take(self, idx):
-        """Rays (and target colours) of the pool rows `idx` (int64 device tensor, row = camera * H * W + pixel)."""
-        idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
-        return _sample(self.camera, self.n_cam, self.pix2cams, self.c2ws, idx, self.near, self.far, self.rgbs, self.device)
-
-    def sample(self, batch_size, generator=None):
-        """-> (Rays of [B, C], rgb [B, 3] or None), all on the device."""
-        idx = torch.randint(0, len(self), (int(batch_size),), device=self.device, generator=generator)
-        return self.take(idx)
+    return generate_camera_rays(camera, c2w, near, far, device)
 
 
 # ------------------------------------------------------------------------------------------------------------ paths
@@ -567,11 +285,11 @@ def _flags(model, outputs, env_rays):
     return surf, surf or "normal" in outputs
 
 
-def _render_rows(model, camera, pix2cams, c2ws, n_cam, first, count, env_rays, surf, normals, near, far, chunk, bufs,
-                 dev, streams=2):
+def _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, chunk, bufs, streams=2):
     """Render rays [first, first + count) of the (frame, pixel) index space into bufs[name][0:count].  The chunks are
     dealt to `streams` HIP streams with the weight packs built once and frozen, as render_image deals them (the same
     kernels on the same rays: the same bits)."""
+    dev = rig.device
     starts = list(range(0, count, chunk))
     cur = torch.cuda.current_stream(dev)
     lanes = [cur]
@@ -596,12 +314,12 @@ def _render_rows(model, camera, pix2cams, c2ws, n_cam, first, count, env_rays, s
             with torch.cuda.stream(lanes[i % len(lanes)]):
                 n = min(chunk, count - s)
                 idx = torch.arange(first + s, first + s + n, dtype=torch.int64, device=dev)
-                rays, _ = _sample(camera, n_cam, pix2cams, c2ws, idx, near, far, None, dev)
+                rays, _ = rig.sample(idx, near, far)
                 outs, _ = model._run(rays, env_rays if surf else None, False, False, surf, False, normals)
                 comp0, dist0, comp1, dist1, _, normal, albedo, surface, _, shading = outs
                 got = dict(coarse_rgb=comp0, fine_rgb=comp1, coarse_dep=dist0, fine_dep=dist1, fine_nor=normal,
                            albedo=albedo, surface_rgb=surface, shading=shading)
-                if isinstance(camera, FisheyeCamera):  # 0 in every channel outside the image circle
+                if isinstance(rig.camera, FisheyeCamera):  # 0 in every channel outside the image circle
                     seen = rays.lossmult > 0
                     for name, buf in bufs.items():
                         buf[s:s + n].copy_(torch.where(seen, got[name].reshape(n, -1), 0.0))
@@ -645,8 +363,8 @@ def render_view(model, camera, c2w, env_rays=None, outputs=("rgb", "depth", "nor
     names = [k for o in outputs for k in _OUTPUTS[o]]
     bufs = {k: torch.empty(H * W, _WIDTH[k], dtype=torch.float32, device=dev) for k in dict.fromkeys(names)}
     with torch.no_grad(), torch.cuda.device(dev):
-        p, c = _device_cams(camera, c2ws, dev)
-        _render_rows(model, camera, p, c, 1, 0, H * W, env_rays, surf, normals, near, far, chunk, bufs, dev)
+        rig = CameraRig(camera, c2ws, dev)
+        _render_rows(model, rig, 0, H * W, env_rays, surf, normals, near, far, chunk, bufs)
     return {k: v.view(1, H, W, -1).permute(0, 3, 1, 2) for k, v in bufs.items()}
 
 
@@ -678,12 +396,11 @@ def render_path(model, camera, poses, env_rays=None, kinds=("ldr", "depth", "nor
         for k in kinds:
             os.makedirs(os.path.join(out_dir, k), exist_ok=True)
     with torch.no_grad(), torch.cuda.device(dev):
-        p, c = _device_cams(camera, c2ws, dev)
+        rig = CameraRig(camera, c2ws, dev)
         for g0 in range(0, n, group):
             nf = min(group, n - g0)
             bufs = {k: torch.empty(nf * HW, _WIDTH[k], dtype=torch.float32, device=dev) for k in names}
-            _render_rows(model, camera, p, c, n, g0 * HW, nf * HW, env_rays, surf, normals, near, far, chunk, bufs,
-                         dev)
+            _render_rows(model, rig, g0 * HW, nf * HW, env_rays, surf, normals, near, far, chunk, bufs)
             for f in range(nf):
                 i = g0 + f
                 for k in kinds:

@@ -75,8 +75,7 @@ def ray_cameras():
 
 def _take(cam, c2ws, idx, rgb_pool, near=0.25, far=7.5):
     from pano_nerf_amd import views
-    p, c = views._device_cams(cam, views._c2w_stack(c2ws), dev())
-    return views._sample(cam, len(c2ws), p, c, idx, near, far, rgb_pool, dev())
+    return views.CameraRig(cam, views._c2w_stack(c2ws), dev()).sample(idx, near, far, rgb_pool)
 
 
 def _shuffled_rows(cam, n_cam, seed):
@@ -154,6 +153,37 @@ def test_generate_camera_rays_is_every_camera():
     assert np.abs(cube.directions.cpu().numpy() - want["directions"]).max() <= 2e-6
     with pytest.raises(RuntimeError):
         views.generate_camera_rays(views.cubemap_camera(3), c2w, device="cpu")
+
+
+def pool_cameras():
+    from pano_nerf_amd import views
+    cams = dict(pano=views.pano_camera(4, 8), pinhole=views.perspective_camera(6, 8, fov_x_deg=70.0), **ray_cameras())
+    for eye in ("left", "right"):
+        cams[f"stereo_{eye}_ipd0"] = views.stereo_pano_camera(4, 8, 0.0, eye)
+    return cams
+
+
+@pytest.mark.parametrize("name", list(pool_cameras()))
+def test_ray_pool_take_is_generate_camera_rays_row_for_row(name):
+    """The decode and store path every camera shares: RayPool.take of every row once, shuffled, plus a row below 0 and a
+    row >= len(pool), equals the per-camera generate_camera_rays rows bit for bit; both outside rows read row 0, colour
+    included.  B = 2 H W + 2 is no multiple of the block size, so the last workgroup is partial."""
+    from pano_nerf_amd import views
+    from pano_nerf_amd.rays import CameraRig, RayPool
+    cam = pool_cameras()[name]
+    c2ws = [generic_c2w(0), generic_c2w(1)]
+    n = 2 * cam.h * cam.w
+    images = np.random.default_rng(12).random((2, cam.h, cam.w, 3)).astype(np.float32)
+    pool = RayPool(CameraRig(cam, np.stack(c2ws), dev()), images, near=0.25, far=7.5)
+    assert len(pool) == n
+    rows = np.concatenate([np.random.default_rng(11).permutation(n), [-3, n + 5]])
+    got, rgb = pool.take(T(rows, torch.int64))
+    full = [views.generate_camera_rays(cam, c, 0.25, 7.5) for c in c2ws]
+    src = torch.as_tensor(np.where((rows >= 0) & (rows < n), rows, 0)).to(dev())
+    assert len(rows) == n + 2 and (src[-2:] == 0).all()
+    for f in got._fields:
+        assert bits_equal(getattr(got, f), torch.cat([getattr(r, f) for r in full], 0)[src]), f
+    assert bits_equal(rgb, T(images.reshape(n, 3))[src])
 
 
 # ------------------------------------------------------------------------------------------------------- reprojection

@@ -5,8 +5,9 @@ no light gather) and with every output ("all": ldr_surf and albedo added), and, 
 render_image on the same rays frame by frame (the yardstick).  --repeats rounds of the three; frames/s, the median and
 the spread (max - min) of each are printed as one JSON line.
 
---what kernels: the two new kernels alone (pn_sample_pinhole_rays over every ray of the path, pn_to_frame for each kind
-at --size) with their bytes moved.  Run it under rocprofv3 for the kernel trace:
+--what kernels: the ray sampler of every camera kind (CameraRig.sample over every ray of the path; the pinhole at --size,
+the others at the nearest shape of theirs) and pn_to_frame for each kind at --size, with their bytes moved.  Run it under
+rocprofv3 for the kernel trace:
 
 --what cameras: render_view of a 6 x 256 cube map and of a 512 x 1024 stereo-panorama pair next to the panorama
 render_view of the same run (rays/s: the renderer is the same, so should the rate be), and views.reproject of a
@@ -32,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pano_nerf_amd as pn  # noqa: E402
 from oracle import pano_oracle as orc  # noqa: E402
 from pano_nerf_amd import views  # noqa: E402
+from pano_nerf_amd.rays import CameraRig  # noqa: E402
 
 BASIC = ("ldr", "depth", "normal")
 ALL = ("ldr", "ldr_surf", "depth", "normal", "albedo")
@@ -156,12 +158,15 @@ def main():
     else:
         res = {}
         dev = torch.device("cuda", torch.cuda.current_device())
-        pc, cc = views._device_cams(cam, views._c2w_stack(path), dev)
-        B = n * H * W
-        idx = torch.arange(B, dtype=torch.int64, device=dev)
-        ms = event_ms(lambda: views._sample(cam, n, pc, cc, idx, 0.0, 10.0, None, dev), 5)
-        byts = B * (8 + 15 * 4)  # index in, 15 floats of ray out
-        res["pn_sample_pinhole_rays"] = dict(rays=B, call_ms=ms, bytes=byts, tb_per_s=byts / (ms * 1e-3) / 1e12)
+        S = max(2, round((H * W / 6) ** 0.5))
+        for name, c in (("pinhole", cam), ("pano", views.pano_camera(H, W)), ("cube", views.cubemap_camera(S)),
+                        ("fisheye", views.fisheye_camera(H, W)), ("stereo_pano", views.stereo_pano_camera(H, W, 0.064, "left"))):
+            rig = CameraRig(c, path, dev)
+            B = len(rig)
+            idx = torch.arange(B, dtype=torch.int64, device=dev)
+            ms = event_ms(lambda: rig.sample(idx, 0.0, 10.0), 5)
+            byts = B * (8 + 15 * 4)  # index in, 15 floats of ray out
+            res[f"sample_{name}_rays"] = dict(rays=B, call_ms=ms, bytes=byts, tb_per_s=byts / (ms * 1e-3) / 1e12)
         g = torch.Generator(device="cuda").manual_seed(0)
         img3 = (torch.rand(H * W, 3, device="cuda", generator=g) * 2.0).view(1, H, W, 3).permute(0, 3, 1, 2)
         dep = (torch.rand(H * W, 1, device="cuda", generator=g) * 8.0).view(1, H, W, 1).permute(0, 3, 1, 2)
