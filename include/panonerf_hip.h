@@ -551,6 +551,57 @@ int pn_reproject(int N, int C, int src_kind, int Hs, int Ws, const float* src_pa
                  const float* dst_params_host, const float* rotation_host, int samples, float fill, const float* image,
                  int64_t image_stride, int64_t cs, int64_t ps, float* out, float* coverage, void* stream);
 
+/* ---- depth-aware view warping (pn_cameras.hip) ------------------------------------------------------------------------
+ * Forward warping of RGB-D frames into other posed cameras with a z-buffer: pn_warp_splat scatters, pn_warp_resolve
+ * gathers.  Cameras are the central kinds above (PANO, PINHOLE, CUBE, FISHEYE; STEREO_PANO is PN_ERR_UNSUPPORTED), params
+ * HOST arrays as for pn_reproject; poses are device arrays of row-major 4x4 c2w (R = c2w[:3,:3], o = c2w[:3, 3]).  All S
+ * sources share (src_kind, Hs, Ws, src_params), all D destinations (dst_kind, Hd, Wd, dst_params).  Everything is fp32,
+ * separate operations in the order written (3-term sums associate to the left: (a + b) + c).
+ * Splat, per source frame s < S and source pixel (i = row, j = column) with t = depth[s, i, j] (depth [S, Hs, Ws]):
+ *   skip unless 0 < t < inf (NaN, 0, negative and Inf are no points).
+ *   dc = the camera-space direction of the ray the samplers above give that pixel, i.e. at position (j + 1/2, i + 1/2):
+ *     PANO unit (theta = -(j + 1/2) / W 2 pi, phi = (i + 1/2) / H pi, as pn_sample_pano_rays), PINHOLE pix2cam @ (px, py, 1)
+ *     NOT normalised, CUBE the table direction divided by its norm, FISHEYE unit; a fisheye pixel with theta > theta_max
+ *     is skipped.  So t is the distance along that sampler's ray (the renderer's depth output) for every camera.
+ *     |dc| = sqrt((x x + y y) + z z) for a pinhole and exactly 1 for the others.
+ *   X = (R_s dc) t + o_s  (R_s dc by 3-term dot products in index order, then one product and one sum per component).
+ * then per destination d < D:
+ *   e = R_d^T (X - o_d)  (e_k = (R[0][k] v_0 + R[1][k] v_1) + R[2][k] v_2),  rho = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2);
+ *   skip unless 0 < rho < inf.
+ *   (qx, qy, face) = the position of direction e in the destination camera by the inverse projections of pn_reproject (qy
+ *   within the face for a cube); skip where that is invalid (behind or off a pinhole's frame, outside a fisheye's circle).
+ *   Footprint: a(i, j) = |u(y, j) - u(y + 1, j)| with u the UNIT direction of a pixel centre (the equidistant formula
+ *   also outside a fisheye's circle; PANO here by theta = -(px / W) 2 pi, phi = (py / H) pi) and the row rule of the radii
+ *   above: rows count within a cube's face, y = min(row, rows - 2).  a_s = a(i, j) of the source camera; a_d that of the
+ *   destination camera at the landing pixel (min(max(floor qy, 0), rows - 1), min(max(floor qx, 0), W - 1)) of `face`.
+ *     size = (scale ((t |dc|) a_s)) / (rho a_d):  the angular size of the source pixel seen from the destination, in
+ *     destination pixels, times scale.   k = 1 unless size > 1 (a NaN size too); else min(max_splat, ceil(size)).
+ *   Pixels: columns x0 .. x0 + k - 1 with x0 = floor(qx - (k - 1) / 2), rows y0 .. y0 + k - 1 with y0 = floor(qy - (k - 1) / 2).
+ *   A destination panorama's columns wrap; every other column and every row outside the image (a cube: outside the face)
+ *   is dropped.  A fisheye is not clipped to its circle.
+ *   For each pixel (y, x): zbuf[d, y, x] = min(zbuf[d, y, x], (uint64(bits of rho) << 32) | (s Hs Ws + i Ws + j)), a 64-bit
+ *   unsigned atomic minimum.  rho > 0, so its bits order as its value; the low word makes every key unique (ties in rho go
+ *   to the lower source index), so the result does not depend on the order of the atomics: repeated calls give the same
+ *   bits.  zbuf [D, Hd, Wd] uint64 is set to all ones (PN_WARP_EMPTY) by the caller; several splats may share one zbuf.
+ * Resolve, per destination d and pixel: key = zbuf[d, y, x].  Empty (all ones, or a low word >= S Hs Ws): index = -1,
+ * depth_out = NaN, coverage = 0 and every channel = fill.  Otherwise index = the low word (int64), coverage = 1,
+ * depth_out = rho / |d_dst| with d_dst the destination's ray direction at the pixel centre (|d_dst| = |pix2cam @ (x + 1/2,
+ * y + 1/2, 1)| for a pinhole, no division for the others): again the distance along that camera's ray.  out[d, c, y, x] =
+ * image[s image_stride + c cs + pix ps] of that source pixel (image [S, C, Hs, Ws] addressed as in pn_reproject; NaN
+ * propagates).  image and out may both be NULL: depth, index and coverage only.  out [D, C, Hd, Wd], depth_out, index
+ * (int64) and coverage [D, Hd, Wd] are contiguous.  One launch each on `stream`; no workspace.
+ * Errors: PN_ERR_UNSUPPORTED (an unknown kind, STEREO_PANO), PN_ERR_BAD_SHAPE (S or D <= 0, a size below the kind's
+ * minimum, S Hs Ws >= 2^32, D Hd Wd >= 2^31, max_splat outside [1, PN_WARP_MAX_SPLAT], scale not positive and finite,
+ * fisheye params not positive, C <= 0 with an image), PN_ERR_NULL (a required pointer; image without out or the reverse). */
+#define PN_WARP_MAX_SPLAT 8
+#define PN_WARP_EMPTY 0xffffffffffffffffull
+int pn_warp_splat(int S, int src_kind, int Hs, int Ws, const float* src_params_host, const float* depth,
+                  const float* src_c2ws, int D, int dst_kind, int Hd, int Wd, const float* dst_params_host,
+                  const float* dst_c2ws, int max_splat, float scale, uint64_t* zbuf, void* stream);
+int pn_warp_resolve(int S, int C, int Hs, int Ws, int D, int dst_kind, int Hd, int Wd, const float* dst_params_host,
+                    const uint64_t* zbuf, const float* image, int64_t image_stride, int64_t cs, int64_t ps, float fill,
+                    float* out, float* depth_out, int64_t* index, float* coverage, void* stream);
+
 /* ---- dataset ingest (pn_data.hip) ---------------------------------------------------------------------------------
  * planes: the channel planes of one decoded scanline OpenEXR file as stored, [Hs][n_ch][Ws] (line, channel, column),
  * fp16 (is_half != 0) or fp32, on the device.  out: [Hs / factor, Ws / factor, C] fp32 interleaved, C = 1 for

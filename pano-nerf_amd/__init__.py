@@ -15,7 +15,8 @@ Public surface (mirrors the reference's names):
     lighting                      spatially-varying lighting: HDR light probes, SH projection, exact and SH irradiance,
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
     views                         novel views: perspective cameras and ray pools, camera paths, render_view / render_path
-                                  and the reference's viewable uint8 frames (HIP kernels)
+                                  and the reference's viewable uint8 frames, reprojection between cameras and depth-aware
+                                  warping of rendered frames to other poses: warp_view, render_path_warped (HIP kernels)
     objects                       virtual object insertion: ray / triangle tracing, the reference's Lambertian and microfacet
                                   shading under light probes, cast shadows, insert_object / insert_path (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR

@@ -77,6 +77,8 @@ SIGNATURES = {
     "pn_to_frame": ("i", "iiipllfffppp" + "p"),
     "pn_sample_camera_rays": ("i", "liiiipppffp" + "p" * 9 + "p"),
     "pn_reproject": ("i", "iiiiipiiippifplllppp"),
+    "pn_warp_splat": ("i", "iiiipppiiiippifpp"),
+    "pn_warp_resolve": ("i", "iiiiiiii" + "ppp" + "lllf" + "pppp" + "p"),
     "pn_ingest_image": ("i", "iiiipiiiiiiffpp"),
     "pn_tri_setup": ("i", "llpppp"),
     "pn_trace_mesh": ("i", "lpplpppi" + "pppp" + "p"),

@@ -1,6 +1,6 @@
 // pn_cameras.hip — cameras (gfx950): ray generation from (camera, pixel) for every camera model (panorama, pinhole,
-// cube map, equidistant fisheye, stereo panorama (ODS)), the panorama pool generator, and reprojection of images between
-// the central cameras (panorama, pinhole, cube map, fisheye).  Conventions are stated in include/panonerf_hip.h.
+// cube map, equidistant fisheye, stereo panorama (ODS)), the panorama pool generator, and reprojection and depth-aware
+// warping of images between the central cameras (panorama, pinhole, cube map, fisheye).  Conventions are stated in include/panonerf_hip.h.
 //
 // Rays: one thread per batch ray regenerates it from the camera matrices, the cone radius included (the neighbour's
 // direction is recomputed in the thread), so no 56-byte-per-ray pool is stored or read; only the 12-byte
@@ -9,6 +9,8 @@
 // direction -> rotated -> source pixel once, its four bilinear taps are reused over the channels (four accumulators at a
 // time), the mean over the valid subsamples is taken in a fixed order, and consecutive lanes store consecutive pixels of
 // a destination row.  No atomics.
+// Warping: z-buffered forward splatting of RGB-D frames into other posed cameras (k_warp_splat, k_warp_resolve), further
+// down beside the reprojection whose projections it shares.
 #include "pn_rays.h"
 #include <math.h>
 
@@ -224,6 +226,135 @@ __global__ __launch_bounds__(kThreads) void k_reproject(int N, int C, int sk, in
     }
 }
 
+// ------------------------------------------------------------------------------------------------ depth-aware warping
+// z-buffered forward splatting of RGB-D frames (pn_warp_splat, pn_warp_resolve; formulas in include/panonerf_hip.h).
+// Splat: one thread per (source frame, source pixel) lifts its pixel to a world point once, then for every destination
+// (gridDim.y, as k_reproject's images) projects it and takes a 64-bit minimum of (rho bits, source index) over its
+// footprint: plain no-return global 64-bit vector atomics, keys unique, so the result is independent of their order.
+// Resolve: one thread per (destination, pixel) decodes the key and gathers.  No LDS, no scratch.
+
+// unit camera-space direction of the centre of pixel (i, j) (a fisheye's equidistant formula outside its circle too)
+__device__ __forceinline__ void unit_dir(int kind, int H, int W, const CamParams& p, int i, int j, float d[3]) {
+    dst_dir(kind, H, W, p, (float)j + 0.5f, (float)i + 0.5f, d);
+    if (kind == PN_CAM_PINHOLE || kind == PN_CAM_CUBE) normalize3(d);
+}
+
+// |u(y, j) - u(y + 1, j)| of the unit directions, rows as row_step_radius counts them: within a cube's face, the last
+// row reusing the one before
+__device__ __forceinline__ float row_step(int kind, int H, int W, const CamParams& p, int i, int j) {
+    const int rows = kind == PN_CAM_CUBE ? W : H;
+    const int top = kind == PN_CAM_CUBE ? (i / W) * W : 0;
+    const int y = i - top;
+    const int yy = y < rows - 1 ? y : rows - 2;
+    float a[3], n[3];
+    unit_dir(kind, H, W, p, top + yy, j, a);
+    unit_dir(kind, H, W, p, top + yy + 1, j, n);
+    return sqrtf(((a[0] - n[0]) * (a[0] - n[0]) + (a[1] - n[1]) * (a[1] - n[1])) + (a[2] - n[2]) * (a[2] - n[2]));
+}
+
+__device__ __forceinline__ float norm3(const float d[3]) { return sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]); }
+
+__global__ __launch_bounds__(kThreads) void k_warp_splat(int64_t n_src, int sk, int Hs, int Ws, CamParams sp,
+                                                         const float* depth, const float* src_c2ws, int D, int dk, int Hd,
+                                                         int Wd, CamParams dp, const float* dst_c2ws, int max_splat,
+                                                         float scale, unsigned long long* zbuf) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= n_src) return;
+    const float t = depth[idx];
+    if (!(t > 0.f && t < INFINITY)) return;
+    const int64_t hws = (int64_t)Hs * Ws;
+    const int pix = (int)(idx % hws);
+    const int i = pix / Ws, j = pix % Ws;
+    const float* m = src_c2ws + 16 * (idx / hws);
+    // the world direction of the pixel's ray, with the arithmetic of the ray kernels (pn_rays.h), and |dc|
+    float w[3], nd = 1.f;
+    if (sk == PN_CAM_PANO) {
+        const float theta = -((float)j + 0.5f) / (float)Ws * 2.f * kPi;
+        const float phi = ((float)i + 0.5f) / (float)Hs * kPi;
+        const float s_ = sinf(phi);
+        const float x = s_ * sinf(theta), y = cosf(phi), z = s_ * cosf(theta);
+        w[0] = x * m[0] + y * m[1] + z * m[2];
+        w[1] = x * m[4] + y * m[5] + z * m[6];
+        w[2] = x * m[8] + y * m[9] + z * m[10];
+    } else {
+        float c[3];
+        if (!dst_dir(sk, Hs, Ws, sp, (float)j + 0.5f, (float)i + 0.5f, c)) return;  // outside a fisheye's circle
+        if (sk == PN_CAM_CUBE) normalize3(c);
+        if (sk == PN_CAM_PINHOLE) nd = norm3(c);
+        rotate3(m, 4, c, w);
+    }
+    float X[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) X[k] = w[k] * t + m[4 * k + 3];
+    const float num = scale * ((t * nd) * row_step(sk, Hs, Ws, sp, i, j));
+    const int64_t hwd = (int64_t)Hd * Wd;
+    const int rows = dk == PN_CAM_CUBE ? Wd : Hd;
+    for (int d = blockIdx.y; d < D; d += gridDim.y) {
+        const float* md = dst_c2ws + 16 * (int64_t)d;
+        float v[3], e[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = X[k] - md[4 * k + 3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = (md[k] * v[0] + md[4 + k] * v[1]) + md[8 + k] * v[2];  // R_d^T v
+        const float rho = norm3(e);
+        if (!(rho > 0.f && rho < INFINITY)) continue;
+        float qx, qy;
+        int face;
+        if (!src_pos(dk, Hd, Wd, dp, e, qx, qy, face)) continue;
+        const int top = dk == PN_CAM_CUBE ? face * Wd : 0;
+        // the landing pixel, kept inside the image (a position on the last border lands in the last pixel)
+        int lx = (int)floorf(qx), ly = (int)floorf(qy);
+        lx = lx < 0 ? 0 : (lx > Wd - 1 ? Wd - 1 : lx);
+        ly = ly < 0 ? 0 : (ly > rows - 1 ? rows - 1 : ly);
+        const float size = num / (rho * row_step(dk, Hd, Wd, dp, top + ly, lx));
+        int k = 1;
+        if (size > 1.f) k = size >= (float)max_splat ? max_splat : (int)ceilf(size);
+        const float half = (float)(k - 1) * 0.5f;
+        const int x0 = (int)floorf(qx - half), y0 = (int)floorf(qy - half);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(rho) << 32) | (unsigned long long)(uint32_t)idx;
+        unsigned long long* zb = zbuf + (int64_t)d * hwd;
+        for (int b = 0; b < k; ++b) {
+            const int y = y0 + b;
+            if (y < 0 || y >= rows) continue;
+            for (int a = 0; a < k; ++a) {
+                int x = x0 + a;
+                if (dk == PN_CAM_PANO) x = ((x % Wd) + Wd) % Wd;
+                else if (x < 0 || x >= Wd) continue;
+                atomicMin(zb + (int64_t)(top + y) * Wd + x, key);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_warp_resolve(int64_t n_src, int C, int Hs, int Ws, int64_t n_dst, int dk, int Hd,
+                                                           int Wd, CamParams dp, const unsigned long long* zbuf,
+                                                           const float* image, int64_t ns, int64_t cs, int64_t ps, float fill,
+                                                           float* out, float* depth_out, int64_t* index, float* coverage) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= n_dst) return;
+    const int64_t hwd = (int64_t)Hd * Wd, hws = (int64_t)Hs * Ws;
+    const int64_t d = idx / hwd, pix = idx % hwd;
+    const unsigned long long key = zbuf[idx];
+    const int64_t src = (int64_t)(key & 0xffffffffull);
+    const bool hit = key != PN_WARP_EMPTY && src < n_src;  // a key no splat of these sources wrote reads as empty
+    float dep = NAN;
+    if (hit) {
+        dep = __uint_as_float((unsigned)(key >> 32));
+        if (dk == PN_CAM_PINHOLE) {
+            float c[3];
+            dst_dir(dk, Hd, Wd, dp, (float)(pix % Wd) + 0.5f, (float)(pix / Wd) + 0.5f, c);
+            dep = dep / norm3(c);
+        }
+    }
+    depth_out[idx] = dep;
+    index[idx] = hit ? src : -1;
+    coverage[idx] = hit ? 1.f : 0.f;
+    if (!out) return;
+    const float* px = hit ? image + (src / hws) * ns + (src % hws) * ps : nullptr;
+    float* o = out + d * C * hwd + pix;
+    for (int c = 0; c < C; ++c) o[(int64_t)c * hwd] = hit ? px[(int64_t)c * cs] : fill;
+}
+
 // minimum image size of a camera kind; false for an unknown kind
 bool min_size(int kind, int H, int W, bool& ok) {
     switch (kind) {
@@ -315,6 +446,49 @@ int pn_reproject(int N, int C, int src_kind, int Hs, int Ws, const float* src_pa
     const dim3 grid(nblk((int64_t)Hd * Wd, kThreads), (unsigned)(N < 65535 ? N : 65535));
     hipLaunchKernelGGL(k_reproject, grid, dim3(kThreads), 0, ST(stream), N, C, src_kind, Hs, Ws, sp, dst_kind, Hd, Wd, dp,
                        rot, samples, fill, image, image_stride, cs, ps, out, coverage);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_warp_splat(int S, int src_kind, int Hs, int Ws, const float* src_params_host, const float* depth,
+                  const float* src_c2ws, int D, int dst_kind, int Hd, int Wd, const float* dst_params_host,
+                  const float* dst_c2ws, int max_splat, float scale, uint64_t* zbuf, void* stream) {
+    bool oks = false, okd = false;
+    if (!min_size(src_kind, Hs, Ws, oks) || !min_size(dst_kind, Hd, Wd, okd)) return PN_ERR_UNSUPPORTED;
+    if (src_kind == PN_CAM_STEREO_PANO || dst_kind == PN_CAM_STEREO_PANO) return PN_ERR_UNSUPPORTED;  // not central
+    if (S <= 0 || D <= 0 || !oks || !okd || max_splat < 1 || max_splat > PN_WARP_MAX_SPLAT || !(scale > 0.f) ||
+        !(scale < INFINITY) || (int64_t)S * Hs * Ws >= ((int64_t)1 << 32) || (int64_t)D * Hd * Wd >= ((int64_t)1 << 31))
+        return PN_ERR_BAD_SHAPE;
+    if (!src_params_host || !dst_params_host || !depth || !src_c2ws || !dst_c2ws || !zbuf) return PN_ERR_NULL;
+    if (src_kind == PN_CAM_FISHEYE && !(src_params_host[0] > 0.f && src_params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    if (dst_kind == PN_CAM_FISHEYE && !(dst_params_host[0] > 0.f && dst_params_host[1] > 0.f)) return PN_ERR_BAD_SHAPE;
+    CamParams sp, dp;
+    for (int k = 0; k < PN_CAM_PARAMS; ++k) sp.v[k] = src_params_host[k], dp.v[k] = dst_params_host[k];
+    const int64_t n_src = (int64_t)S * Hs * Ws;
+    const dim3 grid(nblk(n_src, kThreads), (unsigned)(D < 65535 ? D : 65535));
+    hipLaunchKernelGGL(k_warp_splat, grid, dim3(kThreads), 0, ST(stream), n_src, src_kind, Hs, Ws, sp, depth, src_c2ws, D,
+                       dst_kind, Hd, Wd, dp, dst_c2ws, max_splat, scale, (unsigned long long*)zbuf);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_warp_resolve(int S, int C, int Hs, int Ws, int D, int dst_kind, int Hd, int Wd, const float* dst_params_host,
+                    const uint64_t* zbuf, const float* image, int64_t image_stride, int64_t cs, int64_t ps, float fill,
+                    float* out, float* depth_out, int64_t* index, float* coverage, void* stream) {
+    bool okd = false;
+    if (!min_size(dst_kind, Hd, Wd, okd)) return PN_ERR_UNSUPPORTED;
+    if (dst_kind == PN_CAM_STEREO_PANO) return PN_ERR_UNSUPPORTED;
+    if (S <= 0 || D <= 0 || Hs <= 0 || Ws <= 0 || !okd || (int64_t)S * Hs * Ws >= ((int64_t)1 << 32) ||
+        (int64_t)D * Hd * Wd >= ((int64_t)1 << 31) || ((image || out) && C <= 0))
+        return PN_ERR_BAD_SHAPE;
+    if (!dst_params_host || !zbuf || !depth_out || !index || !coverage || (image == nullptr) != (out == nullptr))
+        return PN_ERR_NULL;
+    CamParams dp;
+    for (int k = 0; k < PN_CAM_PARAMS; ++k) dp.v[k] = dst_params_host[k];
+    const int64_t n_dst = (int64_t)D * Hd * Wd;
+    hipLaunchKernelGGL(k_warp_resolve, dim3(nblk(n_dst, kThreads)), dim3(kThreads), 0, ST(stream), (int64_t)S * Hs * Ws, C, Hs,
+                       Ws, n_dst, dst_kind, Hd, Wd, dp, (const unsigned long long*)zbuf, image, image_stride, cs, ps, fill, out,
+                       depth_out, index, coverage);
     PN_CHECK_LAUNCH();
     return PN_OK;
 }

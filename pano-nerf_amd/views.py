@@ -1,5 +1,5 @@
 """Novel views of a trained model: cameras (pinhole, panorama, cube map, fisheye, stereo panorama), camera paths, viewable
-frames and reprojection of images between cameras.
+frames, reprojection of images between cameras and depth-aware warping of rendered frames to other poses.
 
 Pano-NeRF's models are trained on panoramas, but what a user renders from a trained model is a new view.  This module
 renders one (or a whole path of them) and turns the renderer's outputs into the uint8 images the reference's validation
@@ -27,6 +27,10 @@ tensors raise, there is no host fallback.  Cameras (``cameras.py``, re-exported 
     render_path(model, camera, poses, ...)      dict kind -> uint8 [n, H, W, 3] frames (or PNG / EXR files)
     render_stereo_pano(model, h, w, ipd, c2w, ...)  render_view's dict, the left eye stacked on the right: [1, C, 2 H, W]
     reproject(image, src_camera, dst_camera, ...)   (out [N, C, Hd, Wd], coverage [Hd, Wd]): resample between cameras
+    warp_view(image, depth, src_camera, src_c2w, dst_camera, dst_c2w, ...)   dict image / depth / index / coverage: RGB-D
+                                                frames seen from other poses (z-buffered forward splatting)
+    render_path_warped(model, camera, poses, key_every, ...)   render_path's frames, every key_every-th pose rendered and
+                                                the poses between warped from their two rendered neighbours
 
 Conventions (pixel directions, radii, frame bytes, the cube-map table, the inverse projections) are stated in
 include/panonerf_hip.h.
@@ -45,6 +49,8 @@ from .cameras import (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, Ster
 from .rays import Rays, CameraRig, PerspectiveRayPool, _stream  # noqa
 
 _MAX_SAMPLES = 16
+_MAX_SPLAT = 8  # PN_WARP_MAX_SPLAT
+_WARPED_KINDS = ("ldr", "hdr", "depth")
 
 _FRAME_KINDS = {"ldr": 0, "ldr_gt": 1, "depth": 2, "normal": 3, "albedo": 4}
 # render_view outputs -> the render_image names they fill
@@ -479,3 +485,179 @@ def reproject(image, src_camera, dst_camera, rotation=None, samples=1, fill=0.0)
         _lib.call("pn_reproject", N, C, sk, src.h, src.w, sp.ctypes.data, dk, dst.h, dst.w, dp.ctypes.data, r32.ctypes.data,
                   k, float(fill), x.data_ptr(), sn, sc, sw, out.data_ptr(), cov.data_ptr(), _stream(dev))
     return out, cov
+
+
+# ---------------------------------------------------------------------------------------------------------- warping
+def _poses(c2w, what):
+    """[n, 4, 4] float64 of one pose ([4, 4] or [3, 4]) or a stack of them (array, sequence or tensor)"""
+    if isinstance(c2w, torch.Tensor):
+        c2w = c2w.detach().cpu().numpy()
+    a = np.asarray(c2w, dtype=np.float64)
+    try:
+        return _c2w_stack(a, single=a.ndim == 2)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+
+
+def warp_view(image, depth, src_camera, src_c2w, dst_camera, dst_c2w, max_splat=4, splat_scale=1.0, fill=0.0):
+    """See S RGB-D frames of src_camera at the poses src_c2w from D other poses dst_c2w of dst_camera: every source pixel
+    is lifted to its world point, projected into each destination and splatted over its footprint there, a z-buffer
+    keeping the nearest point per destination pixel (pn_warp_splat, pn_warp_resolve; the formulas are in
+    include/panonerf_hip.h).  Six degrees of freedom at the cost of two small kernels, where render_view costs a full
+    render; what no source saw stays a hole.
+
+    image: [S, C, Hs, Ws] or [C, Hs, Ws] device tensor (any C; permuted views are read in place), or None.  depth:
+    [S, 1, Hs, Ws], [S, Hs, Ws] or [Hs, Ws], the distance t along the ray CameraRig.sample gives each pixel, i.e.
+    render_view's fine_dep as it is (for a pinhole that ray is not normalised, so t is not the Euclidean distance);
+    NaN, Inf, 0 and negative depths are no points.  src_c2w / dst_c2w: [S, 4, 4] / [D, 4, 4] (or [., 3, 4], or one pose).
+    Cameras: panorama, pinhole, cube map or fisheye on either side; a stereo-panorama camera raises ValueError.
+
+    -> dict: "image" [D, C, Hd, Wd] (absent when image is None; `fill` in holes), "depth" [D, 1, Hd, Wd] (t along the
+    destination camera's rays; NaN in holes), "index" [D, Hd, Wd] int64 (the source pixel s Hs Ws + i Ws + j each pixel
+    shows; -1 in holes), "coverage" [D, Hd, Wd] (1 where a point landed, 0 in holes).
+
+    A point covers k x k destination pixels, k = min(max_splat, max(1, ceil(splat_scale * its source pixel's angular size
+    seen from the destination, in destination pixels))): moving closer magnifies a surface, and with k = 1 the background
+    would show between its points.  max_splat in [1, 8].  The result does not depend on the order the points arrive in:
+    repeated calls give the same bits.  So render_view's dict plugs in: warp_view(out["fine_rgb"], out["fine_dep"], ...)."""
+    src, dst = _camera(src_camera), _camera(dst_camera)
+    if isinstance(src, StereoPanoCamera) or isinstance(dst, StereoPanoCamera):
+        raise ValueError("a stereo-panorama camera is not a central projection: it cannot be warped")
+    k = int(max_splat)
+    if k != max_splat or not 1 <= k <= _MAX_SPLAT:
+        raise ValueError(f"max_splat must be an integer in [1, {_MAX_SPLAT}]; got {max_splat!r}")
+    scale = float(splat_scale)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"splat_scale must be positive and finite; got {splat_scale!r}")
+    if not isinstance(depth, torch.Tensor) or depth.dim() not in (2, 3, 4) or (depth.dim() == 4 and depth.shape[1] != 1):
+        raise ValueError("depth must be a [S, 1, Hs, Ws], [S, Hs, Ws] or [Hs, Ws] tensor; got "
+                         f"{getattr(depth, 'shape', type(depth))}")
+    Hs, Ws = (int(v) for v in depth.shape[-2:])
+    if (Hs, Ws) != (src.h, src.w):
+        raise ValueError(f"depth is {Hs} x {Ws} but src_camera is {src.h} x {src.w}")
+    z = depth.detach().reshape(-1, Hs, Ws)
+    S = int(z.shape[0])
+    if S < 1:
+        raise ValueError("depth is empty")
+    x = None
+    if image is not None:
+        if not isinstance(image, torch.Tensor) or image.dim() not in (3, 4):
+            raise ValueError("image must be a [C, Hs, Ws] or [S, C, Hs, Ws] tensor or None; got "
+                             f"{getattr(image, 'shape', type(image))}")
+        x = image.detach()
+        if x.dim() == 3:
+            x = x[None]
+        if x.shape[1] < 1:
+            raise ValueError("image is empty")
+        if tuple(x.shape[2:]) != (Hs, Ws):
+            raise ValueError(f"image is {x.shape[2]} x {x.shape[3]} but src_camera is {src.h} x {src.w}")
+        if x.shape[0] != S:
+            raise ValueError(f"image holds {x.shape[0]} frames but depth {S}")
+    sc2w, dc2w = _poses(src_c2w, "src_c2w"), _poses(dst_c2w, "dst_c2w")
+    if sc2w.shape[0] != S:
+        raise ValueError(f"src_c2w holds {sc2w.shape[0]} poses but depth {S} frames")
+    D = int(dc2w.shape[0])
+    if S * Hs * Ws >= 1 << 32 or D * dst.h * dst.w >= 1 << 31:
+        raise ValueError("too many pixels: S Hs Ws must be below 2^32 and D Hd Wd below 2^31")
+    for t, what in ((z, "depth"), (x, "image")):
+        if t is not None and t.device.type != "cuda":
+            raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (the %s is on %s); there is no CPU fallback"
+                               % (what, t.device))
+    dev = z.device
+    if x is not None and x.device != dev:
+        raise ValueError(f"image is on {x.device} but depth on {dev}")
+    z = z.to(torch.float32).contiguous()
+    C, sn, sc, sw = 0, 0, 0, 0
+    if x is not None:
+        if x.dtype != torch.float32:
+            x = x.to(torch.float32)
+        sn, sc, sh, sw = x.stride()
+        if sh != Ws * sw or min(sn, sc, sw) < 0:  # rows are not evenly spaced pixels: read a copy
+            x = x.contiguous()
+            sn, sc, sh, sw = x.stride()
+        C = int(x.shape[1])
+    (sk, sp), (dk, dp) = _kind_params(src), _kind_params(dst)
+    Hd, Wd = dst.h, dst.w
+    with torch.no_grad(), torch.cuda.device(dev):
+        mats = np.concatenate([sc2w, dc2w]).astype(np.float32).reshape(S + D, 16)
+        mats = torch.from_numpy(mats).to(dev)  # one upload for both sets of poses
+        ms, md = mats[:S], mats[S:]
+        zbuf = torch.full((D, Hd, Wd), -1, dtype=torch.int64, device=dev)  # all ones: PN_WARP_EMPTY
+        out = torch.empty(D, C, Hd, Wd, dtype=torch.float32, device=dev) if x is not None else None
+        dep = torch.empty(D, 1, Hd, Wd, dtype=torch.float32, device=dev)
+        index = torch.empty(D, Hd, Wd, dtype=torch.int64, device=dev)
+        cov = torch.empty(D, Hd, Wd, dtype=torch.float32, device=dev)
+        st = _stream(dev)
+        _lib.call("pn_warp_splat", S, sk, Hs, Ws, sp.ctypes.data, z.data_ptr(), ms.data_ptr(), D, dk, Hd, Wd, dp.ctypes.data,
+                  md.data_ptr(), k, scale, zbuf.data_ptr(), st)
+        _lib.call("pn_warp_resolve", S, C, Hs, Ws, D, dk, Hd, Wd, dp.ctypes.data, zbuf.data_ptr(), _lib.ptr(x), sn, sc, sw,
+                  float(fill), _lib.ptr(out), dep.data_ptr(), index.data_ptr(), cov.data_ptr(), st)
+    res = {"depth": dep, "index": index, "coverage": cov}
+    if out is not None:
+        res["image"] = out
+    return res
+
+
+def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("ldr", "depth"), near=0.0, far=10.0,
+                       exposure=0.0, out_dir=None, chunk_rays=32768, max_splat=4, splat_scale=1.0, fill=0.0):
+    """render_path at interactive frame counts: poses 0, key_every, 2 key_every, ... and the last pose are rendered
+    (render_view); every pose between two rendered poses is warp_view of those two frames (S = 2) into it.  -> render_path's
+    dict of frames ("ldr" and "depth" through to_frame, "hdr" as fp32) plus "coverage" [n, H, W] fp32: 1 at a rendered
+    pose and where a warped frame shows a source pixel, 0 in its holes (disocclusions, which nothing inpaints: `fill` in
+    the colours, NaN in the depth - and a NaN depth anywhere makes to_frame's depth frame black, as upstream's hotmap).
+    A rendered pose's frame is the render itself, so key_every = 1 gives render_path's bytes.  kinds: "ldr", "hdr", "depth"
+    (what a warp carries; the others need the renderer).  With out_dir the frames go to files as render_path writes them
+    and only "coverage" is returned."""
+    from . import io_exr
+    camera, dev, _ = _setup(model, camera, chunk_rays)
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in _WARPED_KINDS]
+    if bad or not kinds:
+        raise ValueError(f"kinds must be a non-empty subset of {sorted(_WARPED_KINDS)}; got {bad[0] if bad else kinds!r}")
+    step = int(key_every)
+    if step != key_every or step < 1:
+        raise ValueError(f"key_every must be a positive integer; got {key_every!r}")
+    c2ws = _c2w_stack(poses)
+    n, H, W = c2ws.shape[0], camera.h, camera.w
+    keys = sorted(set(range(0, n, step)) | {n - 1})
+    frames = {"coverage": torch.empty(n, H, W, dtype=torch.float32, device=dev)}
+    if out_dir is None:
+        frames.update({k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev)
+                       for k in kinds})
+    else:
+        for k in kinds:
+            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+
+    def emit(i, rgb, dep, cov):
+        frames["coverage"][i].copy_(cov)
+        for k in kinds:
+            if k == "hdr":
+                frame = rgb[0].permute(1, 2, 0)
+            elif k == "ldr":
+                frame = to_frame(rgb, "ldr", near, far, exposure)
+            else:
+                frame = to_frame(dep, "depth", near, far)
+            if out_dir is None:
+                frames[k][i].copy_(frame)
+            elif k == "hdr":
+                io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
+            else:
+                io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
+
+    def render(i):
+        v = render_view(model, camera, c2ws[i], env_rays, ("rgb", "depth"), near, far, chunk_rays)
+        return v["fine_rgb"], v["fine_dep"]
+
+    one = torch.ones(H, W, dtype=torch.float32, device=dev)
+    prev = render(keys[0])
+    emit(keys[0], *prev, one)
+    for a, b in zip(keys[:-1], keys[1:]):
+        cur = render(b)
+        if b - a > 1:
+            w = warp_view(torch.cat([prev[0], cur[0]]), torch.cat([prev[1], cur[1]]), camera, c2ws[[a, b]], camera,
+                          c2ws[a + 1:b], max_splat, splat_scale, fill)
+            for f, i in enumerate(range(a + 1, b)):
+                emit(i, w["image"][f:f + 1], w["depth"][f:f + 1], w["coverage"][f])
+        emit(b, *cur, one)
+        prev = cur
+    return frames
