@@ -1,6 +1,7 @@
-// pn_objects.hip — virtual object insertion (gfx950): a brute-force ray / triangle tracer, the reference's surface
-// shading (Lambertian and microfacet, utils/surface_rendering.py:6-61, 129-203) with a light probe's pixels as the
-// lights, the differential-rendering shadow an inserted mesh casts on the scene, hit attributes and the composite.
+// pn_objects.hip — virtual object insertion (gfx950): the ray / triangle tracer and the differential-rendering shadow an
+// inserted mesh casts on the scene, each one kernel template over pn_tri.h's two finders (brute force, and a walk of
+// pn_bvh.hip's tree); the reference's surface shading (Lambertian and microfacet, utils/surface_rendering.py:6-61,
+// 129-203) with a light probe's pixels as the lights, hit attributes and the composite.
 // Conventions (edge rule, tie-break, direction of v, shadow definition) are stated in include/panonerf_hip.h.
 //
 // One ray / hit pixel / scene point per thread; what the threads of a workgroup share (triangles, probe pixels) goes
@@ -14,8 +15,7 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTile = 256;     // probe pixels staged per LDS tile
-constexpr int kTriTile = 256;  // triangles staged per LDS tile (3 float4 each: 12 KB)
+constexpr int kTile = 256;  // probe pixels staged per LDS tile
 constexpr int kMaxProbes = PN_OBJ_MAX_PROBES;
 
 struct Probes {
@@ -42,61 +42,41 @@ __global__ __launch_bounds__(kThreads) void k_tri_setup(int64_t F, int64_t V, co
     tris[f * 3 + 2] = e2;
 }
 
-// the ray / triangle test and the bounding-sphere test live in pn_tri.h: the BVH tracer (pn_bvh.hip) runs the same ones
-using pn_tri::mt_hit;
+using pn_tri::BruteFinder;
+using pn_tri::BvhFinder;
+using pn_tri::Hit;
 using pn_tri::reaches_sphere;
 
-__device__ __forceinline__ void stage_tris(float4* s_tri, const float4* tris, int64_t base, int cnt) {
-    for (int i = threadIdx.x; i < cnt * 3; i += kThreads) s_tri[i] = tris[base * 3 + i];
-}
-
-// closest hit of ray r with the F triangles, in face order: a later face replaces the best only when its t is smaller,
-// so equal t keeps the lower face index whatever the tile size.  any != 0: first hit found ends the ray's search.
-__global__ __launch_bounds__(kThreads) void k_trace(int64_t R, const float* origins, const float* dirs, int64_t F,
-                                                   const float4* tris, const float* t_max, const float* bs, int any,
-                                                   float* t_out, int32_t* face_out, float* bary_out, uint8_t* hit_out) {
-    __shared__ float4 s_tri[kTriTile * 3];
-    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+// closest hit of ray r with the F triangles, as Finder finds it; any != 0: whether there is one.  bs may be NULL, and a
+// finder that walks nodes is never given one (its root box does that job; pn_trace_mesh_bvh takes no sphere), so that
+// instance compiles the test out.
+template <class Finder>
+__global__ __launch_bounds__(Finder::kThreads) void k_trace(int64_t R, const float* origins, const float* dirs, int64_t F,
+                                                           const float4* tris, const float4* nodes, const float* t_max,
+                                                           int any, const float* bs, float* t_out, int32_t* face_out,
+                                                           float* bary_out, uint8_t* hit_out) {
+    __shared__ typename Finder::Shared s_find;
+    const int64_t r = (int64_t)blockIdx.x * Finder::kThreads + threadIdx.x;
     const bool live = r < R;
-    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, best = INFINITY;
+    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
+    Hit h{INFINITY, 0.f, 0.f, -1};
     if (live) {
         ox = origins[r * 3], oy = origins[r * 3 + 1], oz = origins[r * 3 + 2];
         dx = dirs[r * 3], dy = dirs[r * 3 + 1], dz = dirs[r * 3 + 2];
-        if (t_max) best = t_max[r];
+        if (t_max) h.best = t_max[r];
     }
-    bool search = live && (!bs || reaches_sphere(ox, oy, oz, dx, dy, dz, bs));
-    int32_t bf = -1;
-    float bu = 0.f, bv = 0.f;
-    if (__syncthreads_or(search)) {
-        for (int64_t base = 0; base < F; base += kTriTile) {
-            const int cnt = (int)((F - base) < kTriTile ? (F - base) : kTriTile);
-            stage_tris(s_tri, tris, base, cnt);
-            __syncthreads();
-            if (search) {
-                for (int j = 0; j < cnt; ++j) {
-                    float t, u, v;
-                    if (mt_hit(ox, oy, oz, dx, dy, dz, s_tri[j * 3], s_tri[j * 3 + 1], s_tri[j * 3 + 2], t, u, v) &&
-                        t < best) {
-                        best = t, bf = (int32_t)(base + j), bu = u, bv = v;
-                        if (any) {
-                            search = false;
-                            break;
-                        }
-                    }
-                }
-            }
-            if (!__syncthreads_or(search)) break;  // also the barrier before the next tile overwrites this one
-        }
-    }
+    Finder finder(F, tris, nodes, s_find);
+    const bool reach = Finder::kNodes || !bs || reaches_sphere(ox, oy, oz, dx, dy, dz, bs);
+    finder.find(live && reach, ox, oy, oz, dx, dy, dz, any != 0, h);
     if (!live) return;
     if (any) {
-        hit_out[r] = bf >= 0;
+        hit_out[r] = h.face >= 0;
         return;
     }
-    t_out[r] = bf >= 0 ? best : INFINITY;
-    face_out[r] = bf;
-    bary_out[r * 2] = bu;
-    bary_out[r * 2 + 1] = bv;
+    t_out[r] = h.face >= 0 ? h.best : INFINITY;
+    face_out[r] = h.face;
+    bary_out[r * 2] = h.u;
+    bary_out[r * 2 + 1] = h.v;
 }
 
 // reference shading of row r under the light sum_k w[r, k] L_k(pix) (fp64 throughout, pixels in order):
@@ -190,17 +170,18 @@ __global__ __launch_bounds__(kThreads) void k_shade(int64_t R, int K, int64_t HW
 }
 
 // ratio[r] = E(unoccluded) / E(all), E(S) = sum_{pix in S} mean_c L(pix) relu(n . l_pix) omega_pix; pix is occluded when
-// the ray from fl(x + fl(bias n)) along l_pix hits a triangle (t > 0).  One point per thread; the workgroup walks the
-// probe's pixels together, and for a pixel that some thread has to trace the triangles go through LDS (a tile that is
-// already there is not staged again).  Pixels below the point's horizon, pixels whose ray cannot reach the mesh's
-// bounding sphere and points whose hemisphere cannot see it never enter the triangle loop.
-__global__ __launch_bounds__(kThreads) void k_shadow(int64_t R, int64_t HW, Probes pr, const float* dirs,
-                                                    const float* omega, const float* points, const float* normals,
-                                                    float bias, int64_t F, const float4* tris, const float* bs,
-                                                    float* out) {
+// the ray from fl(x + fl(bias n)) along l_pix hits a triangle (t > 0), which is what Finder is asked.  One point per
+// thread; the workgroup walks the probe's pixels together, in order.  Pixels below the point's horizon, pixels whose ray
+// cannot reach the mesh's bounding sphere and points whose hemisphere cannot see it are never asked about.
+template <class Finder>
+__global__ __launch_bounds__(Finder::kThreads) void k_shadow(int64_t R, int64_t HW, Probes pr, const float* dirs,
+                                                            const float* omega, const float* points,
+                                                            const float* normals, float bias, int64_t F,
+                                                            const float4* tris, const float4* nodes, const float* bs,
+                                                            float* out) {
     __shared__ double4 s_dir[kTile];  // l, mean_c L omega
-    __shared__ float4 s_tri[kTriTile * 3];
-    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    __shared__ typename Finder::Shared s_find;
+    const int64_t r = (int64_t)blockIdx.x * Finder::kThreads + threadIdx.x;
     const bool live = r < R;
     float ox = 0.f, oy = 0.f, oz = 0.f;
     double nx = 0.0, ny = 0.0, nz = 0.0;
@@ -219,10 +200,10 @@ __global__ __launch_bounds__(kThreads) void k_shadow(int64_t R, int64_t HW, Prob
         sees = h + rr * sqrt(nx * nx + ny * ny + nz * nz) > 0.0;
     }
     double e_all = 0.0, e_un = 0.0;
-    int64_t staged = -1;  // base of the triangle tile in LDS (the same in every thread)
+    Finder finder(F, tris, nodes, s_find);
     for (int64_t base = 0; base < HW; base += kTile) {
         const int cnt = (int)((HW - base) < kTile ? (HW - base) : kTile);
-        for (int t = threadIdx.x; t < cnt; t += kThreads) {
+        for (int t = threadIdx.x; t < cnt; t += Finder::kThreads) {
             const int64_t pix = base + t;
             const float* xp = pr.x + pix * pr.ps;
             const double lm = ((double)xp[0] + (double)xp[pr.cs] + (double)xp[2 * pr.cs]) / 3.0;
@@ -234,31 +215,10 @@ __global__ __launch_bounds__(kThreads) void k_shadow(int64_t R, int64_t HW, Prob
             const double c = nx * l.x + ny * l.y + nz * l.z;
             const double wgt = c > 0.0 ? l.w * c : 0.0;
             e_all += wgt;
-            const float lx = (float)l.x, ly = (float)l.y, lz = (float)l.z;  // exact: the table is fp32
-            bool todo = sees && c > 0.0 && reaches_sphere(ox, oy, oz, l.x, l.y, l.z, bs);
-            bool occ = false;
-            if (__syncthreads_or(todo)) {
-                for (int64_t tb = 0; tb < F; tb += kTriTile) {
-                    const int tc = (int)((F - tb) < kTriTile ? (F - tb) : kTriTile);
-                    if (staged != tb) {  // every reader of the old tile is past the vote that ended its loop
-                        stage_tris(s_tri, tris, tb, tc);
-                        staged = tb;
-                        __syncthreads();
-                    }
-                    if (todo) {
-                        for (int j = 0; j < tc; ++j) {
-                            float tt, u, v;
-                            if (mt_hit(ox, oy, oz, lx, ly, lz, s_tri[j * 3], s_tri[j * 3 + 1], s_tri[j * 3 + 2], tt, u,
-                                       v)) {
-                                occ = true, todo = false;
-                                break;
-                            }
-                        }
-                    }
-                    if (!__syncthreads_or(todo)) break;
-                }
-            }
-            if (!occ) e_un += wgt;
+            Hit h{INFINITY, 0.f, 0.f, -1};
+            finder.find(sees && c > 0.0 && reaches_sphere(ox, oy, oz, l.x, l.y, l.z, bs), ox, oy, oz, (float)l.x,
+                        (float)l.y, (float)l.z, true, h);  // (float) is exact: the table is fp32
+            if (h.face < 0) e_un += wgt;
         }
         __syncthreads();
     }
@@ -392,8 +352,40 @@ __global__ __launch_bounds__(kThreads) void k_object_composite(int64_t R, const 
     depth[r] = m ? t[r] : scene_dep[r];
 }
 
-bool rows_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31) * kThreads / 2; }
+bool rows_ok(int64_t n, int threads = kThreads) { return n >= 0 && n < ((int64_t)1 << 31) * threads / 2; }
 bool probe_ok(int H, int W) { return H >= 2 && W >= 2 && (int64_t)H * W < ((int64_t)1 << 30); }
+
+// the checks and the launch behind pn_trace_mesh and pn_trace_mesh_bvh (nodes: only a finder that walks them wants them)
+template <class Finder>
+int trace_mesh(int64_t R, const float* origins, const float* directions, int64_t F, const float* tris, const float* nodes,
+               const float* t_max, const float* bsphere, int any_hit, float* t, int32_t* face, float* bary, uint8_t* hit,
+               void* stream) {
+    if (!rows_ok(R, Finder::kThreads) || F <= 0 || F >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
+    if (R == 0) return PN_OK;
+    if (!origins || !directions || !tris || (Finder::kNodes && !nodes)) return PN_ERR_NULL;
+    if (any_hit ? !hit : (!t || !face || !bary)) return PN_ERR_NULL;
+    hipLaunchKernelGGL(k_trace<Finder>, dim3(nblk(R, Finder::kThreads)), dim3(Finder::kThreads), 0, ST(stream), R, origins,
+                       directions, F, (const float4*)tris, (const float4*)nodes, t_max, any_hit, bsphere, t, face, bary,
+                       hit);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+// the same for pn_shadow_ratio and pn_shadow_ratio_bvh
+template <class Finder>
+int shadow_ratio(int64_t R, int H, int W, const float* x, int64_t cs, int64_t ps, const float* dirs, const float* omega,
+                 const float* points, const float* normals, float bias, int64_t F, const float* tris, const float* nodes,
+                 const float* bsphere, float* out, void* stream) {
+    if (!rows_ok(R, Finder::kThreads) || F < 0 || F >= ((int64_t)1 << 31) || !probe_ok(H, W)) return PN_ERR_BAD_SHAPE;
+    if (R == 0) return PN_OK;
+    if (!x || !dirs || !omega || !points || !normals || !out) return PN_ERR_NULL;
+    if (F > 0 && (!tris || !bsphere || (Finder::kNodes && !nodes))) return PN_ERR_NULL;
+    hipLaunchKernelGGL(k_shadow<Finder>, dim3(nblk(R, Finder::kThreads)), dim3(Finder::kThreads), 0, ST(stream), R,
+                       (int64_t)H * W, Probes{x, 0, cs, ps}, dirs, omega, points, normals, bias, F, (const float4*)tris,
+                       (const float4*)nodes, bsphere, out);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
 
 }  // namespace
 
@@ -412,14 +404,15 @@ int pn_tri_setup(int64_t F, int64_t V, const float* vertices, const int32_t* fac
 int pn_trace_mesh(int64_t R, const float* origins, const float* directions, int64_t F, const float* tris,
                   const float* t_max, const float* bsphere, int any_hit, float* t, int32_t* face, float* bary,
                   uint8_t* hit, void* stream) {
-    if (!rows_ok(R) || F <= 0 || F >= ((int64_t)1 << 31)) return PN_ERR_BAD_SHAPE;
-    if (R == 0) return PN_OK;
-    if (!origins || !directions || !tris) return PN_ERR_NULL;
-    if (any_hit ? !hit : (!t || !face || !bary)) return PN_ERR_NULL;
-    hipLaunchKernelGGL(k_trace, dim3(nblk(R, kThreads)), dim3(kThreads), 0, ST(stream), R, origins, directions, F,
-                       (const float4*)tris, t_max, bsphere, any_hit, t, face, bary, hit);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
+    return trace_mesh<BruteFinder>(R, origins, directions, F, tris, nullptr, t_max, bsphere, any_hit, t, face, bary, hit,
+                                   stream);
+}
+
+int pn_trace_mesh_bvh(int64_t R, const float* origins, const float* directions, int64_t F, const float* tris,
+                      const float* nodes, const float* t_max, int any_hit, float* t, int32_t* face, float* bary,
+                      uint8_t* hit, void* stream) {
+    return trace_mesh<BvhFinder>(R, origins, directions, F, tris, nodes, t_max, nullptr, any_hit, t, face, bary, hit,
+                                 stream);
 }
 
 int pn_shade(int64_t R, int K, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
@@ -440,14 +433,15 @@ int pn_shade(int64_t R, int K, int H, int W, const float* x, int64_t probe_strid
 int pn_shadow_ratio(int64_t R, int H, int W, const float* x, int64_t cs, int64_t ps, const float* dirs,
                     const float* omega, const float* points, const float* normals, float bias, int64_t F,
                     const float* tris, const float* bsphere, float* out, void* stream) {
-    if (!rows_ok(R) || F < 0 || F >= ((int64_t)1 << 31) || !probe_ok(H, W)) return PN_ERR_BAD_SHAPE;
-    if (R == 0) return PN_OK;
-    if (!x || !dirs || !omega || !points || !normals || !out) return PN_ERR_NULL;
-    if (F > 0 && (!tris || !bsphere)) return PN_ERR_NULL;
-    hipLaunchKernelGGL(k_shadow, dim3(nblk(R, kThreads)), dim3(kThreads), 0, ST(stream), R, (int64_t)H * W,
-                       Probes{x, 0, cs, ps}, dirs, omega, points, normals, bias, F, (const float4*)tris, bsphere, out);
-    PN_CHECK_LAUNCH();
-    return PN_OK;
+    return shadow_ratio<BruteFinder>(R, H, W, x, cs, ps, dirs, omega, points, normals, bias, F, tris, nullptr, bsphere,
+                                     out, stream);
+}
+
+int pn_shadow_ratio_bvh(int64_t R, int H, int W, const float* x, int64_t cs, int64_t ps, const float* dirs,
+                        const float* omega, const float* points, const float* normals, float bias, int64_t F,
+                        const float* tris, const float* nodes, const float* bsphere, float* out, void* stream) {
+    return shadow_ratio<BvhFinder>(R, H, W, x, cs, ps, dirs, omega, points, normals, bias, F, tris, nodes, bsphere, out,
+                                   stream);
 }
 
 int pn_object_hits(int64_t R, const float* origins, const float* directions, const float* t, const int32_t* face,

@@ -1,5 +1,13 @@
-// pn_tri.h — the ray / triangle test and the bounding-sphere test shared by the brute-force tracer (pn_objects.hip) and
-// the BVH tracer (pn_bvh.hip): one definition, the same bits on both paths.
+// pn_tri.h — what a mesh tracer asks of the triangles (gfx950): the ray / triangle test, the bounding-sphere test and the
+// two finders behind pn_objects.hip's k_trace<Finder> and k_shadow<Finder>, brute force through LDS tiles and a walk of
+// pn_bvh.hip's tree.  One definition of each: both paths run the same test on the same rows.
+//
+// A finder is built once per thread from (F, tris, nodes, its Shared block in LDS) and asked with
+//   find(ask, ox, oy, oz, dx, dy, dz, any, h)
+// by EVERY thread of the workgroup in uniform control flow (the brute-force finder holds barriers); ask = this thread has
+// a ray.  h.best comes in as the ray's t_max (or +inf) and h.face as -1; an accepted hit leaves (best, u, v, face) in h.
+// any: the first hit found ends the ray's search, and of h only face means anything.  kThreads is the workgroup size a
+// finder is written for.
 #pragma once
 #include "pn_common.h"
 #include <math.h>
@@ -38,5 +46,193 @@ __device__ __forceinline__ bool reaches_sphere(double ox, double oy, double oz, 
     const double b = mx * dx + my * dy + mz * dz, dd = dx * dx + dy * dy + dz * dz;
     return b > 0.0 && mm * dd - b * b <= r2 * dd;
 }
+
+struct Hit {
+    float best, u, v;  // best starts at t_max (or +inf)
+    int32_t face;      // -1: none held
+};
+
+// ---------------------------------------------------------------------------------------------------------- brute force
+// Every triangle in face order, streamed through LDS in tiles of kTriTile (3 float4 each: 12 KB): a later face replaces
+// the best only when its t is smaller, so equal t keeps the lower face index whatever the tile size.  The tile loop ends
+// when a vote finds no thread still searching.  A tile that is already in LDS is not staged again: `staged` survives from
+// one question to the next (k_shadow asks once per probe pixel, and a mesh of one tile is loaded once).
+struct BruteFinder {
+    static constexpr int kThreads = 256;
+    static constexpr int kTriTile = 256;
+    static constexpr bool kNodes = false;
+    struct Shared {
+        float4 tri[kTriTile * 3];
+    };
+    int64_t F;
+    const float4* tris;
+    float4* s_tri;
+    int64_t staged = -1;  // base of the triangle tile in LDS (the same in every thread)
+
+    __device__ __forceinline__ BruteFinder(int64_t F, const float4* tris, const float4*, Shared& s)
+        : F(F), tris(tris), s_tri(s.tri) {}
+
+    __device__ __forceinline__ void find(bool ask, float ox, float oy, float oz, float dx, float dy, float dz, bool any,
+                                         Hit& h) {
+        if (!__syncthreads_or(ask)) return;
+        for (int64_t base = 0; base < F; base += kTriTile) {
+            const int cnt = (int)((F - base) < kTriTile ? (F - base) : kTriTile);
+            if (staged != base) {  // every reader of the old tile is past the vote that ended its loop
+                for (int i = threadIdx.x; i < cnt * 3; i += kThreads) s_tri[i] = tris[base * 3 + i];
+                staged = base;
+                __syncthreads();
+            }
+            if (ask) {
+                for (int j = 0; j < cnt; ++j) {
+                    float t, u, v;
+                    if (mt_hit(ox, oy, oz, dx, dy, dz, s_tri[j * 3], s_tri[j * 3 + 1], s_tri[j * 3 + 2], t, u, v) &&
+                        t < h.best) {
+                        h.face = (int32_t)(base + j);
+                        if (any) {  // best stays what it was: under k_shadow's +inf the compare above folds away
+                            ask = false;
+                            break;
+                        }
+                        h.best = t, h.u = u, h.v = v;
+                    }
+                }
+            }
+            if (!__syncthreads_or(ask)) break;  // also the barrier before the next tile overwrites this one
+        }
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------ BVH walk
+// The contract (the box test, the candidate rule, why the tree cannot matter, the node layout and the depth bound) is
+// stated in include/panonerf_hip.h.  One ray per thread, near child first, the far child pushed on a stack in LDS laid out
+// [depth][thread] - lane l always touches bank l % 32, whatever its depth, so a wave's accesses never conflict - sized by
+// the depth bound: 94 x 64 threads x 4 B = 24 064 B per workgroup, one wave.  No scratch.  Neighbouring threads ask about
+// neighbouring rays (or the same direction from neighbouring points), so a wave's walks stay close.
+constexpr int kDepth = PN_BVH_MAX_DEPTH;                // stack entries per thread
+constexpr float kShrink = 1.f - 4.76837158203125e-07f;  // 1 - 2^-21
+constexpr float kGrow = 1.f + 4.76837158203125e-07f;    // 1 + 2^-21
+
+struct Ray {
+    float ox, oy, oz, dx, dy, dz, ix, iy, iz;
+    bool sx, sy, sz;  // the axis is a slab: 1 / d is not finite
+    bool ok;          // every component of o and d is finite
+};
+
+__device__ __forceinline__ Ray make_ray(float ox, float oy, float oz, float dx, float dy, float dz) {
+    Ray r;
+    r.ox = ox, r.oy = oy, r.oz = oz, r.dx = dx, r.dy = dy, r.dz = dz;
+    r.ok = isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(dx) && isfinite(dy) && isfinite(dz);
+    r.ix = 1.f / dx, r.iy = 1.f / dy, r.iz = 1.f / dz;
+    r.sx = !(fabsf(r.ix) < INFINITY), r.sy = !(fabsf(r.iy) < INFINITY), r.sz = !(fabsf(r.iz) < INFINITY);
+    return r;
+}
+
+// one axis of the box test: false when the axis alone rules the box out
+__device__ __forceinline__ bool axis(float lo, float hi, float o, float inv, bool slab, float& tn, float& tf) {
+    if (slab) return lo <= o && o <= hi;
+    const float a = (lo - o) * inv, b = (hi - o) * inv;
+    tn = fmaxf(tn, fminf(a, b));
+    tf = fminf(tf, fmaxf(a, b));
+    return true;
+}
+
+// Does the ray pass the box [lo, hi], and from which tn on?  (header: "Box test".)
+// Monotone in the box: let box P hold box C (lo_P <= lo_C <= hi_C <= hi_P per axis, which exact min / max unions give).
+//   * inv finite: x -> fl(x - o) and x -> fl(x inv) are monotone (rounding is), the second rising for inv > 0 and falling
+//     for inv < 0, so for inv > 0: a_P <= a_C <= b_C <= b_P, for inv < 0 the mirror image; either way
+//     min(a, b)_P <= min(a, b)_C and max(a, b)_P >= max(a, b)_C.  With o and d finite, inv finite and non-zero and lo <= hi,
+//     neither a nor b is NaN (no 0 x inf, no inf - inf), so min / max never drop an operand.
+//   * slab (d == 0 or 1 / d overflows): lo_C <= o <= hi_C implies lo_P <= o <= hi_P, and near = -inf, far = +inf leave tn
+//     and tf alone: P passes the axis whenever C does.
+//   * tn = max of the nears, tf = min of the fars: monotone in each.
+//   * the outward rounding x -> fl(x c), c = 1 -+ 2^-21 chosen by the sign of x, is monotone on each side of 0, maps
+//     x <= 0 to <= 0 and x > 0 to >= 0, hence monotone overall; -inf and +inf stay.
+// So tn_P <= tn_C and tf_P >= tf_C, and when C is passed (tn_C <= tf_C, tf_C >= 0) so is P.
+__device__ __forceinline__ bool box_pass(const Ray& r, float lx, float ly, float lz, float hx, float hy, float hz, float& tn) {
+    if (!r.ok || !(lx <= hx)) return false;  // a ray that is not finite; the empty box
+    float n = -INFINITY, f = INFINITY;
+    if (!axis(lx, hx, r.ox, r.ix, r.sx, n, f) || !axis(ly, hy, r.oy, r.iy, r.sy, n, f) ||
+        !axis(lz, hz, r.oz, r.iz, r.sz, n, f))
+        return false;
+    n = n > 0.f ? n * kShrink : n * kGrow;
+    f = f > 0.f ? f * kGrow : f * kShrink;
+    tn = n;
+    return n <= f && f >= 0.f;
+}
+
+struct BvhFinder {
+    static constexpr int kThreads = 64;  // one wave per workgroup (the LDS stack is per thread)
+    static constexpr bool kNodes = true;
+    struct Shared {
+        int stack[kDepth * kThreads];
+    };
+    int64_t F;
+    const float4 *tris, *nodes;
+    int* stack;  // this thread's column, stride kThreads
+
+    __device__ __forceinline__ BvhFinder(int64_t F, const float4* tris, const float4* nodes, Shared& s)
+        : F(F), tris(tris), nodes(nodes), stack(s.stack + threadIdx.x) {}
+
+    // leaf of face f, whose padded box the ray passes from tn on: the candidate rule, then the replacement rule
+    __device__ __forceinline__ void leaf(const Ray& r, int32_t f, float tn, Hit& h) const {
+        if (f < 0 || f >= F) return;  // PN_BVH_NONE, or a row this library did not write
+        float t, u, v;
+        if (!mt_hit(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, tris[(int64_t)f * 3], tris[(int64_t)f * 3 + 1],
+                    tris[(int64_t)f * 3 + 2], t, u, v))
+            return;
+        if (!(tn <= t)) return;
+        if (t < h.best || (t == h.best && h.face >= 0 && f < h.face)) h.best = t, h.face = f, h.u = u, h.v = v;
+    }
+
+    // Walks the tree from row 0.  A node is skipped only when the ray does not pass its box or tn > best; the near child
+    // is entered first and the far one pushed.  Every internal node is entered at most once, so F iterations always
+    // suffice: the bound also ends the walk over a buffer that is not a tree.
+    template <bool kAny>
+    __device__ __forceinline__ void walk(const Ray& r, Hit& h) const {
+        const int64_t rows = F > 1 ? F - 1 : 1;
+        int32_t cur = 0;
+        int sp = 0;
+        for (int64_t it = 0; it < F; ++it) {
+            const float4 a = nodes[(int64_t)cur * 4], b = nodes[(int64_t)cur * 4 + 1], c = nodes[(int64_t)cur * 4 + 2],
+                         e = nodes[(int64_t)cur * 4 + 3];
+            const int32_t lref = __float_as_int(a.w), rref = __float_as_int(b.w);
+            float tl = 0.f, tr = 0.f;
+            bool hl = box_pass(r, a.x, a.y, a.z, b.x, b.y, b.z, tl) && !(tl > h.best);
+            bool hr = box_pass(r, c.x, c.y, c.z, e.x, e.y, e.z, tr) && !(tr > h.best);
+            if (hl && lref < 0) {
+                leaf(r, ~lref, tl, h);
+                hl = false;
+            }
+            if (hr && rref < 0) {
+                leaf(r, ~rref, tr, h);
+                hr = false;
+            }
+            if (kAny && h.face >= 0) return;
+            hl = hl && lref < rows && !(tl > h.best);
+            hr = hr && rref < rows && !(tr > h.best);
+            if (hl && hr) {
+                const bool left_first = tl <= tr;
+                if (sp < kDepth) stack[sp++ * kThreads] = left_first ? rref : lref;  // sp < kDepth always: the depth bound
+                cur = left_first ? lref : rref;
+            } else if (hl) {
+                cur = lref;
+            } else if (hr) {
+                cur = rref;
+            } else {
+                if (sp == 0) return;
+                cur = stack[--sp * kThreads];
+            }
+        }
+    }
+
+    __device__ __forceinline__ void find(bool ask, float ox, float oy, float oz, float dx, float dy, float dz, bool any,
+                                         Hit& h) const {
+        if (!ask) return;
+        const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
+        if (any)
+            walk<true>(r, h);
+        else
+            walk<false>(r, h);
+    }
+};
 
 }  // namespace pn_tri

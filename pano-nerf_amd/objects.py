@@ -1,8 +1,9 @@
 """Virtual object insertion: a synthetic mesh placed into the captured scene, lit by the light that arrives at its
 position, hidden by what stands in front of it, and darkening the scene under it.
 
-Everything runs on the HIP device through the kernels of ``libpanonerf_hip.so`` (``pn_objects.hip`` plus the renderer's
-and the lighting module's entry points), under ``torch.no_grad()`` on the current stream.  CPU tensors raise: there is no
+Everything runs on the HIP device through the kernels of ``libpanonerf_hip.so`` (``pn_objects.hip``, whose one tracer and
+one shadow kernel ask ``pn_tri.h``'s finders - brute force, or a walk of ``pn_bvh.hip``'s tree - plus the renderer's and
+the lighting module's entry points), under ``torch.no_grad()`` on the current stream.  CPU tensors raise: there is no
 host fallback.  No gradients flow through any of it.
 
     trace_mesh(origins, directions, vertices, faces, t_max, any_hit)   closest hit (t, face, bary) of rays with a mesh
@@ -97,52 +98,34 @@ def _mesh(vertices, faces):
     return vertices.detach().to(torch.float32).contiguous(), faces.detach().to(torch.int32).contiguous()
 
 
-def _triangles(v, f, dev):
-    """(tris [F, 12], bsphere [4]) of a mesh with F > 0: the tracer's per-triangle rows and a sphere around the vertices."""
-    F = int(f.shape[0])
-    tris = torch.empty(F, 12, dtype=torch.float32, device=dev)
-    _lib.call("pn_tri_setup", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tris.data_ptr(), _stream(dev))
-    lo, hi = v.amin(0), v.amax(0)
-    centre = (lo + hi) * 0.5
-    radius = (v - centre).norm(dim=1).amax().reshape(1)
-    return tris, torch.cat([centre, radius]).contiguous()
-
-
-class MeshBVH:
-    """A linear BVH over the triangles of one mesh, on the device: tris [F, 12] (the tracer's rows), nodes
-    [max(F - 1, 1), 16] (both children's boxes and references per row; include/panonerf_hip.h), bsphere [4], F and the
-    device.  Build it with MeshBVH.build; hand it to trace_mesh / shadow_ratio / insert_object as `accel`."""
+class _PreparedMesh:
+    """What a tracer launch reads of one mesh, on the device: tris [F, 12] (pn_tri_setup's rows), bsphere [4] (a sphere
+    around the vertices), F and the device; F = 0 has no tensors.  As it is, it traces by brute force (nodes stays None):
+    accel=None makes one per call.  With a tree it is a MeshBVH."""
 
     def __init__(self, tris, nodes, bsphere, F, device):
         self.tris, self.nodes, self.bsphere, self.F, self.device = tris, nodes, bsphere, F, device
+
+    def _entry(self, name):
+        """(the entry point that traces this mesh, the arguments it takes after tris)"""
+        return name, ()
+
+
+class MeshBVH(_PreparedMesh):
+    """A linear BVH over the triangles of one mesh, on the device: tris [F, 12] (the tracer's rows), nodes
+    [max(F - 1, 1), 16] (both children's boxes and references per row; include/panonerf_hip.h), bsphere [4], F and the
+    device.  Build it with MeshBVH.build; hand it to trace_mesh / shadow_ratio / insert_object as `accel`."""
 
     @classmethod
     def build(cls, vertices, faces):
         """Padded triangle boxes -> 63-bit Morton keys -> torch.sort (stable) -> Karras' radix tree -> bottom-up refit, all
         launched on the current stream without a host synchronisation.  Two builds of a mesh give the same bytes."""
         dev = _cuda(("vertices", vertices), ("faces", faces))
-        v, f = _mesh(vertices, faces)
-        F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
-        if not F:
-            return cls(None, None, None, 0, dev)
         with torch.no_grad(), torch.cuda.device(dev):
-            st = _stream(dev)
-            tris, bs = _triangles(v, f, dev)
-            tbox = torch.empty(F, 2, 4, dtype=torch.float32, device=dev)
-            _lib.call("pn_bvh_boxes", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tbox.data_ptr(), st)
-            nodes = torch.empty(max(F - 1, 1), 16, dtype=torch.float32, device=dev)
-            if F == 1:
-                _lib.call("pn_bvh_tree", F, None, None, tbox.data_ptr(), nodes.data_ptr(), None, None, st)
-                return cls(tris, nodes, bs, F, dev)
-            scene = torch.cat([tbox[:, 0, :3].amin(0), tbox[:, 1, :3].amax(0)]).contiguous()
-            keys = torch.empty(F, dtype=torch.int64, device=dev)
-            _lib.call("pn_bvh_keys", F, tbox.data_ptr(), scene.data_ptr(), keys.data_ptr(), st)
-            skeys, order = torch.sort(keys, stable=True)
-            leaf_parent = torch.empty(F, dtype=torch.int32, device=dev)
-            counters = torch.empty(F - 1, dtype=torch.int32, device=dev)
-            _lib.call("pn_bvh_tree", F, skeys.data_ptr(), order.data_ptr(), tbox.data_ptr(), nodes.data_ptr(),
-                      leaf_parent.data_ptr(), counters.data_ptr(), st)
-        return cls(tris, nodes, bs, F, dev)
+            return _prepare(*_mesh(vertices, faces), dev, "bvh")
+
+    def _entry(self, name):
+        return (name + "_bvh", (self.nodes.data_ptr(),)) if self.F else (name, ())  # nothing to hit: no tree either
 
 
 def _check_accel(accel):
@@ -152,14 +135,43 @@ def _check_accel(accel):
     raise ValueError(f'accel must be None (brute force), "bvh" or a MeshBVH; got {accel!r}')
 
 
-def _bvh_for(accel, v, f, F, dev):
-    """The MeshBVH a call walks: the one handed in or one built for this call.  Of a tree handed in only the face count
-    and the device are compared with the mesh: keeping the two in step is the caller's business (VirtualObject.bvh() does)."""
+def _prepare(v, f, dev, accel):
+    """The mesh a call launches on, of the tensors _mesh returns: the tracer's rows and a sphere around the vertices, made
+    for this call (accel=None: brute force), with a tree built for it ("bvh"), or the MeshBVH handed in.  Of a tree handed
+    in only the face count and the device are compared with the mesh: keeping the two in step is the caller's business
+    (VirtualObject.bvh() does).  Launches on the current stream."""
+    F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
+    cls = _PreparedMesh if accel is None else MeshBVH
+    if not F:
+        return cls(None, None, None, 0, dev)
     if isinstance(accel, MeshBVH):
-        if accel.F != F or (F and accel.device != dev):
+        if accel.F != F or accel.device != dev:
             raise ValueError(f"accel is a MeshBVH of {accel.F} faces on {accel.device}; the mesh has {F} on {dev}")
         return accel
-    return MeshBVH.build(v, f)
+    st = _stream(dev)
+    tris = torch.empty(F, 12, dtype=torch.float32, device=dev)
+    _lib.call("pn_tri_setup", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tris.data_ptr(), st)
+    lo, hi = v.amin(0), v.amax(0)
+    centre = (lo + hi) * 0.5
+    radius = (v - centre).norm(dim=1).amax().reshape(1)
+    bsphere = torch.cat([centre, radius]).contiguous()
+    if accel is None:
+        return cls(tris, None, bsphere, F, dev)
+    tbox = torch.empty(F, 2, 4, dtype=torch.float32, device=dev)
+    _lib.call("pn_bvh_boxes", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tbox.data_ptr(), st)
+    nodes = torch.empty(max(F - 1, 1), 16, dtype=torch.float32, device=dev)
+    if F == 1:
+        _lib.call("pn_bvh_tree", F, None, None, tbox.data_ptr(), nodes.data_ptr(), None, None, st)
+        return cls(tris, nodes, bsphere, F, dev)
+    scene = torch.cat([tbox[:, 0, :3].amin(0), tbox[:, 1, :3].amax(0)]).contiguous()
+    keys = torch.empty(F, dtype=torch.int64, device=dev)
+    _lib.call("pn_bvh_keys", F, tbox.data_ptr(), scene.data_ptr(), keys.data_ptr(), st)
+    skeys, order = torch.sort(keys, stable=True)
+    leaf_parent = torch.empty(F, dtype=torch.int32, device=dev)
+    counters = torch.empty(F - 1, dtype=torch.int32, device=dev)
+    _lib.call("pn_bvh_tree", F, skeys.data_ptr(), order.data_ptr(), tbox.data_ptr(), nodes.data_ptr(),
+              leaf_parent.data_ptr(), counters.data_ptr(), st)
+    return cls(tris, nodes, bsphere, F, dev)
 
 
 def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False, accel=None):
@@ -180,7 +192,6 @@ def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False, 
         if t_max.numel() != R:
             raise ValueError(f"t_max must hold {R} values; got {tuple(t_max.shape)}")
         tm = t_max.detach().to(torch.float32).reshape(R).contiguous()
-    F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
     with torch.no_grad(), torch.cuda.device(dev):
         if any_hit:
             hit = torch.zeros(R, dtype=torch.uint8, device=dev)
@@ -190,14 +201,11 @@ def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False, 
             t = torch.full((R,), float("inf"), dtype=torch.float32, device=dev)
             face = torch.full((R,), -1, dtype=torch.int32, device=dev)
             bary = torch.zeros(R, 2, dtype=torch.float32, device=dev)
-        if R and F and accel is not None:
-            bvh = _bvh_for(accel, v, f, F, dev)
-            _lib.call("pn_trace_mesh_bvh", R, o.data_ptr(), d.data_ptr(), F, bvh.tris.data_ptr(), bvh.nodes.data_ptr(),
-                      _lib.ptr(tm), int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit),
-                      _stream(dev))
-        elif R and F:
-            tris, bs = _triangles(v, f, dev)
-            _lib.call("pn_trace_mesh", R, o.data_ptr(), d.data_ptr(), F, tris.data_ptr(), _lib.ptr(tm), bs.data_ptr(),
+        mesh = _prepare(v, f, dev, accel) if R else None
+        if R and mesh.F:
+            name, nodes = mesh._entry("pn_trace_mesh")
+            sphere = () if nodes else (mesh.bsphere.data_ptr(),)  # a walk has its boxes: pn_trace_mesh_bvh takes no sphere
+            _lib.call(name, R, o.data_ptr(), d.data_ptr(), mesh.F, mesh.tris.data_ptr(), *nodes, _lib.ptr(tm), *sphere,
                       int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit), _stream(dev))
     return hit.bool() if any_hit else (t, face, bary)
 
@@ -263,19 +271,14 @@ def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3, accel=None)
     R = int(p.shape[0])
     n = _rows3(normals, "normals", R)
     v, f = _mesh(vertices, faces)
-    F = int(f.shape[0]) if v.shape[0] else 0  # no vertices: nothing to hit
     with torch.no_grad(), torch.cuda.device(dev):
         dirs, omega = _table(H, W, dev)
         out = torch.empty(R, dtype=torch.float32, device=dev)
-        if R and F and accel is not None:
-            bvh = _bvh_for(accel, v, f, F, dev)
-            _lib.call("pn_shadow_ratio_bvh", R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(),
-                      p.data_ptr(), n.data_ptr(), float(bias), F, bvh.tris.data_ptr(), bvh.nodes.data_ptr(),
-                      bvh.bsphere.data_ptr(), out.data_ptr(), _stream(dev))
-        elif R:
-            tris, bs = _triangles(v, f, dev) if F else (None, None)
-            _lib.call("pn_shadow_ratio", R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(), p.data_ptr(),
-                      n.data_ptr(), float(bias), F, _lib.ptr(tris), _lib.ptr(bs), out.data_ptr(), _stream(dev))
+        if R:
+            mesh = _prepare(v, f, dev, accel)
+            name, nodes = mesh._entry("pn_shadow_ratio")
+            _lib.call(name, R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(), p.data_ptr(), n.data_ptr(),
+                      float(bias), mesh.F, _lib.ptr(mesh.tris), *nodes, _lib.ptr(mesh.bsphere), out.data_ptr(), _stream(dev))
     return out
 
 
@@ -555,6 +558,26 @@ def _texture_hits(obj, R, mask, face, bary, d, t, normals_in, radii, albedo, rou
               _lib.ptr(normals), _lib.ptr(lod), _stream(dev))
 
 
+def _hit_rows(R, t, face, bary, radii, scene_dep, mismatch):
+    """(t [R], face [R] int32, bary [R, 2], radii [R] or None, scene_dep [R] or None) as the kernels read them: fp32 /
+    int32, contiguous.  mismatch: the caller's message for a t, face or bary of another length."""
+    if t.numel() != R or face.numel() != R or tuple(bary.shape) != (R, 2):
+        raise ValueError(mismatch)
+    tt = t.detach().to(torch.float32).reshape(R).contiguous()
+    ff = face.detach().to(torch.int32).reshape(R).contiguous()
+    bb = bary.detach().to(torch.float32).contiguous()
+    dep = rad = None
+    if scene_dep is not None:
+        if scene_dep.numel() != R:
+            raise ValueError(f"scene_dep must hold {R} values; got {tuple(scene_dep.shape)}")
+        dep = scene_dep.detach().to(torch.float32).reshape(R).contiguous()
+    if radii is not None:
+        if radii.numel() != R or radii.dim() > 2:
+            raise ValueError(f"radii must be [R] or [R, 1] with R = {R}; got {tuple(radii.shape)}")
+        rad = radii.detach().to(torch.float32).reshape(R).contiguous()
+    return tt, ff, bb, rad, dep
+
+
 def sample_textures(obj, mask, face, bary, directions, t, normals, radii=None):
     """The texture sampler on its own, at hits given by hand: mask [R] bool, face [R] int32, bary [R, 2], directions
     [R, 3], t [R], normals [R, 3] (the shading normals, facing the eye), radii [R] / [R, 1] or None.  Returns a dict with
@@ -568,17 +591,11 @@ def sample_textures(obj, mask, face, bary, directions, t, normals, radii=None):
     d = _rows3(directions, "directions")
     R = int(d.shape[0])
     n = _rows3(normals, "normals", R)
-    if mask.numel() != R or t.numel() != R or face.numel() != R or tuple(bary.shape) != (R, 2):
-        raise ValueError(f"mask, t, face [R] and bary [R, 2] must match the {R} rows")
-    rad = None
-    if radii is not None:
-        if radii.numel() != R or radii.dim() > 2:
-            raise ValueError(f"radii must be [R] or [R, 1] with R = {R}; got {tuple(radii.shape)}")
-        rad = radii.detach().to(torch.float32).reshape(R).contiguous()
+    mismatch = f"mask, t, face [R] and bary [R, 2] must match the {R} rows"
+    if mask.numel() != R:
+        raise ValueError(mismatch)
+    tt, ff, bb, rad, _ = _hit_rows(R, t, face, bary, radii, None, mismatch)
     m8 = mask.detach().reshape(R).to(torch.uint8).contiguous()
-    ff = face.detach().to(torch.int32).reshape(R).contiguous()
-    bb = bary.detach().to(torch.float32).contiguous()
-    tt = t.detach().to(torch.float32).reshape(R).contiguous()
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
         out = dict(lod=e(R, 3))
@@ -611,21 +628,8 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
     o = _rows3(origins, "origins")
     R = int(o.shape[0])
     d = _rows3(directions, "directions", R)
-    if t.numel() != R or face.numel() != R or tuple(bary.shape) != (R, 2):
-        raise ValueError(f"t, face [R] and bary [R, 2] must match the {R} rays")
-    tt = t.detach().to(torch.float32).reshape(R).contiguous()
-    ff = face.detach().to(torch.int32).reshape(R).contiguous()
-    bb = bary.detach().to(torch.float32).contiguous()
-    dep = None
-    if scene_dep is not None:
-        if scene_dep.numel() != R:
-            raise ValueError(f"scene_dep must hold {R} values; got {tuple(scene_dep.shape)}")
-        dep = scene_dep.detach().to(torch.float32).reshape(R).contiguous()
-    rad = None
-    if radii is not None:
-        if radii.numel() != R or radii.dim() > 2:
-            raise ValueError(f"radii must be [R] or [R, 1] with R = {R}; got {tuple(radii.shape)}")
-        rad = radii.detach().to(torch.float32).reshape(R).contiguous()
+    tt, ff, bb, rad, dep = _hit_rows(R, t, face, bary, radii, scene_dep,
+                                     f"t, face [R] and bary [R, 2] must match the {R} rays")
     pos = None if probe_positions is None else _positions(obj, probe_positions, dev)
     K = 1 if pos is None else int(pos.shape[0])
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -654,20 +658,11 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
     return out
 
 
-def _frame_rays(camera, c2w, near, far, dev, radii=False):
-    """(origins, directions) [H W, 3] of the rays render_view renders for this camera and pose; radii=True adds their cone
-    radii [H W, 1]."""
+def _frame_rays(camera, c2w, near, far, dev):
+    """(origins, directions [H W, 3], cone radii [H W, 1]) of the rays render_view renders for this camera and pose."""
     from . import views
     rays = views.generate_camera_rays(camera, c2w, near, far, dev)
-    return (rays.origins, rays.directions, rays.radii) if radii else (rays.origins, rays.directions)
-
-
-def _object_accel(obj, accel):
-    """accel of insert_object / insert_path -> what trace_mesh and shadow_ratio get: None, or one MeshBVH for every call."""
-    _check_accel(accel)
-    if accel == "bvh" and isinstance(obj, VirtualObject):
-        return obj.bvh()
-    return accel
+    return rays.origins, rays.directions, rays.radii
 
 
 def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, near, far, chunk_rays, accel=None):
@@ -680,13 +675,10 @@ def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, nea
     rows = lambda x: x.permute(0, 2, 3, 1).reshape(R, -1)  # the [H W, C] buffer behind a render_view output
     s_rgb, s_dep, s_nor = rows(scene["fine_rgb"]), rows(scene["fine_dep"]), rows(scene["fine_nor"])
     with torch.no_grad(), torch.cuda.device(dev):
-        o, d, radii = _frame_rays(camera, c2w, near, far, dev, radii=True)
+        o, d, radii = _frame_rays(camera, c2w, near, far, dev)
         t, face, bary = trace_mesh(o, d, obj.vertices, obj.faces, accel=accel)
         K = int(pos.shape[0])
-        if obj.textured:
-            at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None, radii=radii)
-        else:
-            at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None)
+        at = hit_attributes(obj, o, d, t, face, bary, s_dep, pos if K > 1 else None, radii=radii)
         mask = at["mask"]
         object_rgb = torch.zeros(R, 3, dtype=torch.float32, device=dev)
         hit = torch.nonzero(mask).reshape(-1)  # the one host synchronisation: sizes the shading launch
@@ -749,7 +741,7 @@ def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32,
     camera, dev, _ = views._setup(model, camera, chunk_rays)
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
     return _insert(model, camera, c2w, obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays,
-                   _object_accel(obj, accel))
+                   obj.bvh() if accel == "bvh" else accel)
 
 
 def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32, 64), shadows=True, shadow_probe=(8, 16),
@@ -769,7 +761,7 @@ def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32,
     c2ws = views._c2w_stack(poses)
     n, H, W = c2ws.shape[0], camera.h, camera.w
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
-    accel = _object_accel(obj, accel)
+    accel = obj.bvh() if accel == "bvh" else accel  # one MeshBVH for every frame
     frames = {}
     if out_dir is None:
         frames = {k: torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev) for k in kinds}

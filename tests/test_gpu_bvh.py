@@ -171,6 +171,31 @@ def test_trace_is_the_restatement_and_is_brute_force(name):
     assert bits_equal(a, t) and bits_equal(b, face) and bits_equal(c, bary)
 
 
+@pytest.mark.parametrize("rows", [(255, 256, 512), (256, 512)])
+def test_equal_t_across_the_brute_force_tiles_keeps_the_lowest_face(rows):
+    """One triangle three (two) times among 513 faces, the copies in different 256-triangle LDS tiles of the brute-force
+    finder (255 | 256 | 512): every hit is a tie in t, and the lowest face index must win on every path.  The other faces
+    are (0, 0, 0): det == 0, never hit."""
+    from pano_nerf_amd import objects
+    v, one = bspec.scenes()["coincident"]
+    o, d = bspec.scene_rays(v, one[:1])  # aimed at the triangle itself
+    f = np.zeros((513, 3), np.int32)
+    f[list(rows)] = [0, 1, 2]
+    assert len(o) == 18146 and len(o) % 256 and len(o) % 64
+    rt, rface, rbary, lost, _ = bspec.candidate_trace(o, d, v, f)
+    assert lost == 0 and int((rface >= 0).sum()) == 2529 and np.all(rface[rface >= 0] == rows[0])
+    tm = np.where(rface >= 0, rt, f32(1.0)).astype(f32)  # exclusive: the winner and its equals are cut away
+    assert not (bspec.candidate_trace(o, d, v, f, t_max=tm)[1] >= 0).any()
+    to, td, tv, tf = T(o), T(d), T(v), T(f, torch.int32)
+    for accel in (None, "bvh", objects.MeshBVH.build(tv, tf)):
+        t, face, bary = objects.trace_mesh(to, td, tv, tf, accel=accel)
+        assert same_bits(N(face), rface) and same_bits(N(t), rt) and same_bits(N(bary), rbary), accel
+        assert np.array_equal(N(objects.trace_mesh(to, td, tv, tf, any_hit=True, accel=accel)), rface >= 0), accel
+        t2, face2, bary2 = objects.trace_mesh(to, td, tv, tf, t_max=T(tm), accel=accel)
+        assert bool(torch.isinf(t2).all()) and bool((face2 == -1).all()) and bool((bary2 == 0).all()), accel
+        assert not bool(objects.trace_mesh(to, td, tv, tf, t_max=T(tm), any_hit=True, accel=accel).any()), accel
+
+
 def test_trace_with_faces_that_index_outside_the_vertices():
     from pano_nerf_amd import objects
     v, f = _tree_mesh("bad")

@@ -92,7 +92,7 @@ def bvh_stages(v, f, iters):
     dev = v.device
     F, st = int(f.shape[0]), torch.cuda.current_stream(v.device).cuda_stream
     out = {}
-    out["bvh_tri_setup_sphere_ms"], _ = timed(lambda: objects._triangles(v, f, dev), iters)
+    out["bvh_tri_setup_sphere_ms"], _ = timed(lambda: objects._prepare(v, f, dev, None), iters)
     tbox = torch.empty(F, 2, 4, device=dev)
     out["bvh_boxes_ms"], _ = timed(lambda: _lib.call("pn_bvh_boxes", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(),
                                                      tbox.data_ptr(), st), iters)
@@ -142,7 +142,7 @@ def main():
                 sprobe = torch.rand(1, 8, 16, 3, device=dev, generator=g).permute(0, 3, 1, 2) * 2.0
                 s_dep = torch.full((R,), 2.5, device=dev)
                 s_nor = torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=1)
-            o, d = objects._frame_rays(cam, c2w, 0.0, 10.0, dev)
+            o, d, _ = objects._frame_rays(cam, c2w, 0.0, 10.0, dev)
             brute, fast = a.accel in ("none", "both"), a.accel in ("bvh", "both")
             out["accel"] = a.accel
             if fast:

@@ -75,7 +75,7 @@ def main():
     copy_rate = 2 * src.numel() * 4 / (1e-3 * ms)
     out["hbm_copy_GBps"] = copy_rate / 1e9
     del src, dst
-    o, d, radii = objects._frame_rays(cam, c2w, 0.0, 10.0, dev, radii=True)
+    o, d, radii = objects._frame_rays(cam, c2w, 0.0, 10.0, dev)
     objs = {"no_maps": quad(c2w, dev, a.size, 0), "albedo": quad(c2w, dev, a.size, 1), "three_maps": quad(c2w, dev, a.size, 3)}
     t, face, bary = objects.trace_mesh(o, d, objs["no_maps"].vertices, objs["no_maps"].faces)
     out["hit_pixels"] = int((face >= 0).sum())
