@@ -178,10 +178,10 @@ int pn_mlp_backward(int64_t M, int rows_per_ray, int64_t view_rows, int num_dens
                     void* stream, void* side_stream);
 
 
-/* ---- fused on-chip MLP chains (pn_chain.hip) ---------------------------------------------------------------------
+/* ---- fused on-chip MLP chains (pn_chain.hip; weight gradients: pn_wgrad.hip) ----------------------------------------
  * The same MLP (models/pano_mip_nerf.py:95-114, models/mip_nerf.py:81-102), encodings (models/mip.py:394-441) and
  * their reverse / forward-mode passes as ONE kernel per pass: every layer is computed transposed on
- * v_mfma_f32_32x32x16_bf16, a wave carries the activations of its 32 samples from layer to layer in registers, the
+ * v_mfma_f32_16x16x32_bf16 / _f16, a wave carries the activations of its 16 samples from layer to layer in registers, the
  * weights stream through an LDS ring by LDS-DMA.  planes = 3: exact 3-term bf16 split, six partial products (fp32
  * accuracy); planes = 2: fp16 pairs (x 2^e = h + l, |error| < 2^-24 |x|), three partial products, one power-of-two scale
  * per weight matrix and per sample (chains) or per tensor (weight gradients), fp32 accumulate; planes = 1: plain bf16
@@ -189,12 +189,11 @@ int pn_mlp_backward(int64_t M, int rows_per_ray, int64_t view_rows, int num_dens
  * elem[Mp/tile][F][tile] (sample-minor, tile = pn_chain_tile(), Mp = pn_pad_rows(M)), elem = float for planes 3 and 2,
  * bf16 for planes = 1 (the stored value is the bf16 the next GEMM consumes: the float* parameters below then point at
  * 2-byte elements, and a buffer sized in floats is twice as large as needed); gate words are uint32 [9][Mp][8]
- * (per row: tile-dependent lane-group order, see pn_chain.hip; producers and consumers are all in this library). */
-/* samples per block of the sample-minor tensors (= samples per wave of the chain kernels): 16 (v_mfma_f32_16x16x32_bf16,
- * two waves per SIMD; the build default) or 32 (v_mfma_f32_32x32x16_bf16, -DPN_CHAIN_TILE=32).  Below, "T layout" means
- * elem[Mp / tile][F][tile]. */
+ * (per row: lane-group order, see pn_chain.hip; producers and consumers are all in this library). */
+/* samples per block of the sample-minor tensors (= samples per wave of the chain kernels): 16 (v_mfma_f32_16x16x32, two
+ * waves per SIMD).  Callers ask instead of assuming it.  Below, "T layout" means elem[Mp / tile][F][tile]. */
 int pn_chain_tile(void);
-/* "Q24": with planes = 2 and 16-sample tiles, the 256-wide tensors that only pn_chain_wgrad reads back are stored in THREE bytes per
+/* "Q24": with planes = 2, the 256-wide tensors that only pn_chain_wgrad reads back are stored in THREE bytes per
  * element - fp32 rounded to 16 significant bits (round to nearest on the dropped byte), the four features of a quad block of a
  * sample in 12 bytes: elem[Mp / 16][F / 4][16][12 B], byte b of a feature's three = bits 8 (b + 1) .. 8 (b + 1) + 7 of the rounded
  * fp32 - a quarter of the step's HBM traffic in these tensors; each keeps its slot's address (slot * Mp * 256 floats) and uses the

@@ -25,7 +25,7 @@ def _f32(x):
 
 class _Eval:
     """Buffers of one MLP evaluation over M sample rows (all caller-owned HBM).  planes = 0: layer-wise GEMM path
-    (row-major activations); planes = 3 / 2 / 1: fused chain kernels (T32 sample-minor tensors, see pn_chain.hip)."""
+    (row-major activations); planes = 3 / 2 / 1: fused chain kernels (T32 sample-minor tensors, see csrc/pn_chain.hip, pn_wgrad.hip)."""
 
     def __init__(self, M, rows_per_ray, viewdirs, nc, dev, planes=0, keep=True, tfmt=0):
         self.M, self.rows_per_ray, self.nc = M, rows_per_ray, nc
@@ -170,8 +170,7 @@ def _chain_tangent(ev, cfg, params, pack, v, st, wgs=0):
     _lib.call("pn_chain_tangent", ev.M, ev.nc, ev.planes, params.data_ptr(), pack.data_ptr(), ev.mean.data_ptr(),
               ev.cov.data_ptr(), ev.masks.data_ptr(), v.data_ptr(), ev.edot.data_ptr(), ev.tang.data_ptr(),
               ev.sdot.data_ptr(), _lib.ptr(ev.amax), ev.tfmt, wgs, st)
-    z = e if _lib.load().pn_chain_tile() == 16 else (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
-    ev.coef = z(Mp * 32)
+    ev.coef = e(Mp * 32)
 
 
 def _chain_backward(ev, cfg, params, pack, d_raw_rgb, d_raw_den, v, d_mean, st, wgs=0):
@@ -179,15 +178,13 @@ def _chain_backward(ev, cfg, params, pack, d_raw_rgb, d_raw_den, v, d_mean, st, 
     ran it: ev.sdot set); leaves the T32 tensors the weight-gradient GEMMs read on `ev`.  wgs: workgroup budget (0 = all CUs)."""
     dev = d_raw_rgb.device
     e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    # drgb / d8 / coef hold a padded k-step that the 32-sample build (pn_chain_tile() = 32) writes only half of; the
-    # default 16-sample kernels write every feature of every padded row themselves (0.3 ms of fills per step)
-    z = e if _lib.load().pn_chain_tile() == 16 else (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
+    # (no fills: the kernels write every feature of every padded row of drgb / d8 / coef themselves)
     Mp = ev.Mp
     if v is None:
         ev.edot = ev.tang = ev.coef = ev.sdot = None
     elif getattr(ev, "sdot", None) is None:
         _chain_tangent(ev, cfg, params, pack, v, st, wgs)
-    ev.drgb, ev.dhv, ev.d8, ev.delta = z(Mp * 32), e(Mp * 128), z(Mp * 288), e(8 * Mp * 256)
+    ev.drgb, ev.dhv, ev.d8, ev.delta = e(Mp * 32), e(Mp * 128), e(Mp * 288), e(8 * Mp * 256)
     _lib.call("pn_chain_backward", ev.M, ev.nc, ev.planes, cfg.density_bias, pack.data_ptr(), ev.masks.data_ptr(),
               ev.raw_den.data_ptr(), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(), _lib.ptr(ev.sdot), ev.mean.data_ptr(),
               ev.cov.data_ptr(), ev.drgb.data_ptr(), ev.dhv.data_ptr(), ev.d8.data_ptr(), ev.delta.data_ptr(),

@@ -1,7 +1,7 @@
 """Host-side views of the sample-minor ("T layout") tensors the fused chains write and pn_chain_wgrad reads - for tests and
 tools; the training path never touches them on the host.
 
-fp32 T layout: elem[Mp / tile][F][tile].  Q24 (include/panonerf_hip.h, pn_chain_q24_slots; fp16-pair mode, 16-sample tiles): fp32
+fp32 T layout: elem[Mp / tile][F][tile].  Q24 (include/panonerf_hip.h, pn_chain_q24_slots; fp16-pair mode): fp32
 rounded to 16 significant bits, three bytes per element, the four features of a quad of a sample together:
 byte[Mp / 16][F / 4][16][4][3], byte b of an element = bits 8 (b + 1) .. 8 (b + 1) + 7 of the rounded fp32."""
 import torch

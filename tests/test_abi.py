@@ -63,6 +63,9 @@ def test_library_exports_every_symbol():
     assert handle.pn_param_layout(1, off) == 612740
     assert handle.pn_param_layout(3, off) < 0
     assert handle.pn_strerror(-2).decode().startswith("unsupported")
+    # the fused chains have ONE tile shape, and with it the fp16-pair mode always has its Q24 tensors
+    assert handle.pn_chain_tile() == 16
+    assert handle.pn_chain_q24_slots(2, 1, 0) != 0
 
 
 def test_split_k_workspace_is_monotone_in_rows():
