@@ -601,6 +601,62 @@ int pn_warp_resolve(int S, int C, int Hs, int Ws, int D, int dst_kind, int Hd, i
                     const uint64_t* zbuf, const float* image, int64_t image_stride, int64_t cs, int64_t ps, float fill,
                     float* out, float* depth_out, int64_t* index, float* coverage, void* stream);
 
+/* ---- finishing warped frames: "the same surface", blending and hole filling (pn_cameras.hip, pn_inpaint.hip) --------------
+ * One parameter depth_ratio = r in [0, 1) decides whether two depths belong to one surface: positive depths a <= b do iff
+ * b (1 - r) <= a.  q = 1 - r is one fp32 subtraction on the host; every comparison costs one fp32 product.  Everything is
+ * fp32, separate operations in the order written; sums associate to the left and start from their first term.  The usual
+ * r = 0.05 is a convention, not a measurement.
+ *
+ * Blending (pn_warp_blend): S layers of D warped frames, images [S, D, C, H, W], depths [S, D, H, W], weights [S, D] (a
+ * DEVICE array; positive and finite, which the caller checks), all contiguous.  Per destination d and pixel:
+ *   a layer s counts iff 0 < z_s < inf (z_s = depths[s, d, pixel]; NaN, 0, negative and Inf are no points).
+ *   No layer counts: every channel = fill, depth_out = NaN, coverage = 0.
+ *   Otherwise zn = the smallest such z_s; the layers with z_s q <= zn are kept, the others are occluded.  coverage = 1.
+ *   One layer kept: its colours and its depth are copied, bit for bit.
+ *   Several kept: (sum of w_s v_s) / (sum of w_s) over the kept layers in layer order, for each colour and for z
+ *   (w_s = weights[s, d]; NaN in a kept colour propagates).
+ * out [D, C, H, W], depth_out and coverage [D, H, W] are contiguous.  One launch, one thread per pixel, gathers only.
+ * Errors: PN_ERR_BAD_SHAPE (a size <= 0, r outside [0, 1) or not finite, S D C H W >= 2^31), PN_ERR_NULL (any pointer).
+ *
+ * Hole filling (pn_fill_holes): push-pull over a pyramid that fills a hole from its FARTHER neighbours only - a
+ * disocclusion shows what lay behind the foreground, so the foreground must not bleed into it.  In place on N images:
+ * image [N, C, H, W], depth [N, H, W] or NULL, known [N, H, W] fp32 (known iff > 0) or NULL (all known), domain [H, W]
+ * uint8 shared by all images or NULL (all inside), filled [N, H, W] uint8 (written everywhere).  A pixel is known iff it
+ * is inside the domain, its `known` is > 0 and, with a depth, 0 < z < inf; its z is depth's, or 1 without a depth (plain
+ * push-pull).  A pixel outside the domain is never known and never written.
+ * Levels: level 0 is the frame; level l is ((H_{l-1} + 1) >> 1) x ((W_{l-1} + 1) >> 1); the pyramid has L levels above
+ * the frame: up to 1 x 1, or `levels` if that is fewer (PN_FILL_ALL_LEVELS: up to 1 x 1).  A texel holds C colours and z;
+ * z = 0 is unknown.
+ * Pull, l = 1 .. L, per texel (y, x) of level l: its children (2 y + dy, 2 x + dx) in the order (0,0), (0,1), (1,0), (1,1)
+ * that exist in level l - 1 and are known.  None: the texel is unknown.  Otherwise zf = their largest z, the children
+ * with zf q <= z_i are kept, and each colour and z is the sum over the kept children in that order divided by their
+ * count (as a float).
+ * Push, l = L - 1 .. 0, after level l + 1's own push; only the unknown texels of level l (at level 0: inside the domain)
+ * are written.  Four taps in level l + 1: rows (near, far) = ((y - 1) >> 1, (y + 1) >> 1) for odd y and (y / 2, y / 2 - 1)
+ * for even y, columns by the same rule on x; in the order and with the weights (near, near) 9, (near row, far column) 3,
+ * (far row, near column) 3, (far, far) 1.  Rows clamp to the level; columns clamp too, or with wrap_x (a panorama) wrap
+ * modulo W_{l+1}; a clamped duplicate counts twice.  The known taps: none, and the texel stays unknown.  Otherwise zf =
+ * their largest z, the taps with zf q <= z_i are kept, and each colour and z is (sum of w_i v_i) / (sum of w_i) over the
+ * kept taps in tap order.
+ * Outputs: the holes of image (and depth) are filled, known pixels keep their bits; filled = 1 where a value was written
+ * and 0 elsewhere; a pixel no level reaches (capped levels, nothing known) keeps its input bits.  A NaN colour of a known
+ * pixel propagates into what it fills.
+ * One call makes every launch on `stream` (at most 2 L, a pull and a push per level; the levels of at most 1024 texels
+ * share one launch, one workgroup per image with their planes in LDS: the same arithmetic, the same bits): one thread
+ * per texel looping over the channels, gathers only, no atomics, no host read or synchronisation, so repeated calls
+ * give the same bits.  work holds
+ * levels 1 .. L as [N, C + 1, H_l, W_l] planes: pn_fill_holes_work_floats(N, C, H, W, levels) floats (work_floats is what
+ * the caller has; with L = 0 nothing is needed and work may be NULL).
+ * Errors: PN_ERR_BAD_SHAPE (a size <= 0, N (C + 1) H W >= 2^31, r outside [0, 1) or not finite, levels < 0, work_floats too
+ * small; pn_fill_holes_work_floats returns it as its value), PN_ERR_NULL (image, filled, or work with L > 0). */
+#define PN_FILL_ALL_LEVELS 32
+int pn_warp_blend(int S, int D, int C, int H, int W, const float* images, const float* depths, const float* weights,
+                  float depth_ratio, float fill, float* out, float* depth_out, float* coverage, void* stream);
+int64_t pn_fill_holes_work_floats(int N, int C, int H, int W, int levels);
+int pn_fill_holes(int N, int C, int H, int W, float* image, float* depth, const float* known, const uint8_t* domain,
+                  int wrap_x, float depth_ratio, int levels, uint8_t* filled, float* work, int64_t work_floats,
+                  void* stream);
+
 /* ---- dataset ingest (pn_data.hip) ---------------------------------------------------------------------------------
  * planes: the channel planes of one decoded scanline OpenEXR file as stored, [Hs][n_ch][Ws] (line, channel, column),
  * fp16 (is_half != 0) or fp32, on the device.  out: [Hs / factor, Ws / factor, C] fp32 interleaved, C = 1 for

@@ -79,6 +79,9 @@ SIGNATURES = {
     "pn_reproject": ("i", "iiiiipiiippifplllppp"),
     "pn_warp_splat": ("i", "iiiipppiiiippifpp"),
     "pn_warp_resolve": ("i", "iiiiiiii" + "ppp" + "lllf" + "pppp" + "p"),
+    "pn_warp_blend": ("i", "iiiii" + "ppp" + "ff" + "ppp" + "p"),
+    "pn_fill_holes_work_floats": ("l", "iiiii"),
+    "pn_fill_holes": ("i", "iiii" + "pppp" + "ifi" + "ppl" + "p"),
     "pn_ingest_image": ("i", "iiiipiiiiiiffpp"),
     "pn_tri_setup": ("i", "llpppp"),
     "pn_trace_mesh": ("i", "lpplpppi" + "pppp" + "p"),

@@ -355,6 +355,59 @@ __global__ __launch_bounds__(kThreads) void k_warp_resolve(int64_t n_src, int C,
     for (int c = 0; c < C; ++c) o[(int64_t)c * hwd] = hit ? px[(int64_t)c * cs] : fill;
 }
 
+// blend S layers of warped frames per destination pixel: the layers on the nearest surface, by weight (pn_warp_blend)
+__global__ __launch_bounds__(kThreads) void k_warp_blend(int S, int64_t D, int C, int64_t hw, const float* images,
+                                                         const float* depths, const float* weights, float q, float fill,
+                                                         float* out, float* depth_out, float* coverage) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= D * hw) return;
+    const int64_t d = idx / hw, pix = idx % hw;
+    const int64_t zs = D * hw, vs = D * C * hw;  // layer strides of depths and images
+    const float* z = depths + idx;
+    float zn = INFINITY;
+    for (int s = 0; s < S; ++s) {
+        const float t = z[s * zs];
+        if (t > 0.f && t < zn) zn = t;  // NaN, 0, negative and Inf are no points
+    }
+    float* o = out + d * C * hw + pix;
+    if (!(zn < INFINITY)) {
+        depth_out[idx] = NAN;
+        coverage[idx] = 0.f;
+        for (int c = 0; c < C; ++c) o[(int64_t)c * hw] = fill;
+        return;
+    }
+    int kept = 0, one = 0;
+    float wsum = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float t = z[s * zs];
+        if (!(t > 0.f && t < INFINITY && t * q <= zn)) continue;
+        const float w = weights[s * D + d];
+        wsum = kept ? wsum + w : w;
+        one = kept ? one : s;
+        ++kept;
+    }
+    coverage[idx] = 1.f;
+    const float* v = images + d * C * hw + pix;
+    if (kept == 1) {  // a single source keeps its bits
+        depth_out[idx] = z[one * zs];
+        for (int c = 0; c < C; ++c) o[(int64_t)c * hw] = v[one * vs + (int64_t)c * hw];
+        return;
+    }
+    for (int c = 0; c <= C; ++c) {
+        float acc = 0.f;
+        bool first = true;
+        for (int s = 0; s < S; ++s) {
+            const float t = z[s * zs];
+            if (!(t > 0.f && t < INFINITY && t * q <= zn)) continue;
+            const float x = weights[s * D + d] * (c == C ? t : v[s * vs + (int64_t)c * hw]);
+            acc = first ? x : acc + x;
+            first = false;
+        }
+        if (c == C) depth_out[idx] = acc / wsum;
+        else o[(int64_t)c * hw] = acc / wsum;
+    }
+}
+
 // minimum image size of a camera kind; false for an unknown kind
 bool min_size(int kind, int H, int W, bool& ok) {
     switch (kind) {
@@ -489,6 +542,19 @@ int pn_warp_resolve(int S, int C, int Hs, int Ws, int D, int dst_kind, int Hd, i
     hipLaunchKernelGGL(k_warp_resolve, dim3(nblk(n_dst, kThreads)), dim3(kThreads), 0, ST(stream), (int64_t)S * Hs * Ws, C, Hs,
                        Ws, n_dst, dst_kind, Hd, Wd, dp, (const unsigned long long*)zbuf, image, image_stride, cs, ps, fill, out,
                        depth_out, index, coverage);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_warp_blend(int S, int D, int C, int H, int W, const float* images, const float* depths, const float* weights,
+                  float depth_ratio, float fill, float* out, float* depth_out, float* coverage, void* stream) {
+    if (S <= 0 || D <= 0 || C <= 0 || H <= 0 || W <= 0 || !(depth_ratio >= 0.f && depth_ratio < 1.f) ||
+        (int64_t)S * D * C * H * W >= ((int64_t)1 << 31))
+        return PN_ERR_BAD_SHAPE;
+    if (!images || !depths || !weights || !out || !depth_out || !coverage) return PN_ERR_NULL;
+    const int64_t hw = (int64_t)H * W;
+    hipLaunchKernelGGL(k_warp_blend, dim3(nblk(D * hw, kThreads)), dim3(kThreads), 0, ST(stream), S, (int64_t)D, C, hw, images,
+                       depths, weights, 1.f - depth_ratio, fill, out, depth_out, coverage);
     PN_CHECK_LAUNCH();
     return PN_OK;
 }

@@ -31,6 +31,11 @@ tensors raise, there is no host fallback.  Cameras (``cameras.py``, re-exported 
                                                 frames seen from other poses (z-buffered forward splatting)
     render_path_warped(model, camera, poses, key_every, ...)   render_path's frames, every key_every-th pose rendered and
                                                 the poses between warped from their two rendered neighbours
+                                                (blend=True: blended by weight; inpaint=True: holes filled)
+    blend_warps(images, depths, weights, ...)   dict image / depth / coverage: S layers of warped frames blended per pixel
+                                                among the layers on the nearest surface
+    fill_holes(image, depth, coverage, camera, ...)   dict image / depth / filled: holes filled by a push-pull pyramid that
+                                                prefers the background
 
 Conventions (pixel directions, radii, frame bytes, the cube-map table, the inverse projections) are stated in
 include/panonerf_hip.h.
@@ -598,16 +603,178 @@ def warp_view(image, depth, src_camera, src_c2w, dst_camera, dst_c2w, max_splat=
     return res
 
 
+def _depth_ratio(depth_ratio):
+    r = float(depth_ratio)
+    if not 0.0 <= r < 1.0:  # NaN fails too
+        raise ValueError(f"depth_ratio must lie in [0, 1); got {depth_ratio!r}")
+    return r
+
+
+def _on_device(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (the %s is on %s); there is no CPU fallback"
+                           % (what, t.device))
+
+
+def blend_warps(images, depths, weights, depth_ratio=0.05, fill=0.0):
+    """Blend S layers of D warped frames by weight, per pixel, among the layers that show the nearest surface (pn_warp_blend;
+    the rule is in include/panonerf_hip.h).  images: [S, D, C, H, W] device tensor, e.g. torch.stack of the "image" of S
+    single-source warp_view calls; depths: [S, D, H, W] or [S, D, 1, H, W], their "depth"; weights: [S, D] or [S] (one
+    weight per layer for every frame), positive and finite.
+
+    A layer counts at a pixel iff 0 < z < inf.  With zn the smallest such z, the layers with z (1 - depth_ratio) <= zn are
+    kept and the others are occluded; one kept layer is copied bit for bit, several give (sum w v) / (sum w) in layer
+    order, for the colours and the depth.  depth_ratio = 0.05 is a convention, not a measurement.
+    -> dict "image" [D, C, H, W], "depth" [D, 1, H, W], "coverage" [D, H, W] (warp_view's shapes): where no layer counts,
+    `fill`, NaN and 0; coverage 1 elsewhere."""
+    r = _depth_ratio(depth_ratio)
+    if not isinstance(images, torch.Tensor) or images.dim() != 5:
+        raise ValueError(f"images must be a [S, D, C, H, W] tensor; got {getattr(images, 'shape', type(images))}")
+    S, D, C, H, W = (int(v) for v in images.shape)
+    if min(S, D, C, H, W) < 1:
+        raise ValueError("images is empty")
+    if not isinstance(depths, torch.Tensor) or tuple(depths.shape) not in ((S, D, H, W), (S, D, 1, H, W)):
+        raise ValueError(f"depths must be [S, D, H, W] = {(S, D, H, W)} (or [S, D, 1, H, W]); got "
+                         f"{getattr(depths, 'shape', type(depths))}")
+    if S * D * C * H * W >= 1 << 31:
+        raise ValueError("too many values: S D C H W must be below 2^31")
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape == (S,):
+        w = np.repeat(w[:, None], D, 1)
+    if w.shape != (S, D):
+        raise ValueError(f"weights must be [S, D] = {(S, D)} or [S]; got shape {w.shape}")
+    w32 = np.ascontiguousarray(w.astype(np.float32))
+    if not (np.isfinite(w32).all() and (w32 > 0).all()):
+        raise ValueError("weights must be positive and finite")
+    _on_device(images, "images")
+    _on_device(depths, "depths")
+    dev = images.device
+    if depths.device != dev:
+        raise ValueError(f"depths is on {depths.device} but images on {dev}")
+    x = images.detach().to(torch.float32).contiguous()
+    z = depths.detach().to(torch.float32).contiguous()
+    with torch.no_grad(), torch.cuda.device(dev):
+        wd = torch.from_numpy(w32).to(dev)
+        out = torch.empty(D, C, H, W, dtype=torch.float32, device=dev)
+        dep = torch.empty(D, 1, H, W, dtype=torch.float32, device=dev)
+        cov = torch.empty(D, H, W, dtype=torch.float32, device=dev)
+        _lib.call("pn_warp_blend", S, D, C, H, W, x.data_ptr(), z.data_ptr(), wd.data_ptr(), r, float(fill), out.data_ptr(),
+                  dep.data_ptr(), cov.data_ptr(), _stream(dev))
+    return {"image": out, "depth": dep, "coverage": cov}
+
+
+_FILL_ALL_LEVELS = 32  # PN_FILL_ALL_LEVELS
+_DOMAINS = {}
+
+
+def _domain(camera, dev):
+    """uint8 [H, W] device tensor of camera_mask(camera), made once per camera and device"""
+    key = (camera, str(dev))
+    if key not in _DOMAINS:
+        _DOMAINS[key] = torch.from_numpy(np.ascontiguousarray(camera_mask(camera), dtype=np.uint8)).to(dev)
+    return _DOMAINS[key]
+
+
+def fill_holes(image, depth=None, coverage=None, camera=None, depth_ratio=0.05, levels=None):
+    """Fill the holes of N frames by push-pull over an image pyramid that prefers the background (pn_fill_holes; the rule
+    is in include/panonerf_hip.h): a disocclusion shows what lay BEHIND the foreground, so wherever known neighbours
+    differ in depth by more than depth_ratio only the farther ones are averaged.  depth_ratio = 0.05 is a convention,
+    not a measurement.
+
+    image: [N, C, H, W] or [C, H, W] device tensor (any C).  depth: [N, 1, H, W], [N, H, W] or [H, W], or None.  coverage:
+    [N, H, W], [N, 1, H, W] or [H, W], or None (everything covered).  A pixel is known where coverage > 0 and, with a
+    depth, 0 < z < inf; without a depth every known pixel lies at z = 1, which is plain depth-blind push-pull.  So
+    warp_view's or blend_warps' dict plugs in: fill_holes(w["image"], w["depth"], w["coverage"], camera).
+    camera: what the frame is an image of.  A panorama wraps in columns; a cube map's 6 S x S strip is filled as six
+    independent S x S faces (nothing crosses a face border, so a face with no known pixel stays a hole); a fisheye is
+    filled inside its image circle only (camera_mask) and nothing outside it is read or written; a pinhole camera or
+    None is a plain image; a stereo-panorama camera raises ValueError.  levels: the number of pyramid levels above the
+    frame (None: up to 1 x 1, which fills every image that has a known pixel; l levels reach about 2^l pixels into a hole).
+
+    -> dict "image" [N, C, H, W], "depth" [N, 1, H, W] (absent when depth is None) and "filled" [N, H, W] bool: True where a
+    value was written.  Known pixels keep their bits, and so does a hole that no level reaches.  The inputs are not
+    modified.  Repeated calls give the same bits."""
+    cam = None if camera is None else _camera(camera)
+    if isinstance(cam, StereoPanoCamera):
+        raise ValueError("a stereo-panorama camera is not a central projection: its frames cannot be filled")
+    r = _depth_ratio(depth_ratio)
+    lv = _FILL_ALL_LEVELS
+    if levels is not None:
+        lv = int(levels)
+        if lv != levels or lv < 0:
+            raise ValueError(f"levels must be a non-negative integer or None; got {levels!r}")
+        lv = min(lv, _FILL_ALL_LEVELS)
+    if not isinstance(image, torch.Tensor) or image.dim() not in (3, 4):
+        raise ValueError(f"image must be a [C, H, W] or [N, C, H, W] tensor; got {getattr(image, 'shape', type(image))}")
+    x = image.detach()
+    if x.dim() == 3:
+        x = x[None]
+    N, C, H, W = (int(v) for v in x.shape)
+    if min(N, C, H, W) < 1:
+        raise ValueError("image is empty")
+    if cam is not None and (H, W) != (cam.h, cam.w):
+        raise ValueError(f"image is {H} x {W} but camera is {cam.h} x {cam.w}")
+    if N * (C + 1) * H * W >= 1 << 31:
+        raise ValueError("too many values: N (C + 1) H W must be below 2^31")
+    _on_device(x, "image")
+    dev = x.device
+    planes = []
+    for t, what in ((depth, "depth"), (coverage, "coverage")):
+        if t is None:
+            planes.append(None)
+            continue
+        ok = isinstance(t, torch.Tensor) and (tuple(t.shape) in ((N, H, W), (N, 1, H, W)) or (N == 1 and tuple(t.shape) == (H, W)))
+        if not ok:
+            raise ValueError(f"{what} must be [N, H, W] = {(N, H, W)}, [N, 1, H, W] or [H, W]; got {getattr(t, 'shape', type(t))}")
+        _on_device(t, what)
+        if t.device != dev:
+            raise ValueError(f"{what} is on {t.device} but image on {dev}")
+        planes.append(t.detach().reshape(N, H, W))
+    z, known = planes
+    cube = isinstance(cam, CubeCamera)
+    n, h = (6 * N, W) if cube else (N, H)  # a cube strip is 6 N images of W x W: depth, known and filled as they lie
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty((N, 6, C, W, W) if cube else (N, C, H, W), dtype=torch.float32, device=dev)
+        out.copy_(x.reshape(N, C, 6, W, W).permute(0, 2, 1, 3, 4) if cube else x)
+        if z is not None:
+            z = z.to(torch.float32, copy=True).contiguous()
+        if known is not None:
+            known = known.to(torch.float32).contiguous()
+        domain = _domain(cam, dev) if isinstance(cam, FisheyeCamera) else None
+        filled = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+        floats = int(_lib.load().pn_fill_holes_work_floats(n, C, h, W, lv))
+        _lib.check(min(floats, 0), "pn_fill_holes_work_floats")
+        work = torch.empty(floats, dtype=torch.float32, device=dev) if floats else None
+        _lib.call("pn_fill_holes", n, C, h, W, out.data_ptr(), _lib.ptr(z), _lib.ptr(known), _lib.ptr(domain),
+                  int(isinstance(cam, PanoCamera)), r, lv, filled.data_ptr(), _lib.ptr(work), floats, _stream(dev))
+        if cube:
+            out = out.permute(0, 2, 1, 3, 4).reshape(N, C, H, W)
+    res = {"image": out, "filled": filled.view(torch.bool)}
+    if z is not None:
+        res["depth"] = z.view(N, 1, H, W)
+    return res
+
+
 def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("ldr", "depth"), near=0.0, far=10.0,
-                       exposure=0.0, out_dir=None, chunk_rays=32768, max_splat=4, splat_scale=1.0, fill=0.0):
+                       exposure=0.0, out_dir=None, chunk_rays=32768, max_splat=4, splat_scale=1.0, fill=0.0, blend=False,
+                       inpaint=False, depth_ratio=0.05, levels=None):
     """render_path at interactive frame counts: poses 0, key_every, 2 key_every, ... and the last pose are rendered
     (render_view); every pose between two rendered poses is warp_view of those two frames (S = 2) into it.  -> render_path's
     dict of frames ("ldr" and "depth" through to_frame, "hdr" as fp32) plus "coverage" [n, H, W] fp32: 1 at a rendered
-    pose and where a warped frame shows a source pixel, 0 in its holes (disocclusions, which nothing inpaints: `fill` in
+    pose and where a warped frame shows a source pixel, 0 in its holes (disocclusions, which nothing inpaints unless inpaint is set: `fill` in
     the colours, NaN in the depth - and a NaN depth anywhere makes to_frame's depth frame black, as upstream's hotmap).
     A rendered pose's frame is the render itself, so key_every = 1 gives render_path's bytes.  kinds: "ldr", "hdr", "depth"
     (what a warp carries; the others need the renderer).  With out_dir the frames go to files as render_path writes them
-    and only "coverage" is returned."""
+    and only "coverage" is returned.
+
+    blend: every pose i between the rendered poses a < b is warped from a alone and from b alone (two warp_view calls with
+    S = 1) and the two layers go through blend_warps with the weights (b - i) / (b - a) and (i - a) / (b - a), so view-
+    dependent colour fades from one key to the next where both see a surface, instead of switching per pixel.  inpaint:
+    the warped (or blended) frames go through fill_holes with the camera before to_frame, so their depth frames are
+    complete; "coverage" still reports what the warp covered, i.e. which pixels were invented.  depth_ratio and levels
+    are blend_warps' and fill_holes'.  Rendered poses are never touched; with both off these are the calls described above."""
     from . import io_exr
     camera, dev, _ = _setup(model, camera, chunk_rays)
     kinds = tuple(kinds)
@@ -654,8 +821,17 @@ def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("l
     for a, b in zip(keys[:-1], keys[1:]):
         cur = render(b)
         if b - a > 1:
-            w = warp_view(torch.cat([prev[0], cur[0]]), torch.cat([prev[1], cur[1]]), camera, c2ws[[a, b]], camera,
-                          c2ws[a + 1:b], max_splat, splat_scale, fill)
+            if blend:  # each key frame warped alone, the two layers weighted by the distance to the other key
+                ws = [warp_view(src[0], src[1], camera, c2ws[j], camera, c2ws[a + 1:b], max_splat, splat_scale, fill)
+                      for src, j in ((prev, a), (cur, b))]
+                wts = [[(b - i) / (b - a) for i in range(a + 1, b)], [(i - a) / (b - a) for i in range(a + 1, b)]]
+                w = blend_warps(torch.stack([ws[0]["image"], ws[1]["image"]]), torch.stack([ws[0]["depth"], ws[1]["depth"]]),
+                                wts, depth_ratio, fill)
+            else:
+                w = warp_view(torch.cat([prev[0], cur[0]]), torch.cat([prev[1], cur[1]]), camera, c2ws[[a, b]], camera,
+                              c2ws[a + 1:b], max_splat, splat_scale, fill)
+            if inpaint:  # coverage stays the warp's: the record of what was invented
+                w = {**w, **fill_holes(w["image"], w["depth"], w["coverage"], camera, depth_ratio, levels)}
             for f, i in enumerate(range(a + 1, b)):
                 emit(i, w["image"][f:f + 1], w["depth"][f:f + 1], w["coverage"][f])
         emit(b, *cur, one)
