@@ -7,6 +7,8 @@ RuntimeError.  Build with ``python __graft_entry__.py`` or ``pano-nerf_amd/csrc/
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpanonerf_hip.so")
 
@@ -138,3 +140,8 @@ def call(name, *args):
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()
+
+
+def stream(dev):
+    """Raw handle of the device's current HIP stream: the last argument of every launching entry point."""
+    return torch.cuda.current_stream(dev).cuda_stream

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .render import _Eval, _mlp_forward, _planes_of, _tfmt_of
+from .render import _Field
 
 Mesh = collections.namedtuple("Mesh", ["vertices", "faces", "normals", "colors"])
 ObjMesh = collections.namedtuple("ObjMesh", ["vertices", "faces", "uv", "face_uv", "normals", "face_material", "materials"])
@@ -84,18 +84,12 @@ def _variance(model, variance, step=None):
 def _field_rows(model, dev, M, fill, outputs, viewdirs, chunk_rows, results):
     """Evaluate the field over M rows in chunks; fill(first, m, mean, cov) writes a chunk's (mean, cov) rows; results:
     output name -> [M, ...] tensor (or, for "sigma", any [M] view, e.g. a flat volume)."""
-    mlp, nc = model.mlp, model._NC
-    mode = model.mlp_mode
-    planes, tfmt = _planes_of(mode), _tfmt_of(mode)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    params = mlp.flat_params()
-    wpack = mlp.chain_packed(st, planes) if planes else mlp.packed(st)
+    f = _Field.of(model, dev)
     want_grad = "normal" in results or "grad" in results
-    chunk = int(chunk_rows) if chunk_rows else (_CHUNK_CHAIN if planes else _CHUNK_LAYERWISE)
+    chunk = int(chunk_rows) if chunk_rows else (_CHUNK_CHAIN if f.planes else _CHUNK_LAYERWISE)
     if chunk <= 0:
         raise ValueError(f"chunk_rows must be positive; got {chunk_rows!r}")
     dummy_view = torch.zeros(1, 3, dtype=torch.float32, device=dev)
-    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     for first in range(0, M, chunk):
         m = min(chunk, M - first)
         if viewdirs is None:  # sigma / albedo / normals do not read the view: one dummy view row for the whole chunk
@@ -104,27 +98,14 @@ def _field_rows(model, dev, M, fill, outputs, viewdirs, chunk_rows, results):
             vd, rpr = viewdirs, m
         else:
             vd, rpr = viewdirs[first:first + m], 1
-        ev = _Eval(m, rpr, vd, nc, dev, planes, False, tfmt)
+        ev = f.evaluation(m, rpr, vd, False)
         fill(first, m, ev.mean, ev.cov)
-        _mlp_forward(ev, params, wpack, st)
-        gmean = None
-        if want_grad:
-            gmean = results["grad"][first:first + m] if "grad" in results else e(m, 3)
-            if planes:
-                rs = e(ev.Mp * 256)
-                _lib.call("pn_chain_density_grad", m, nc, planes, model.density_bias, params.data_ptr(), wpack.data_ptr(),
-                          ev.mean.data_ptr(), ev.cov.data_ptr(), ev.masks.data_ptr(), ev.raw_den.data_ptr(),
-                          rs.data_ptr(), 0, gmean.data_ptr(), None, tfmt, 0, st)
-            else:
-                rs, scratch = e(8, ev.Mp, 256), e(ev.Mp, 96)
-                _lib.call("pn_density_grad", m, nc, model.density_bias, params.data_ptr(), wpack.data_ptr(),
-                          ev.mean.data_ptr(), ev.cov.data_ptr(), ev.acts.data_ptr(), ev.masks.data_ptr(),
-                          ev.raw_den.data_ptr(), rs.data_ptr(), scratch.data_ptr(), gmean.data_ptr(), st)
-            del rs
+        f.forward(ev)
         sl = lambda k: (results[k][first:first + m] if k in results else None)
-        _lib.call("pn_field_epilogue", m, nc, model.density_bias, model.rgb_padding, ev.raw_rgb.data_ptr(),
+        gmean = f.density_grad(ev, False, sl("grad")) if want_grad else None
+        _lib.call("pn_field_epilogue", m, f.nc, f.density_bias, f.rgb_padding, ev.raw_rgb.data_ptr(),
                   ev.raw_den.data_ptr(), _lib.ptr(gmean), _lib.ptr(sl("sigma")), _lib.ptr(sl("albedo")),
-                  _lib.ptr(sl("rgb")), _lib.ptr(sl("normal")), st)
+                  _lib.ptr(sl("rgb")), _lib.ptr(sl("normal")), f.st)
         del ev
 
 
@@ -195,7 +176,7 @@ def grid_points(bounds, resolution, variance=0.0, device=None):
         mean = torch.empty(n, 3, dtype=torch.float32, device=dev)
         cov = torch.empty(n, 3, dtype=torch.float32, device=dev)
         _lib.call("pn_grid_points", *res, 0, n, *lo, *step, float(variance), mean.data_ptr(), cov.data_ptr(),
-                  torch.cuda.current_stream(dev).cuda_stream)
+                  _lib.stream(dev))
     return mean, cov
 
 
@@ -212,7 +193,7 @@ def density_grid(model, bounds, resolution, variance=None, chunk_rows=None):
     dev = _model_device(model)
     vol = torch.empty(res, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
 
         def fill(first, m, mean, cov):
             _lib.call("pn_grid_points", *res, first, m, *lo, *step, variance, mean.data_ptr(), cov.data_ptr(), st)
@@ -241,7 +222,7 @@ def marching_tetrahedra(sigma, level, bounds=None):
         lo, step = _placement(bounds, res)
     level = float(level)
     with torch.no_grad(), torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
         s = sigma.detach().to(torch.float32).contiguous()
         work = torch.empty(int(_lib.load().pn_mt_work_bytes(*res)), dtype=torch.uint8, device=dev)
         totals = torch.empty(2, dtype=torch.int64, device=dev)

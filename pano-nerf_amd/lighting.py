@@ -29,7 +29,7 @@ from . import _lib
 from .geometry import _model_device, _placement, _resolution, grid_points
 from .cameras import PanoCamera
 from .rays import CameraRig, Rays
-from .render import _Cfg, _light_gather, _planes_of, _tfmt_of
+from .render import _Field, _light_gather, _planes_of
 
 IrradianceVolume = collections.namedtuple("IrradianceVolume", ["sh", "lo", "step"])
 
@@ -52,10 +52,6 @@ def _cuda(*tensors):
         if t.device != dev:
             raise RuntimeError(f"tensors are on {dev} and {t.device}")
     return dev
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _size(height, width):
@@ -160,7 +156,7 @@ def sh_project(probes):
         out = torch.empty(P, 9, 3, dtype=torch.float32, device=dev)
         work = torch.empty(int(_lib.load().pn_probe_sh_work_doubles(P, H, W)), dtype=torch.float64, device=dev)
         _lib.call("pn_probe_sh", P, H, W, x.data_ptr(), sp, sc, sw, dirs.data_ptr(), omega.data_ptr(), out.data_ptr(),
-                  work.data_ptr(), _stream(dev))
+                  work.data_ptr(), _lib.stream(dev))
     return out
 
 
@@ -176,7 +172,7 @@ def irradiance(probes, normals):
         dirs, omega = _table(H, W, dev)
         out = torch.empty(P, K, 3, dtype=torch.float32, device=dev)
         _lib.call("pn_probe_irradiance", P, H, W, x.data_ptr(), sp, sc, sw, dirs.data_ptr(), omega.data_ptr(), K,
-                  n.data_ptr(), int(per), out.data_ptr(), _stream(dev))
+                  n.data_ptr(), int(per), out.data_ptr(), _lib.stream(dev))
     return out
 
 
@@ -221,13 +217,8 @@ def field_irradiance(model, points, normals, env_rays, chunk_points=None):
         raise RuntimeError(f"points are on {dev}, the model on {_model_device(model)}")
     M = int(points.shape[0])
     out = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    mode = model.mlp_mode
-    planes = _planes_of(mode)
-    cfg = _Cfg(nc=model._NC, density_bias=model.density_bias, rgb_padding=model.rgb_padding,
-               disable_integration=model.disable_integration, num_env_samples=model.num_env_samples, planes=planes,
-               tfmt=_tfmt_of(mode))
+    planes = _planes_of(model.mlp_mode)
     with torch.no_grad(), torch.cuda.device(dev):
-        st = _stream(dev)
         env, _ = model._env_inputs(env_rays, True, dev)  # the renderer's fp32 copies of the caller's (fp16) rays
         D = int(env[0].shape[0])
         rows = (_ROWS_CHAIN if planes else _ROWS_LAYERWISE) // (D * model.num_env_samples)
@@ -236,9 +227,7 @@ def field_irradiance(model, points, normals, env_rays, chunk_points=None):
             raise ValueError(f"chunk_points must be positive; got {chunk_points!r}")
         if not M:
             return out
-        mlp = model.mlp
-        params = mlp.flat_params()
-        wpack = mlp.chain_packed(st, planes) if planes else mlp.packed(st)
+        f = _Field.of(model, dev)
         pts = points.detach().to(torch.float32).contiguous()
         nrm = normals.detach().to(torch.float32).contiguous()
         zeros3 = torch.zeros(min(chunk, M), 3, dtype=torch.float32, device=dev)
@@ -246,10 +235,12 @@ def field_irradiance(model, points, normals, env_rays, chunk_points=None):
         ones = torch.ones(min(chunk, M), 3, dtype=torch.float32, device=dev)  # albedo placeholder: only shading is kept
         for first in range(0, M, chunk):
             m = min(chunk, M - first)
-            _, _, _, shading = _light_gather(cfg, params, wpack, pts[first:first + m], zeros3[:m], zeros1[:m], *env,
-                                             None, ones[:m], nrm[first:first + m], False, st)
+            _, _, _, shading = _light_gather(f, pts[first:first + m], zeros3[:m], zeros1[:m], *env, None, ones[:m],
+                                             nrm[first:first + m], False)
             out[first:first + m].copy_(shading)
     return out
+
+
 
 
 def irradiance_volume(model, bounds, resolution, height=16, width=32, near=0.0, far=10.0, chunk_rays=32768):
@@ -289,7 +280,7 @@ def sample_irradiance(volume, points, normals):
         p = points.detach().to(torch.float32).contiguous()
         n = normals.detach().to(torch.float32).contiguous()
         _lib.call("pn_sh_volume_irradiance", *(int(v) for v in sh.shape[:3]), *(float(v) for v in lo),
-                  *(float(v) for v in step), s.data_ptr(), M, p.data_ptr(), n.data_ptr(), out.data_ptr(), _stream(dev))
+                  *(float(v) for v in step), s.data_ptr(), M, p.data_ptr(), n.data_ptr(), out.data_ptr(), _lib.stream(dev))
     return out
 
 

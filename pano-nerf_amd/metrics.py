@@ -157,10 +157,6 @@ def _device(*ts):
     return next(t.device for t in ts if t is not None and t.is_cuda)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _planes(t):
     """(tensor, C, H, W, channel stride, pixel stride) of an fp32 CUDA image, read in place whenever its H and W
     dimensions collapse into one pixel index (as in the permuted [1, C, H, W] views render_image returns)."""
@@ -207,7 +203,7 @@ def _image_sums(x, y, tx=TONE_NONE, ty=TONE_NONE, out=None, work=None):
         out = torch.empty(_N_SUMS, dtype=torch.float64, device=dev) if out is None else out
         work = _workspace(dev, c, h, w) if work is None else work
         _lib.call("pn_metric_sums", c, h, w, xt.data_ptr(), xcs, xps, tx, yt.data_ptr(), ycs, yps, ty, out.data_ptr(),
-                  work.data_ptr(), _stream(dev))
+                  work.data_ptr(), _lib.stream(dev))
         return out
     a, b = _chw(x), _chw(y)
     d = _tonemap(a, tx).double() - _tonemap(b, ty).double()
@@ -241,7 +237,7 @@ def _ssim_sums(x, y, tx=TONE_NONE, ty=TONE_NONE, window_size=11, max_val=1.0, wa
         smap = torch.empty(c, h, w, dtype=torch.float32, device=dev) if want_map else None
         _lib.call("pn_metric_ssim", c, h, w, xt.data_ptr(), xcs, xps, tx, yt.data_ptr(), ycs, yps, ty, int(window_size),
                   _device_taps(dev).data_ptr(), float(max_val), _lib.ptr(smap), out.data_ptr(), work.data_ptr(),
-                  _stream(dev))
+                  _lib.stream(dev))
         return out, smap
     a = _tonemap(_chw(x), tx).double()[:, None]
     b = _tonemap(_chw(y), ty).double()[:, None]
@@ -270,7 +266,7 @@ def _normal_sums(x, y, y_normalize=0, out=None, work=None):
         out = torch.empty(_N_NORMALS, dtype=torch.float64, device=dev) if out is None else out
         work = _workspace(dev, 3, h, w) if work is None else work
         _lib.call("pn_metric_normals", h, w, xt.data_ptr(), xcs, xps, yt.data_ptr(), ycs, yps, int(y_normalize),
-                  out.data_ptr(), work.data_ptr(), _stream(dev))
+                  out.data_ptr(), work.data_ptr(), _lib.stream(dev))
         return out
     a, b = _chw(x), _chw(y)
     for _ in range(y_normalize):
@@ -293,7 +289,7 @@ def _depth_sums(pred, gt, mask=None, out=None, work=None):
         out = torch.empty(_N_DEPTH, dtype=torch.float64, device=dev) if out is None else out
         work = _workspace(dev, 1, 1, 1) if work is None else work
         _lib.call("pn_metric_depth", p.numel(), p.data_ptr(), ps, g.data_ptr(), gs, _lib.ptr(m), ms, out.data_ptr(),
-                  work.data_ptr(), _stream(dev))
+                  work.data_ptr(), _lib.stream(dev))
         return out
     p, g = pred.reshape(-1).double(), gt.reshape(-1).double()
     if mask is not None:

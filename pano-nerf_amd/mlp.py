@@ -60,7 +60,7 @@ class RadianceMLP(torch.nn.Module):
         self._wpack = None
         self._generation = 0  # bumped by every writer that bypasses autograd's version counters (FlatAdam: raw pointers)
         self._chain = {}  # planes -> packed chains of the fused kernels (buffer reused, contents rebuilt per call)
-        self._frozen = False  # concurrent_step: packs built once before the sub-batch streams fork
+        self._frozen = False  # parallel.lanes: packs built once before the streams fork
         self.last_flat_grad = None
         self._flatten()
 
@@ -128,7 +128,7 @@ class RadianceMLP(torch.nn.Module):
         """Fragment-ordered bf16 planes of every weight matrix, in both directions, for the fused chain kernels
         (pn_chain_pack: ~3-7 MB written); rebuilt on every call for the same reason as `packed`.  The rebuild is IN PLACE on
         the caller's stream: code that runs forwards on several streams at once builds the pack once before the fork and
-        sets `_frozen` for the duration (parallel.concurrent_step, renderer.render_image)."""
+        sets `_frozen` for the duration (parallel.lanes)."""
         flat = self.flat_params()
         buf = self._chain.get(planes)
         if buf is None or buf.device != flat.device:
@@ -138,6 +138,10 @@ class RadianceMLP(torch.nn.Module):
             return buf
         _lib.call("pn_chain_pack", flat.data_ptr(), self.num_density_channels, planes, buf.data_ptr(), stream)
         return buf
+
+    def pack(self, stream, planes):
+        """The weight pack of a kernel family: planes = 0 layer-wise, 3 / 2 / 1 the fused chains (render._planes_of)."""
+        return self.chain_packed(stream, planes) if planes else self.packed(stream)
 
     def grad_views(self, flat_grad):
         return [flat_grad[self._offsets[k]:self._offsets[k] + p.numel()].view(p.shape) for k, p in self.named_in_order()]

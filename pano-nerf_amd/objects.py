@@ -76,10 +76,6 @@ def _cuda(*named):
     return dev
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _rows3(t, name, R=None):
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
         raise ValueError(f"{name} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
@@ -148,7 +144,7 @@ def _prepare(v, f, dev, accel):
         if accel.F != F or accel.device != dev:
             raise ValueError(f"accel is a MeshBVH of {accel.F} faces on {accel.device}; the mesh has {F} on {dev}")
         return accel
-    st = _stream(dev)
+    st = _lib.stream(dev)
     tris = torch.empty(F, 12, dtype=torch.float32, device=dev)
     _lib.call("pn_tri_setup", F, int(v.shape[0]), v.data_ptr(), f.data_ptr(), tris.data_ptr(), st)
     lo, hi = v.amin(0), v.amax(0)
@@ -206,7 +202,7 @@ def trace_mesh(origins, directions, vertices, faces, t_max=None, any_hit=False, 
             name, nodes = mesh._entry("pn_trace_mesh")
             sphere = () if nodes else (mesh.bsphere.data_ptr(),)  # a walk has its boxes: pn_trace_mesh_bvh takes no sphere
             _lib.call(name, R, o.data_ptr(), d.data_ptr(), mesh.F, mesh.tris.data_ptr(), *nodes, _lib.ptr(tm), *sphere,
-                      int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit), _stream(dev))
+                      int(bool(any_hit)), _lib.ptr(t), _lib.ptr(face), _lib.ptr(bary), _lib.ptr(hit), _lib.stream(dev))
     return hit.bool() if any_hit else (t, face, bary)
 
 
@@ -250,7 +246,7 @@ def shade(probes, albedo, normals, viewdirs, roughness=None, weights=None):
         if R:
             _lib.call("pn_shade", R, K, H, W, x.data_ptr(), sp, sc, sw, dirs.data_ptr(), omega.data_ptr(), a.data_ptr(),
                       n.data_ptr(), vd.data_ptr(), _lib.ptr(rough_t), rough_all, int(micro), _lib.ptr(w), rgb.data_ptr(),
-                      diffuse.data_ptr(), specular.data_ptr(), _lib.ptr(shading), _stream(dev))
+                      diffuse.data_ptr(), specular.data_ptr(), _lib.ptr(shading), _lib.stream(dev))
     return rgb, diffuse, specular, shading
 
 
@@ -278,7 +274,7 @@ def shadow_ratio(points, normals, probe, vertices, faces, bias=1e-3, accel=None)
             mesh = _prepare(v, f, dev, accel)
             name, nodes = mesh._entry("pn_shadow_ratio")
             _lib.call(name, R, H, W, x.data_ptr(), sc, sw, dirs.data_ptr(), omega.data_ptr(), p.data_ptr(), n.data_ptr(),
-                      float(bias), mesh.F, _lib.ptr(mesh.tris), *nodes, _lib.ptr(mesh.bsphere), out.data_ptr(), _stream(dev))
+                      float(bias), mesh.F, _lib.ptr(mesh.tris), *nodes, _lib.ptr(mesh.bsphere), out.data_ptr(), _lib.stream(dev))
     return out
 
 
@@ -335,8 +331,8 @@ class Texture:
             self.data = torch.empty(n // 4, 4, dtype=torch.float32, device=dev)
             table = torch.from_numpy(_decode_table(srgb)).to(dev) if is_u8 else None
             _lib.call("pn_tex_ingest", self.H, self.W, self.C, int(is_u8), img.data_ptr(), _lib.ptr(table),
-                      self.data.data_ptr(), _stream(dev))
-            _lib.call("pn_tex_pyramid", self.H, self.W, self.data.data_ptr(), _stream(dev))
+                      self.data.data_ptr(), _lib.stream(dev))
+            _lib.call("pn_tex_pyramid", self.H, self.W, self.data.data_ptr(), _lib.stream(dev))
             for x in (img, table):  # the launches above read them on this stream
                 if x is not None:
                     x.record_stream(torch.cuda.current_stream(dev))
@@ -555,7 +551,7 @@ def _texture_hits(obj, R, mask, face, bary, d, t, normals_in, radii, albedo, rou
               normals_in.data_ptr(), _lib.ptr(radii), int(obj.vertices.shape[0]), obj.vertices.data_ptr(),
               int(obj.faces.shape[0]), obj.faces.data_ptr(), int(obj.uv.shape[0]), obj.uv.data_ptr(),
               _lib.ptr(obj.face_uv), *tex, _WRAP[obj.wrap], int(obj.flip_v), _lib.ptr(albedo), _lib.ptr(roughness),
-              _lib.ptr(normals), _lib.ptr(lod), _stream(dev))
+              _lib.ptr(normals), _lib.ptr(lod), _lib.stream(dev))
 
 
 def _hit_rows(R, t, face, bary, radii, scene_dep, mismatch):
@@ -644,7 +640,7 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
                       _lib.ptr(dep), int(obj.vertices.shape[0]), obj.vertices.data_ptr(), int(obj.faces.shape[0]),
                       obj.faces.data_ptr(), _lib.ptr(obj.normals), _lib.ptr(obj.vertex_albedo), *col, K, _lib.ptr(pos),
                       mask.data_ptr(), out["points"].data_ptr(), out["normals"].data_ptr(), out["albedo"].data_ptr(),
-                      out["viewdirs"].data_ptr(), _lib.ptr(weights), _lib.ptr(spoints), _stream(dev))
+                      out["viewdirs"].data_ptr(), _lib.ptr(weights), _lib.ptr(spoints), _lib.stream(dev))
         if obj.textured:
             rough = e(R) if obj.roughness_map is not None else None
             _texture_hits(obj, R, mask, ff, bb, d, tt, out["normals"], rad, out["albedo"], rough, out["normals"], None, dev)
@@ -697,7 +693,7 @@ def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, nea
         depth = torch.empty(R, dtype=torch.float32, device=dev)
         m8 = mask.to(torch.uint8)
         _lib.call("pn_object_composite", R, m8.data_ptr(), object_rgb.data_ptr(), t.data_ptr(), s_rgb.data_ptr(),
-                  s_dep.reshape(R).data_ptr(), shadow.data_ptr(), rgb.data_ptr(), depth.data_ptr(), _stream(dev))
+                  s_dep.reshape(R).data_ptr(), shadow.data_ptr(), rgb.data_ptr(), depth.data_ptr(), _lib.stream(dev))
     img = lambda x: x.reshape(1, H, W, -1).permute(0, 3, 1, 2)
     return dict(scene_rgb=scene["fine_rgb"], scene_dep=scene["fine_dep"], scene_nor=scene["fine_nor"],
                 mask=img(mask.to(torch.float32)), object_rgb=img(object_rgb), shadow=img(shadow), rgb=img(rgb),

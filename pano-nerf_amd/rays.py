@@ -27,10 +27,6 @@ def namedtuple_map(fn, tup):
     return type(tup)(*map(fn, tup))
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _cuda_device(device):
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -49,7 +45,7 @@ def generate_pano_rays(h, w, c2w, near=0.0, far=10.0, device="cuda"):
     out = [torch.empty(h * w, d, dtype=torch.float32, device=device) for d in _DIMS]
     with torch.cuda.device(device):
         _lib.call("pn_raygen_pano", int(h), int(w), c.ctypes.data, float(near), float(far),
-                  *[t.data_ptr() for t in out], _stream(device))
+                  *[t.data_ptr() for t in out], _lib.stream(device))
     return Rays(*out)
 
 
@@ -63,7 +59,7 @@ def generate_lit_rays(num, radius, near=0.0, far=10.0, device="cuda"):
     device = torch.device(device)
     buf = torch.empty(14 * num, dtype=torch.float16, device=device)
     with torch.cuda.device(device):
-        _lib.call("pn_lit_rays", int(num), float(radius), float(near), float(far), buf.data_ptr(), _stream(device))
+        _lib.call("pn_lit_rays", int(num), float(radius), float(near), float(far), buf.data_ptr(), _lib.stream(device))
     v3 = buf[:9 * num].view(3, num, 3)
     s = buf[9 * num:].view(5, num, 1)
     return Rays(v3[0], v3[1], v3[2], s[0], s[1], s[2], s[3], s[4])
@@ -113,7 +109,7 @@ class CameraRig:
             outs = [torch.empty(B, d, dtype=torch.float32, device=dev) for d in _DIMS]
             rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if rgb_pool is not None else None
             _lib.call(self._entry, B, *self._head, idx.data_ptr(), *self._mats, float(near), float(far), _lib.ptr(rgb_pool),
-                      *[x.data_ptr() for x in outs], _lib.ptr(rgb), _stream(dev))
+                      *[x.data_ptr() for x in outs], _lib.ptr(rgb), _lib.stream(dev))
         return Rays(*outs), rgb
 
 

@@ -83,37 +83,6 @@ class _Cfg:
         self.__dict__.update(kw)
 
 
-def _mlp_forward(ev, params, wpack, st):
-    if ev.planes:
-        _lib.call("pn_chain_forward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, ev.planes, wpack.data_ptr(),
-                  ev.mean.data_ptr(), ev.cov.data_ptr(), ev.viewdirs.data_ptr(), ev.viewtab.data_ptr(), ev.enc.data_ptr(),
-                  _lib.ptr(ev.acts),
-                  ev.masks.data_ptr(), ev.raw_rgb.data_ptr(), ev.raw_den.data_ptr(), _lib.ptr(ev.amax), ev.tfmt, 0, st)
-        return
-    _lib.call("pn_mlp_forward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, params.data_ptr(), wpack.data_ptr(),
-              ev.mean.data_ptr(), ev.cov.data_ptr(), ev.viewdirs.data_ptr(), ev.enc.data_ptr(), ev.viewenc.data_ptr(),
-              ev.viewbias.data_ptr(), ev.acts.data_ptr(), ev.masks.data_ptr(), ev.raw_rgb.data_ptr(),
-              ev.raw_den.data_ptr(), st)
-
-
-def _composite_forward(ev, R, N, cfg, white, dirs, dir_mod, st):
-    dev = ev.raw_rgb.device
-    comp = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    dist = torch.empty(R, dtype=torch.float32, device=dev)
-    acc = torch.empty(R, dtype=torch.float32, device=dev)
-    w = torch.empty(R, N, dtype=torch.float32, device=dev)
-    _lib.call("pn_composite_forward", R, N, ev.nc, cfg.density_bias, cfg.rgb_padding, int(white), ev.raw_rgb.data_ptr(),
-              ev.raw_den.data_ptr(), ev.t.data_ptr(), dirs.data_ptr(), dir_mod, comp.data_ptr(), dist.data_ptr(),
-              acc.data_ptr(), w.data_ptr(), st)
-    return comp, dist, acc, w
-
-
-def _composite_backward(ev, R, N, cfg, white, dirs, dir_mod, d_comp, d_dist, d_w, d_raw_rgb, d_raw_den, st):
-    _lib.call("pn_composite_backward", R, N, ev.nc, cfg.density_bias, cfg.rgb_padding, int(white),
-              ev.raw_rgb.data_ptr(), ev.raw_den.data_ptr(), ev.t.data_ptr(), dirs.data_ptr(), dir_mod,
-              d_comp.data_ptr(), _lib.ptr(d_dist), _lib.ptr(d_w), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(), st)
-
-
 _SIDE = {}
 
 
@@ -125,33 +94,6 @@ def _side_stream(dev):
     return _SIDE[key]
 
 
-def _mlp_backward(ev, cfg, params, wpack, d_raw_rgb, d_raw_den, v, d_mean, flat_grad, st, defer=False, deferred=()):
-    """One evaluation's backward.  `defer=True` leaves its trunk weight-gradient operands in the returned workspace;
-    the last call of the step passes those as `deferred` = [(eval, work, had_tangent), ...] and reduces them all in
-    one GEMM per layer."""
-    import ctypes
-    m_batched = ev.M * (2 if v is not None else 1) + sum(e.M * (2 if t else 1) for e, _, t in deferred)
-    n = int(_lib.load().pn_mlp_backward_work_floats(ev.M, ev.rows_per_ray, ev.view_rows, m_batched if deferred else 0))
-    work = torch.empty(n, dtype=torch.float32, device=flat_grad.device)
-    nd = len(deferred)
-    if nd:
-        dM = (ctypes.c_int64 * nd)(*[e.M for e, _, _ in deferred])
-        denc = (ctypes.c_void_p * nd)(*[e.enc.data_ptr() for e, _, _ in deferred])
-        dacts = (ctypes.c_void_p * nd)(*[e.acts.data_ptr() for e, _, _ in deferred])
-        drs = (ctypes.c_void_p * nd)(*[(e.rsweep.data_ptr() if t else None) for e, _, t in deferred])
-        dwork = (ctypes.c_void_p * nd)(*[w.data_ptr() for _, w, _ in deferred])
-        dtan = (ctypes.c_int * nd)(*[int(bool(t)) for _, _, t in deferred])
-    else:
-        dM = denc = dacts = drs = dwork = dtan = None
-    _lib.call("pn_mlp_backward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, cfg.density_bias, params.data_ptr(),
-              wpack.data_ptr(), ev.mean.data_ptr(), ev.cov.data_ptr(), ev.enc.data_ptr(), ev.viewenc.data_ptr(),
-              ev.acts.data_ptr(), ev.masks.data_ptr(), ev.raw_den.data_ptr(), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(),
-              _lib.ptr(ev.rsweep), _lib.ptr(v), _lib.ptr(d_mean), flat_grad.data_ptr(), work.data_ptr(),
-              m_batched if deferred else 0, int(defer), nd, dM, denc, dacts, drs, dwork, dtan, st,
-              _side_stream(flat_grad.device).cuda_stream if cfg.overlap else None)
-    return work
-
-
 class _ChainEvalC(ctypes.Structure):
     """PnChainEval of include/panonerf_hip.h"""
     _fields_ = [("M", ctypes.c_int64), ("enc_t", ctypes.c_void_p), ("acts_t", ctypes.c_void_p),
@@ -160,77 +102,184 @@ class _ChainEvalC(ctypes.Structure):
                 ("tang_t", ctypes.c_void_p), ("coef_t", ctypes.c_void_p), ("amax", ctypes.c_void_p)]
 
 
-def _chain_tangent(ev, cfg, params, pack, v, st, wgs=0):
-    """Forward-mode tangent sweep along v = dL/d(grad_mean): edot, hdot_0..7 (with r_l: the second-order weight gradients)
-    and sdot (the second-order addend of the backward chain's density seed)."""
-    dev = v.device
-    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    Mp = ev.Mp
-    ev.edot, ev.tang, ev.sdot = e(Mp * 96), e(8 * Mp * 256), e(ev.M)
-    _lib.call("pn_chain_tangent", ev.M, ev.nc, ev.planes, params.data_ptr(), pack.data_ptr(), ev.mean.data_ptr(),
-              ev.cov.data_ptr(), ev.masks.data_ptr(), v.data_ptr(), ev.edot.data_ptr(), ev.tang.data_ptr(),
-              ev.sdot.data_ptr(), _lib.ptr(ev.amax), ev.tfmt, wgs, st)
-    ev.coef = e(Mp * 32)
+class _Field:
+    """The radiance field as one call sees it: everything that is fixed for the call (the mode's kernel family and T
+    format, the flat parameter block, the mode's weight pack - built here, once - and the stream) and the only code that
+    knows which entry point evaluates it.  Every MLP evaluation of the package goes through one of these: the renderer,
+    geometry.query_field, lighting.field_irradiance."""
+
+    def __init__(self, cfg, mlp, dev, st):
+        self.nc, self.density_bias, self.rgb_padding = cfg.nc, cfg.density_bias, cfg.rgb_padding
+        self.disable_integration, self.num_env_samples = cfg.disable_integration, cfg.num_env_samples
+        self.planes, self.tfmt = cfg.planes, cfg.tfmt
+        self.overlap, self.batch_wgrad = cfg.overlap, cfg.batch_wgrad
+        self.concurrent = bool(cfg.planes) and bool(cfg.overlap)  # the weight-gradient schedule of _RenderFn.backward
+        self.dev, self.st = dev, st
+        self.params = mlp.flat_params()
+        self.pack = mlp.pack(st, cfg.planes)
+
+    @classmethod
+    def of(cls, model, dev):
+        """The field of `model` on the device's current stream (callers outside the renderer)."""
+        return cls(model._cfg(), model.mlp, dev, _lib.stream(dev))
+
+    def _empty(self, *s):
+        return torch.empty(*s, dtype=torch.float32, device=self.dev)
+
+    def evaluation(self, M, rows_per_ray, viewdirs, keep):
+        return _Eval(M, rows_per_ray, viewdirs, self.nc, self.dev, self.planes, keep, self.tfmt)
+
+    def forward(self, ev):
+        if self.planes:
+            _lib.call("pn_chain_forward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, ev.planes, self.pack.data_ptr(),
+                      ev.mean.data_ptr(), ev.cov.data_ptr(), ev.viewdirs.data_ptr(), ev.viewtab.data_ptr(), ev.enc.data_ptr(),
+                      _lib.ptr(ev.acts),
+                      ev.masks.data_ptr(), ev.raw_rgb.data_ptr(), ev.raw_den.data_ptr(), _lib.ptr(ev.amax), ev.tfmt, 0, self.st)
+            return
+        _lib.call("pn_mlp_forward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, self.params.data_ptr(), self.pack.data_ptr(),
+                  ev.mean.data_ptr(), ev.cov.data_ptr(), ev.viewdirs.data_ptr(), ev.enc.data_ptr(), ev.viewenc.data_ptr(),
+                  ev.viewbias.data_ptr(), ev.acts.data_ptr(), ev.masks.data_ptr(), ev.raw_rgb.data_ptr(),
+                  ev.raw_den.data_ptr(), self.st)
+
+    def density_grad(self, ev, keep, out=None):
+        """d sigma / d mean of a forwarded evaluation -> ev.gmean ([M, 3]; `out` if given).  The sweep vectors stay on
+        `ev.rsweep` for the second-order backward when `keep`; the chains then need one slot only for inference, the
+        layer-wise kernels all eight and a scratch either way."""
+        ev.rsweep = self._empty(8 if (keep or not self.planes) else 1, ev.Mp, 256)
+        ev.gmean = out if out is not None else self._empty(ev.M, 3)
+        if self.planes:
+            _lib.call("pn_chain_density_grad", ev.M, ev.nc, self.planes, self.density_bias, self.params.data_ptr(),
+                      self.pack.data_ptr(), ev.mean.data_ptr(), ev.cov.data_ptr(), ev.masks.data_ptr(),
+                      ev.raw_den.data_ptr(), ev.rsweep.data_ptr(), int(keep), ev.gmean.data_ptr(),
+                      _lib.ptr(ev.amax), ev.tfmt, 0, self.st)
+        else:
+            scratch = self._empty(ev.Mp, 96)
+            _lib.call("pn_density_grad", ev.M, ev.nc, self.density_bias, self.params.data_ptr(), self.pack.data_ptr(),
+                      ev.mean.data_ptr(), ev.cov.data_ptr(), ev.acts.data_ptr(), ev.masks.data_ptr(),
+                      ev.raw_den.data_ptr(), ev.rsweep.data_ptr(), scratch.data_ptr(), ev.gmean.data_ptr(), self.st)
+        if not keep:
+            ev.rsweep = None
+        return ev.gmean
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, ev, d_raw_rgb, d_raw_den, v, d_mean, flat_grad, pending, last=False):
+        """Serial schedule: the data gradients of one evaluation now, its weight gradients with those of the step's other
+        evaluations (`pending`, the caller's list) in the call with last=True - one TN GEMM per layer over all their rows.
+        The layer-wise kernels fold that reduction into the last evaluation's own pn_mlp_backward; with batch_wgrad off
+        they reduce every evaluation at once."""
+        if self.planes:
+            self.chain_backward(ev, d_raw_rgb, d_raw_den, v, d_mean)
+            pending.append(ev)
+            if last:
+                self.chain_wgrad(pending, flat_grad, self.st)
+        elif last:
+            self._layer_backward(ev, d_raw_rgb, d_raw_den, v, d_mean, flat_grad, deferred=pending)
+        else:
+            work = self._layer_backward(ev, d_raw_rgb, d_raw_den, v, d_mean, flat_grad, defer=self.batch_wgrad)
+            if self.batch_wgrad:
+                pending.append((ev, work, v is not None))
+
+    def _layer_backward(self, ev, d_raw_rgb, d_raw_den, v, d_mean, flat_grad, defer=False, deferred=()):
+        """One evaluation's backward.  `defer=True` leaves its trunk weight-gradient operands in the returned workspace;
+        the last call of the step passes those as `deferred` = [(eval, work, had_tangent), ...] and reduces them all in
+        one GEMM per layer."""
+        m_batched = ev.M * (2 if v is not None else 1) + sum(e.M * (2 if t else 1) for e, _, t in deferred)
+        n = int(_lib.load().pn_mlp_backward_work_floats(ev.M, ev.rows_per_ray, ev.view_rows, m_batched if deferred else 0))
+        work = torch.empty(n, dtype=torch.float32, device=flat_grad.device)
+        nd = len(deferred)
+        if nd:
+            dM = (ctypes.c_int64 * nd)(*[e.M for e, _, _ in deferred])
+            denc = (ctypes.c_void_p * nd)(*[e.enc.data_ptr() for e, _, _ in deferred])
+            dacts = (ctypes.c_void_p * nd)(*[e.acts.data_ptr() for e, _, _ in deferred])
+            drs = (ctypes.c_void_p * nd)(*[(e.rsweep.data_ptr() if t else None) for e, _, t in deferred])
+            dwork = (ctypes.c_void_p * nd)(*[w.data_ptr() for _, w, _ in deferred])
+            dtan = (ctypes.c_int * nd)(*[int(bool(t)) for _, _, t in deferred])
+        else:
+            dM = denc = dacts = drs = dwork = dtan = None
+        _lib.call("pn_mlp_backward", ev.M, ev.rows_per_ray, ev.view_rows, ev.nc, self.density_bias, self.params.data_ptr(),
+                  self.pack.data_ptr(), ev.mean.data_ptr(), ev.cov.data_ptr(), ev.enc.data_ptr(), ev.viewenc.data_ptr(),
+                  ev.acts.data_ptr(), ev.masks.data_ptr(), ev.raw_den.data_ptr(), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(),
+                  _lib.ptr(ev.rsweep), _lib.ptr(v), _lib.ptr(d_mean), flat_grad.data_ptr(), work.data_ptr(),
+                  m_batched if deferred else 0, int(defer), nd, dM, denc, dacts, drs, dwork, dtan, self.st,
+                  _side_stream(flat_grad.device).cuda_stream if self.overlap else None)
+        return work
+
+    def chain_tangent(self, ev, v, wgs=0):
+        """Forward-mode tangent sweep along v = dL/d(grad_mean): edot, hdot_0..7 (with r_l: the second-order weight gradients)
+        and sdot (the second-order addend of the backward chain's density seed)."""
+        e, Mp = self._empty, ev.Mp
+        ev.edot, ev.tang, ev.sdot = e(Mp * 96), e(8 * Mp * 256), e(ev.M)
+        _lib.call("pn_chain_tangent", ev.M, ev.nc, ev.planes, self.params.data_ptr(), self.pack.data_ptr(), ev.mean.data_ptr(),
+                  ev.cov.data_ptr(), ev.masks.data_ptr(), v.data_ptr(), ev.edot.data_ptr(), ev.tang.data_ptr(),
+                  ev.sdot.data_ptr(), _lib.ptr(ev.amax), ev.tfmt, wgs, self.st)
+        ev.coef = e(Mp * 32)
+
+    def chain_backward(self, ev, d_raw_rgb, d_raw_den, v, d_mean, wgs=0):
+        """Fused data-gradient chain of one evaluation (tangent sweep first when v = dL/d(grad_mean) is given, unless the caller
+        ran it: ev.sdot set); leaves the T32 tensors the weight-gradient GEMMs read on `ev`.  wgs: workgroup budget (0 = all CUs)."""
+        e, Mp = self._empty, ev.Mp
+        # (no fills: the kernels write every feature of every padded row of drgb / d8 / coef themselves)
+        if v is None:
+            ev.edot = ev.tang = ev.coef = ev.sdot = None
+        elif getattr(ev, "sdot", None) is None:
+            self.chain_tangent(ev, v, wgs)
+        ev.drgb, ev.dhv, ev.d8, ev.delta = e(Mp * 32), e(Mp * 128), e(Mp * 288), e(8 * Mp * 256)
+        _lib.call("pn_chain_backward", ev.M, ev.nc, ev.planes, self.density_bias, self.pack.data_ptr(), ev.masks.data_ptr(),
+                  ev.raw_den.data_ptr(), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(), _lib.ptr(ev.sdot), ev.mean.data_ptr(),
+                  ev.cov.data_ptr(), ev.drgb.data_ptr(), ev.dhv.data_ptr(), ev.d8.data_ptr(), ev.delta.data_ptr(),
+                  _lib.ptr(ev.coef), _lib.ptr(d_mean), _lib.ptr(ev.amax), ev.tfmt, wgs, self.st)
+
+    def chain_wgrad(self, evals, flat_grad, st, which=3, wgs=0):
+        """One TN GEMM per layer over the sample blocks of the given evaluations (all of the step's, or - concurrent schedule -
+        one at a time, on the side stream `st`).  which: 1 first-order products, 2 second-order trunk rows, 3 both
+        (include/panonerf_hip.h)."""
+        lib = _lib.load()
+        arr = (_ChainEvalC * len(evals))()
+        for i, ev in enumerate(evals):
+            second = ev.tang is not None
+            first = bool(which & 1)  # (the second-order trunk rows alone are reduced before the evaluation's backward chain has run)
+            arr[i] = _ChainEvalC(ev.M, ev.enc.data_ptr(), ev.acts.data_ptr(), ev.drgb.data_ptr() if first else None,
+                                 ev.dhv.data_ptr() if first else None, ev.d8.data_ptr() if first else None,
+                                 ev.delta.data_ptr() if first else None, ev.rsweep.data_ptr() if second else None,
+                                 ev.edot.data_ptr() if second else None, ev.tang.data_ptr() if second else None,
+                                 ev.coef.data_ptr() if second else None, _lib.ptr(ev.amax))
+        n = int(lib.pn_chain_wgrad_work_floats())
+        work = torch.empty(n, dtype=torch.float32, device=flat_grad.device)
+        _lib.check(lib.pn_chain_wgrad(len(evals), ctypes.cast(arr, ctypes.c_void_p), self.nc, self.planes, flat_grad.data_ptr(),
+                                      work.data_ptr(), n, which, evals[0].tfmt, wgs, st), "pn_chain_wgrad")
+        return work
+def _composite_forward(f, ev, R, N, white, dirs, dir_mod):
+    e = f._empty
+    comp, dist, acc, w = e(R, 3), e(R), e(R), e(R, N)
+    _lib.call("pn_composite_forward", R, N, ev.nc, f.density_bias, f.rgb_padding, int(white), ev.raw_rgb.data_ptr(),
+              ev.raw_den.data_ptr(), ev.t.data_ptr(), dirs.data_ptr(), dir_mod, comp.data_ptr(), dist.data_ptr(),
+              acc.data_ptr(), w.data_ptr(), f.st)
+    return comp, dist, acc, w
 
 
-def _chain_backward(ev, cfg, params, pack, d_raw_rgb, d_raw_den, v, d_mean, st, wgs=0):
-    """Fused data-gradient chain of one evaluation (tangent sweep first when v = dL/d(grad_mean) is given, unless the caller
-    ran it: ev.sdot set); leaves the T32 tensors the weight-gradient GEMMs read on `ev`.  wgs: workgroup budget (0 = all CUs)."""
-    dev = d_raw_rgb.device
-    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    # (no fills: the kernels write every feature of every padded row of drgb / d8 / coef themselves)
-    Mp = ev.Mp
-    if v is None:
-        ev.edot = ev.tang = ev.coef = ev.sdot = None
-    elif getattr(ev, "sdot", None) is None:
-        _chain_tangent(ev, cfg, params, pack, v, st, wgs)
-    ev.drgb, ev.dhv, ev.d8, ev.delta = e(Mp * 32), e(Mp * 128), e(Mp * 288), e(8 * Mp * 256)
-    _lib.call("pn_chain_backward", ev.M, ev.nc, ev.planes, cfg.density_bias, pack.data_ptr(), ev.masks.data_ptr(),
-              ev.raw_den.data_ptr(), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(), _lib.ptr(ev.sdot), ev.mean.data_ptr(),
-              ev.cov.data_ptr(), ev.drgb.data_ptr(), ev.dhv.data_ptr(), ev.d8.data_ptr(), ev.delta.data_ptr(),
-              _lib.ptr(ev.coef), _lib.ptr(d_mean), _lib.ptr(ev.amax), ev.tfmt, wgs, st)
+def _composite_backward(f, ev, R, N, white, dirs, dir_mod, d_comp, d_dist, d_w, d_raw_rgb, d_raw_den):
+    _lib.call("pn_composite_backward", R, N, ev.nc, f.density_bias, f.rgb_padding, int(white),
+              ev.raw_rgb.data_ptr(), ev.raw_den.data_ptr(), ev.t.data_ptr(), dirs.data_ptr(), dir_mod,
+              d_comp.data_ptr(), _lib.ptr(d_dist), _lib.ptr(d_w), d_raw_rgb.data_ptr(), d_raw_den.data_ptr(), f.st)
 
 
-def _chain_wgrad(evals, nc, planes, flat_grad, st, which=3, wgs=0):
-    """One TN GEMM per layer over the sample blocks of the given evaluations (all of the step's, or - concurrent schedule -
-    one at a time).  which: 1 first-order products, 2 second-order trunk rows, 3 both (include/panonerf_hip.h)."""
-    lib = _lib.load()
-    arr = (_ChainEvalC * len(evals))()
-    for i, ev in enumerate(evals):
-        second = ev.tang is not None
-        first = bool(which & 1)  # (the second-order trunk rows alone are reduced before the evaluation's backward chain has run)
-        arr[i] = _ChainEvalC(ev.M, ev.enc.data_ptr(), ev.acts.data_ptr(), ev.drgb.data_ptr() if first else None,
-                             ev.dhv.data_ptr() if first else None, ev.d8.data_ptr() if first else None,
-                             ev.delta.data_ptr() if first else None, ev.rsweep.data_ptr() if second else None,
-                             ev.edot.data_ptr() if second else None, ev.tang.data_ptr() if second else None,
-                             ev.coef.data_ptr() if second else None, _lib.ptr(ev.amax))
-    n = int(lib.pn_chain_wgrad_work_floats())
-    work = torch.empty(n, dtype=torch.float32, device=flat_grad.device)
-    _lib.check(lib.pn_chain_wgrad(len(evals), ctypes.cast(arr, ctypes.c_void_p), nc, planes, flat_grad.data_ptr(),
-                                  work.data_ptr(), n, which, evals[0].tfmt, wgs, st), "pn_chain_wgrad")
-    return work
-
-
-def _light_gather(cfg, params, wpack, o, d, dist, env_d, env_rad, env_near, env_far, env_omega, env_rand, albedo, normal,
-                  keep, st):
+def _light_gather(f, o, d, dist, env_d, env_rad, env_near, env_far, env_omega, env_rand, albedo, normal, keep):
     """The light estimate at x_surf = o + d * dist (models/pano_mip_nerf.py:319-359): D light rays of Ne samples each
     through the field, composited, then the Lambertian sums of the surface shading (utils/surface_rendering.py:104-165).
     Shared by the renderer and lighting.field_irradiance.  -> (env evaluation, env_rgb [B D, 3], diffuse, shading)."""
-    dev, B, nc, planes = o.device, o.shape[0], cfg.nc, cfg.planes
-    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    D, Ne = env_d.shape[0], cfg.num_env_samples
-    ee = _Eval(B * D * Ne, Ne, env_d, nc, dev, planes, keep, cfg.tfmt)
+    B, D, Ne, e = o.shape[0], env_d.shape[0], f.num_env_samples, f._empty
+    ee = f.evaluation(B * D * Ne, Ne, env_d, keep)
     ee.t = e(B * D, Ne + 1)
     _lib.call("pn_sample_env", B, D, Ne, o.data_ptr(), d.data_ptr(), dist.data_ptr(), env_d.data_ptr(),
               env_rad.data_ptr(), env_near.data_ptr(), env_far.data_ptr(), _lib.ptr(env_rand),
-              ee.t.data_ptr(), ee.mean.data_ptr(), ee.cov.data_ptr(), st)
-    if cfg.disable_integration:
+              ee.t.data_ptr(), ee.mean.data_ptr(), ee.cov.data_ptr(), f.st)
+    if f.disable_integration:
         ee.cov.zero_()
-    _mlp_forward(ee, params, wpack, st)
-    env_rgb, _, _, _ = _composite_forward(ee, B * D, Ne, cfg, False, env_d, D, st)
+    f.forward(ee)
+    env_rgb, _, _, _ = _composite_forward(f, ee, B * D, Ne, False, env_d, D)
     diffuse, shading = e(B, 3), e(B, 3)
     _lib.call("pn_surface_forward", B, D, env_rgb.data_ptr(), albedo.data_ptr(), normal.data_ptr(),
-              env_d.data_ptr(), env_omega.data_ptr(), diffuse.data_ptr(), shading.data_ptr(), st)
+              env_d.data_ptr(), env_omega.data_ptr(), diffuse.data_ptr(), shading.data_ptr(), f.st)
     return ee, env_rgb, diffuse, shading
 
 
@@ -246,51 +295,37 @@ class _RenderFn(torch.autograd.Function):
             raise RuntimeError("pano_nerf_amd renders on a HIP device only (tensors are on %s); there is no CPU "
                                "fallback" % dev)
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            params = mlp.flat_params()
-            planes = cfg.planes
-            wpack = mlp.chain_packed(st, planes) if planes else mlp.packed(st)
+            st = _lib.stream(dev)
+            f = _Field(cfg, mlp, dev, st)
             B, N, nc = o.shape[0], cfg.num_samples, cfg.nc
             S, M = N + 1, o.shape[0] * cfg.num_samples
-            e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+            e = f._empty
             keep = cfg.keep  # inference (no_grad): release the big activation buffers as soon as possible
             # ---- level 0: stratified samples
-            e0 = _Eval(M, N, vd, nc, dev, planes, keep, cfg.tfmt)
+            e0 = f.evaluation(M, N, vd, keep)
             e0.t = e(B, S)
             _lib.call("pn_sample_coarse", B, N, int(cfg.disparity), o.data_ptr(), d.data_ptr(), radii.data_ptr(), near.data_ptr(),
                       far.data_ptr(), _lib.ptr(t_rand), e0.t.data_ptr(), e0.mean.data_ptr(), e0.cov.data_ptr(), st)
             if cfg.disable_integration:  # models/pano_mip_nerf.py:241-243: every encoding of compute_graph sees a zero covariance
                 e0.cov.zero_()
-            _mlp_forward(e0, params, wpack, st)
-            comp0, dist0, _, w0 = _composite_forward(e0, B, N, cfg, cfg.white_bkgd, d, B, st)
+            f.forward(e0)
+            comp0, dist0, _, w0 = _composite_forward(f, e0, B, N, cfg.white_bkgd, d, B)
             if not keep:
                 e0.acts = e0.masks = e0.enc = None
             # ---- level 1: PDF resample (no gradient through the weights: stop_resample_grad)
-            e1 = _Eval(M, N, vd, nc, dev, planes, keep, cfg.tfmt)
+            e1 = f.evaluation(M, N, vd, keep)
             e1.t = e(B, S)
             _lib.call("pn_resample", B, N, e0.t.data_ptr(), w0.data_ptr(), cfg.resample_padding, _lib.ptr(u_rand),
                       o.data_ptr(), d.data_ptr(), radii.data_ptr(), e1.t.data_ptr(), e1.mean.data_ptr(),
                       e1.cov.data_ptr(), st)
             if cfg.disable_integration:
                 e1.cov.zero_()
-            _mlp_forward(e1, params, wpack, st)
-            comp1, dist1, _, w1 = _composite_forward(e1, B, N, cfg, cfg.white_bkgd, d, B, st)
+            f.forward(e1)
+            comp1, dist1, _, w1 = _composite_forward(f, e1, B, N, cfg.white_bkgd, d, B)
             normal = ort = albedo = surface = diffuse = shading = None
             ee = env_rgb = None
             if cfg.normals:
-                e1.rsweep = e(8 if (keep or not planes) else 1, e1.Mp, 256)
-                e1.gmean = e(M, 3)
-                scratch = None
-                if planes:
-                    _lib.call("pn_chain_density_grad", M, nc, planes, cfg.density_bias, params.data_ptr(),
-                              wpack.data_ptr(), e1.mean.data_ptr(), e1.cov.data_ptr(), e1.masks.data_ptr(),
-                              e1.raw_den.data_ptr(), e1.rsweep.data_ptr(), int(keep), e1.gmean.data_ptr(),
-                              _lib.ptr(e1.amax), e1.tfmt, 0, st)
-                else:
-                    scratch = e(e1.Mp, 96)
-                    _lib.call("pn_density_grad", M, nc, cfg.density_bias, params.data_ptr(), wpack.data_ptr(),
-                              e1.mean.data_ptr(), e1.cov.data_ptr(), e1.acts.data_ptr(), e1.masks.data_ptr(),
-                              e1.raw_den.data_ptr(), e1.rsweep.data_ptr(), scratch.data_ptr(), e1.gmean.data_ptr(), st)
+                f.density_grad(e1, keep)
                 normal = e(B, 3)
                 ort_ray = e(B) if cfg.use_ort else None
                 albedo = e(B, 3) if (cfg.surf and nc == 5) else None
@@ -298,14 +333,11 @@ class _RenderFn(torch.autograd.Function):
                           d.data_ptr(), normal.data_ptr(), _lib.ptr(ort_ray), _lib.ptr(albedo), st)
                 if cfg.use_ort:
                     ort = ort_ray.mean()
-                if not keep:
-                    e1.rsweep = None
-                    del scratch
             if not keep:
                 e1.acts = e1.masks = e1.enc = None
             if cfg.surf:
-                ee, env_rgb, diffuse, shading = _light_gather(cfg, params, wpack, o, d, dist1, env_d, env_rad, env_near,
-                                                              env_far, env_omega, env_rand, albedo, normal, keep, st)
+                ee, env_rgb, diffuse, shading = _light_gather(f, o, d, dist1, env_d, env_rad, env_near, env_far, env_omega,
+                                                              env_rand, albedo, normal, keep)
                 surface = diffuse.clone()
         ctx.cfg, ctx.mlp = cfg, mlp
         # `normal` and `albedo` are OUTPUTS of this Function: they go through save_for_backward (an output kept as a plain
@@ -313,10 +345,10 @@ class _RenderFn(torch.autograd.Function):
         # that is never back-propagated would leak its activation buffers).  The evaluation buffers are not outputs.
         ctx.has_normal, ctx.has_albedo = normal is not None, albedo is not None
         ctx.save_for_backward(*[x for x in (normal, albedo) if x is not None])
-        ctx.pack = (o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, params, wpack)
+        ctx.pack = (o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, f)
         ctx.param_version = mlp._version() if keep else None
         if getattr(mlp, "debug_keep", False):  # diagnostics only (tests/diag/diag_full.py, tests/test_gpu_grads.py)
-            mlp.debug_pack = (o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, albedo, normal, params, wpack)
+            mlp.debug_pack = (o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, albedo, normal, f.params, f.pack)
         outs = (comp0, dist0, comp1, dist1, ort, normal, albedo, surface, diffuse, shading)
         ctx.present = [x is not None for x in outs]
         return tuple(x if x is not None else torch.zeros((), device=dev) for x in outs)
@@ -327,7 +359,7 @@ class _RenderFn(torch.autograd.Function):
         cfg, mlp = ctx.cfg, ctx.mlp
         if ctx.pack is None:
             raise RuntimeError("pano_nerf_amd: backward through the same render twice (its buffers were released)")
-        o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, params, wpack = ctx.pack
+        o, d, vd, env_d, env_omega, e0, e1, ee, w1, env_rgb, f = ctx.pack
         saved = list(ctx.saved_tensors)
         normal = saved.pop(0) if ctx.has_normal else None
         albedo = saved.pop(0) if ctx.has_albedo else None
@@ -361,45 +393,16 @@ class _RenderFn(torch.autograd.Function):
         gz = lambda g, *s: _f32(g) if g is not None else z(*s)
         with torch.cuda.device(dev):
             main = torch.cuda.current_stream(dev)
-            st = main.cuda_stream
-            flat_grad = torch.zeros(params.numel(), dtype=torch.float32, device=dev)  # outlives this call (.grad views)
-            # CONCURRENT WEIGHT GRADIENTS (fused chains, cfg.overlap): the weight-gradient GEMMs of an evaluation start on a side
-            # stream as soon as its backward chain is done and run beside the next evaluation's chains, each kernel family on its
-            # share of the CUs (cfg.chain_wgs / cfg.wgrad_wgs: a chain workgroup and a 256-wide weight-gradient workgroup fill a
-            # CU each, so the two launches occupy disjoint CUs) - the chains are bound by matrix-instruction issue and their T
-            # stores, the weight gradients by their operand reads.  Level 0, whose gradient depends on nothing of level 1, goes
-            # first so that its weight gradients have the env-light and level-1 chains to run under; the second-order trunk rows
-            # of level 1 (r_l^T hdot_{l-1}: complete after the tangent sweep) run under its backward chain; only its first-order
-            # products are left for the end, on the whole chip.  All reductions into flat_grad happen on the side stream, in a
-            # fixed order.
-            conc = bool(cfg.planes) and bool(cfg.overlap)
-            side = _side_stream(dev) if conc else None
-            cw, ww = (cfg.chain_wgs, cfg.wgrad_wgs) if conc else (0, 0)
-            held = []  # workspaces of the side-stream jobs (kept until the join)
+            f.st = st = main.cuda_stream  # (the stream this backward runs on, which autograd makes the forward's)
+            flat_grad = torch.zeros(f.params.numel(), dtype=torch.float32, device=dev)  # outlives this call (.grad views)
 
-            def wg(evals, which=3, wgs=0):
-                if not conc:
-                    _chain_wgrad(evals, nc, cfg.planes, flat_grad, st, which, wgs)
-                    return
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    held.append(_chain_wgrad(evals, nc, cfg.planes, flat_grad, side.cuda_stream, which, wgs))
-
-            def level0():
-                d_rr0, d_rd0 = z(M, 3), z(M, nc)
-                _composite_backward(e0, B, N, cfg, cfg.white_bkgd, d, B, gz(g_comp0, B, 3), gz(g_dist0, B), None, d_rr0,
-                                    d_rd0, st)
-                return d_rr0, d_rd0
-
-            pending = []  # (evaluation, its workspace, ran the tangent sweep): weight gradients batched into the last call
-            if conc:
-                d_rr0, d_rd0 = level0()
-                _chain_backward(e0, cfg, params, wpack, d_rr0, d_rd0, None, None, st)  # (alone on the chip: every CU)
-                wg([e0], 3, ww)
-            d_dist1 = gz(g_dist1, B).clone() if g_dist1 is not None else z(B)  # (accumulated into below: a private buffer)
-            d_normal = gz(g_normal, B, 3) if cfg.normals else None
-            d_albedo = None
-            if cfg.surf:
+            # The three adjoint steps.  `bwd(ev, d_raw_rgb, d_raw_den, v, d_mean)` is the schedule's backward of one evaluation.
+            def env_light(bwd):
+                """Surface shading, env composite, env field, env origins -> (d_dist1, d_normal, d_albedo) entering level 1."""
+                d_dist1 = gz(g_dist1, B).clone() if g_dist1 is not None else z(B)  # (accumulated into below: a private buffer)
+                d_normal = gz(g_normal, B, 3) if cfg.normals else None
+                if not cfg.surf:
+                    return d_dist1, d_normal, None
                 D, Ne = env_d.shape[0], cfg.num_env_samples
                 if g_surface is not None and g_diffuse is not None:
                     d_dif = _f32(g_surface) + _f32(g_diffuse)
@@ -413,56 +416,65 @@ class _RenderFn(torch.autograd.Function):
                 d_albedo = gz(g_albedo, B, 3) + d_alb_s
                 d_normal = d_normal + d_nrm_s
                 d_rr, d_rd = z(ee.M, 3), z(ee.M, nc)
-                _composite_backward(ee, B * D, Ne, cfg, False, env_d, D, d_env, None, None, d_rr, d_rd, st)
+                _composite_backward(f, ee, B * D, Ne, False, env_d, D, d_env, None, None, d_rr, d_rd)
                 d_mean_e = z(ee.M, 3)
-                if cfg.planes:
-                    _chain_backward(ee, cfg, params, wpack, d_rr, d_rd, None, d_mean_e, st, cw)
-                    if conc:
-                        wg([ee], 3, ww)
-                    else:
-                        pending.append(ee)
-                else:
-                    pending.append((ee, _mlp_backward(ee, cfg, params, wpack, d_rr, d_rd, None, d_mean_e, flat_grad, st,
-                                                      defer=cfg.batch_wgrad), False))
+                bwd(ee, d_rr, d_rd, None, d_mean_e)
                 _lib.call("pn_env_origin_backward", B, D * Ne, d_mean_e.data_ptr(), d.data_ptr(), d_dist1.data_ptr(), st)
-            d_rr, d_rd = z(M, 3), z(M, nc)
-            d_w1 = v = None
-            if cfg.normals:
-                d_w1, v = z(B, N), z(M, 3)
-                d_ort_ray = None
-                if cfg.use_ort and g_ort is not None:
-                    d_ort_ray = (_f32(g_ort) / B).expand(B).contiguous()
-                _lib.call("pn_surf_gather_backward", B, N, nc, e1.gmean.data_ptr(), w1.data_ptr(),
-                          e1.raw_den.data_ptr(), d.data_ptr(), d_normal.data_ptr(), _lib.ptr(d_ort_ray),
-                          _lib.ptr(d_albedo), d_w1.data_ptr(), v.data_ptr(), d_rd.data_ptr(), st)
-            _composite_backward(e1, B, N, cfg, cfg.white_bkgd, d, B, gz(g_comp1, B, 3), d_dist1, d_w1, d_rr, d_rd, st)
-            if cfg.planes:
-                e1.sdot = None
-                if conc and v is not None:
-                    _chain_tangent(e1, cfg, params, wpack, v, st, cw)
-                    wg([e1], 2, ww)  # second-order trunk rows, under the backward chain
-                _chain_backward(e1, cfg, params, wpack, d_rr, d_rd, v, None, st, cw)
-                if conc:
-                    wg([e1], 1 if v is not None else 3, 0)  # what is left runs alone: every CU
-                else:
-                    pending.append(e1)
+                return d_dist1, d_normal, d_albedo
+
+            def level1(bwd, d_dist1, d_normal, d_albedo):
+                d_rr, d_rd = z(M, 3), z(M, nc)
+                d_w1 = v = None
+                if cfg.normals:
+                    d_w1, v = z(B, N), z(M, 3)
+                    d_ort_ray = None
+                    if cfg.use_ort and g_ort is not None:
+                        d_ort_ray = (_f32(g_ort) / B).expand(B).contiguous()
+                    _lib.call("pn_surf_gather_backward", B, N, nc, e1.gmean.data_ptr(), w1.data_ptr(),
+                              e1.raw_den.data_ptr(), d.data_ptr(), d_normal.data_ptr(), _lib.ptr(d_ort_ray),
+                              _lib.ptr(d_albedo), d_w1.data_ptr(), v.data_ptr(), d_rd.data_ptr(), st)
+                _composite_backward(f, e1, B, N, cfg.white_bkgd, d, B, gz(g_comp1, B, 3), d_dist1, d_w1, d_rr, d_rd)
+                bwd(e1, d_rr, d_rd, v, None)
+
+            def level0(bwd):
+                d_rr, d_rd = z(M, 3), z(M, nc)
+                _composite_backward(f, e0, B, N, cfg.white_bkgd, d, B, gz(g_comp0, B, 3), gz(g_dist0, B), None, d_rr, d_rd)
+                bwd(e0, d_rr, d_rd, None, None)
+
+            if not f.concurrent:
+                # SERIAL: env light, level 1, level 0, then the weight gradients of all three in one batched reduction
+                pending = []
+                bwd = lambda ev, *g: f.backward(ev, *g, flat_grad, pending, last=ev is e0)
+                level1(bwd, *env_light(bwd))
+                level0(bwd)
             else:
-                pending.append((e1, _mlp_backward(e1, cfg, params, wpack, d_rr, d_rd, v, None, flat_grad, st,
-                                                  defer=cfg.batch_wgrad), v is not None))
-                if not cfg.batch_wgrad:
-                    pending = []
-            if conc:
+                # CONCURRENT WEIGHT GRADIENTS (fused chains, cfg.overlap): the weight-gradient GEMMs of an evaluation start on a side
+                # stream as soon as its backward chain is done and run beside the next evaluation's chains, each kernel family on its
+                # share of the CUs (cfg.chain_wgs / cfg.wgrad_wgs: a chain workgroup and a 256-wide weight-gradient workgroup fill a
+                # CU each, so the two launches occupy disjoint CUs) - the chains are bound by matrix-instruction issue and their T
+                # stores, the weight gradients by their operand reads.  Level 0, whose gradient depends on nothing of level 1, goes
+                # first so that its weight gradients have the env-light and level-1 chains to run under; the second-order trunk rows
+                # of level 1 (r_l^T hdot_{l-1}: complete after the tangent sweep) run under its backward chain; only its first-order
+                # products are left for the end, on the whole chip.  All reductions into flat_grad happen on the side stream, in a
+                # fixed order.
+                side, cw, ww = _side_stream(dev), cfg.chain_wgs, cfg.wgrad_wgs
+                held = []  # workspaces of the side-stream jobs (kept until the join)
+
+                def wg(ev, which, wgs):
+                    side.wait_stream(main)
+                    with torch.cuda.stream(side):
+                        held.append(f.chain_wgrad([ev], flat_grad, side.cuda_stream, which, wgs))
+
+                def bwd(ev, d_rr, d_rd, v, d_mean):
+                    if v is not None:
+                        f.chain_tangent(ev, v, cw)
+                        wg(ev, 2, ww)  # second-order trunk rows, under the backward chain
+                    f.chain_backward(ev, d_rr, d_rd, v, d_mean, 0 if ev is e0 else cw)  # (level 0 is alone on the chip: every CU)
+                    wg(ev, 1 if v is not None else 3, 0 if ev is e1 else ww)  # what is left of level 1 runs alone: every CU
+
+                level0(bwd)
+                level1(bwd, *env_light(bwd))
                 main.wait_stream(side)
-            else:
-                d_rr0, d_rd0 = level0()
-                if cfg.planes:
-                    _chain_backward(e0, cfg, params, wpack, d_rr0, d_rd0, None, None, st)
-                    pending.append(e0)
-                    _chain_wgrad(pending, nc, cfg.planes, flat_grad, st)
-                else:
-                    _mlp_backward(e0, cfg, params, wpack, d_rr0, d_rd0, None, None, flat_grad, st, deferred=pending)
-            pending = []
-            held = []
         mlp.last_flat_grad = flat_grad
         ctx.pack = None
         if getattr(mlp, "defer_param_grads", False):
@@ -585,20 +597,23 @@ class _RenderBase(torch.nn.Module):
             self._env_src = src  # keeps the sources alive: their addresses cannot be handed to other tensors meanwhile
         return self._env_f32, key
 
+    def _cfg(self, white_bkgd=False, surf=False, use_ort=False, normals=False):
+        return _Cfg(num_samples=self.num_samples, nc=self._NC, density_bias=self.density_bias,
+                    rgb_padding=self.rgb_padding, resample_padding=self.resample_padding, disparity=self.disparity,
+                    disable_integration=self.disable_integration,
+                    white_bkgd=bool(white_bkgd), surf=bool(surf), use_ort=bool(use_ort), normals=bool(normals),
+                    num_env_samples=self.num_env_samples, overlap=self.overlap_weight_grads, planes=_planes_of(self.mlp_mode),
+                    tfmt=_tfmt_of(self.mlp_mode), chain_wgs=int(self.overlap_chain_wgs), wgrad_wgs=int(self.overlap_wgrad_wgs),
+                    batch_wgrad=self.batch_weight_grads,
+                    keep=torch.is_grad_enabled() and any(p.requires_grad for p in self.mlp.parameters()))
+
     def _run(self, rays, env_rays, randomized, white_bkgd, surf, use_ort, normals):
         o, d, vd = _f32(rays.origins), _f32(rays.directions), _f32(rays.viewdirs)
         radii, near, far = _f32(rays.radii).reshape(-1), _f32(rays.near).reshape(-1), _f32(rays.far).reshape(-1)
         dev = o.device
         env, env_key = self._env_inputs(env_rays, surf, dev)
         t_rand, u_rand, env_rand = self._noise(randomized, o.shape[0], dev, surf)
-        cfg = _Cfg(num_samples=self.num_samples, nc=self._NC, density_bias=self.density_bias,
-                   rgb_padding=self.rgb_padding, resample_padding=self.resample_padding, disparity=self.disparity,
-                   disable_integration=self.disable_integration,
-                   white_bkgd=bool(white_bkgd), surf=bool(surf), use_ort=bool(use_ort), normals=bool(normals),
-                   num_env_samples=self.num_env_samples, overlap=self.overlap_weight_grads, planes=_planes_of(self.mlp_mode),
-                   tfmt=_tfmt_of(self.mlp_mode), chain_wgs=int(self.overlap_chain_wgs), wgrad_wgs=int(self.overlap_wgrad_wgs),
-                   batch_wgrad=self.batch_weight_grads,
-                   keep=torch.is_grad_enabled() and any(p.requires_grad for p in self.mlp.parameters()))
+        cfg = self._cfg(white_bkgd, surf, use_ort, normals)
         plist = [p for _, p in self.mlp.named_in_order()]
         if (self.replay_inference and not cfg.keep and not randomized and dev.type == "cuda"
                 and 0 < o.shape[0] <= self.replay_inference_max_rays and (env_key is not None or not cfg.surf)

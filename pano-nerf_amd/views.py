@@ -51,7 +51,8 @@ from .geometry import _model_device
 from .cameras import (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, StereoPanoCamera, perspective_camera,  # noqa
                       pano_camera, cubemap_camera, fisheye_camera, stereo_pano_camera, camera_mask, cube_faces,
                       cube_solid_angles, _camera, _kind_params, _c2w_stack)
-from .rays import Rays, CameraRig, PerspectiveRayPool, _stream  # noqa
+from .parallel import lanes
+from .rays import Rays, CameraRig, PerspectiveRayPool  # noqa
 
 _MAX_SAMPLES = 16
 _MAX_SPLAT = 8  # PN_WARP_MAX_SPLAT
@@ -276,7 +277,7 @@ def to_frame(image, kind, near=None, far=None, exposure=0.0):
     with torch.no_grad(), torch.cuda.device(dev):
         work = torch.empty(2, dtype=torch.float32, device=dev) if kind == "depth" else None
         _lib.call("pn_to_frame", _FRAME_KINDS[kind], H, W, x.data_ptr(), cs, sw, float(2.0 ** float(exposure)), near_f,
-                  range_f, _lib.ptr(_lut(dev) if kind == "depth" else None), _lib.ptr(work), out.data_ptr(), _stream(dev))
+                  range_f, _lib.ptr(_lut(dev) if kind == "depth" else None), _lib.ptr(work), out.data_ptr(), _lib.stream(dev))
     return out
 
 
@@ -302,27 +303,10 @@ def _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, c
     kernels on the same rays: the same bits)."""
     dev = rig.device
     starts = list(range(0, count, chunk))
-    cur = torch.cuda.current_stream(dev)
-    lanes = [cur]
-    forked = streams > 1 and len(starts) > 1
-    if forked:
-        from .parallel import _streams
-        if surf:  # the cached fp32 env rays are made on this stream, before the other lanes fork from it
-            model._env_inputs(env_rays, True, dev)
-        from .render import _planes_of
-        planes = _planes_of(model.mlp_mode)
-        model.mlp._frozen = False
-        if planes:
-            model.mlp.chain_packed(cur.cuda_stream, planes)
-        else:
-            model.mlp.packed(cur.cuda_stream)
-        model.mlp._frozen = True
-        lanes += _streams(dev, min(int(streams), len(starts)) - 1)
-        for s in lanes[1:]:
-            s.wait_stream(cur)
-    try:
+    # (with surface outputs the cached fp32 env rays are made on this stream, before the other lanes fork from it)
+    with lanes(model, dev, min(int(streams), len(starts)), env_rays if surf else None) as lane:
         for i, s in enumerate(starts):
-            with torch.cuda.stream(lanes[i % len(lanes)]):
+            with torch.cuda.stream(lane[i % len(lane)]):
                 n = min(chunk, count - s)
                 idx = torch.arange(first + s, first + s + n, dtype=torch.int64, device=dev)
                 rays, _ = rig.sample(idx, near, far)
@@ -337,11 +321,6 @@ def _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, c
                     continue
                 for name, buf in bufs.items():
                     buf[s:s + n].copy_(got[name].reshape(n, -1))
-    finally:
-        if forked:
-            model.mlp._frozen = False
-    for s in lanes[1:]:
-        cur.wait_stream(s)
 
 
 def _setup(model, camera, chunk_rays):
@@ -488,7 +467,7 @@ def reproject(image, src_camera, dst_camera, rotation=None, samples=1, fill=0.0)
     cov = torch.empty(dst.h, dst.w, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
         _lib.call("pn_reproject", N, C, sk, src.h, src.w, sp.ctypes.data, dk, dst.h, dst.w, dp.ctypes.data, r32.ctypes.data,
-                  k, float(fill), x.data_ptr(), sn, sc, sw, out.data_ptr(), cov.data_ptr(), _stream(dev))
+                  k, float(fill), x.data_ptr(), sn, sc, sw, out.data_ptr(), cov.data_ptr(), _lib.stream(dev))
     return out, cov
 
 
@@ -592,7 +571,7 @@ def warp_view(image, depth, src_camera, src_c2w, dst_camera, dst_c2w, max_splat=
         dep = torch.empty(D, 1, Hd, Wd, dtype=torch.float32, device=dev)
         index = torch.empty(D, Hd, Wd, dtype=torch.int64, device=dev)
         cov = torch.empty(D, Hd, Wd, dtype=torch.float32, device=dev)
-        st = _stream(dev)
+        st = _lib.stream(dev)
         _lib.call("pn_warp_splat", S, sk, Hs, Ws, sp.ctypes.data, z.data_ptr(), ms.data_ptr(), D, dk, Hd, Wd, dp.ctypes.data,
                   md.data_ptr(), k, scale, zbuf.data_ptr(), st)
         _lib.call("pn_warp_resolve", S, C, Hs, Ws, D, dk, Hd, Wd, dp.ctypes.data, zbuf.data_ptr(), _lib.ptr(x), sn, sc, sw,
@@ -661,7 +640,7 @@ def blend_warps(images, depths, weights, depth_ratio=0.05, fill=0.0):
         dep = torch.empty(D, 1, H, W, dtype=torch.float32, device=dev)
         cov = torch.empty(D, H, W, dtype=torch.float32, device=dev)
         _lib.call("pn_warp_blend", S, D, C, H, W, x.data_ptr(), z.data_ptr(), wd.data_ptr(), r, float(fill), out.data_ptr(),
-                  dep.data_ptr(), cov.data_ptr(), _stream(dev))
+                  dep.data_ptr(), cov.data_ptr(), _lib.stream(dev))
     return {"image": out, "depth": dep, "coverage": cov}
 
 
@@ -748,7 +727,7 @@ def fill_holes(image, depth=None, coverage=None, camera=None, depth_ratio=0.05, 
         _lib.check(min(floats, 0), "pn_fill_holes_work_floats")
         work = torch.empty(floats, dtype=torch.float32, device=dev) if floats else None
         _lib.call("pn_fill_holes", n, C, h, W, out.data_ptr(), _lib.ptr(z), _lib.ptr(known), _lib.ptr(domain),
-                  int(isinstance(cam, PanoCamera)), r, lv, filled.data_ptr(), _lib.ptr(work), floats, _stream(dev))
+                  int(isinstance(cam, PanoCamera)), r, lv, filled.data_ptr(), _lib.ptr(work), floats, _lib.stream(dev))
         if cube:
             out = out.permute(0, 2, 1, 3, 4).reshape(N, C, H, W)
     res = {"image": out, "filled": filled.view(torch.bool)}

@@ -443,3 +443,51 @@ def test_concurrent_sub_batches_give_the_whole_batch_gradient(parts):
     for p, ref in zip(model.mlp.parameters(), full_pgrad):
         assert float((p.grad - ref).norm()) <= 1e-4 * float(ref.norm()) + 1e-12
     assert first[1][0].shape[0] == (B + parts - 1) // parts
+
+
+def _pano_8x16(golden):
+    import pano_nerf_amd as pn
+    rays = pn.generate_pano_rays(8, 16, golden("raygen_8x16")["c2ws"][0])
+    return rays, pn.generate_lit_rays(10, pn.rays.pano_pixel_radius(rays))
+
+
+def test_lanes_unfreeze_the_packs_when_the_body_raises(golden):
+    """parallel.lanes builds the weight packs once and freezes them for its body.  An exception inside must leave the
+    model as it was: `_frozen` cleared, so that the next forward re-packs and sees parameters changed in between."""
+    import pano_nerf_amd as pn
+    from pano_nerf_amd.parallel import lanes
+    rays, env = _pano_8x16(golden)
+    kw = dict(rays=rays, env_rays=env, randomized=False, white_bkgd=False, enable_surf=True, use_ort_loss=True)
+    fine = lambda m: [x for x in m(**kw)[1] if x is not None]
+    model = make_pano(16)
+    with torch.no_grad():
+        before = fine(model)
+        with pytest.raises(ZeroDivisionError):
+            with lanes(model, dev(), 2) as streams:
+                assert len(streams) == 2 and model.mlp._frozen is True
+                1 / 0
+        assert model.mlp._frozen is False
+        for p in model.mlp.parameters():
+            p.mul_(1.25)
+        after = fine(model)
+        fresh = make_pano(16)
+        fresh.mlp.load_state_dict(model.mlp.state_dict())
+        want = fine(fresh)
+    assert not torch.equal(after[0], before[0])  # the pack was rebuilt from the scaled parameters
+    assert len(after) == len(want) == 8
+    for a, b in zip(after, want):
+        assert torch.equal(a, b)
+
+
+def test_render_image_on_two_streams_is_bit_identical(golden):
+    """Chunks dealt to two streams over frozen packs: the same kernels on the same rays as on one stream."""
+    import pano_nerf_amd as pn
+    rays, env = _pano_8x16(golden)
+    img_rays = pn.Rays(*[x.view(1, 8, 16, -1) for x in rays])
+    model = make_pano(16)
+    one = pn.render_image(model, img_rays, env, 8, 16, chunk_size=48, streams=1)
+    two = pn.render_image(model, img_rays, env, 8, 16, chunk_size=48, streams=2)
+    torch.cuda.synchronize()
+    assert sum(x is not None for x in two) == 8
+    for a, b in zip(one, two):
+        assert (a is None and b is None) or torch.equal(a, b)

@@ -49,15 +49,12 @@ def timed(fn, iters):
 def train_forward_rate(model, rows, iters):
     """rows/s of the training forward chain (pn_chain_forward with the activation stash) on `rows` sample rows."""
     dev = torch.device("cuda")
-    st = torch.cuda.current_stream().cuda_stream
-    planes, tfmt = render._planes_of(model.mlp_mode), render._tfmt_of(model.mlp_mode)
-    params = model.mlp.flat_params()
-    wpack = model.mlp.chain_packed(st, planes)
+    f = render._Field.of(model, dev)
     vd = torch.nn.functional.normalize(torch.randn(rows // 128, 3, device=dev), dim=-1)
-    ev = render._Eval(rows, 128, vd, 5, dev, planes, True, tfmt)
+    ev = f.evaluation(rows, 128, vd, True)
     ev.mean.uniform_(-1.5, 1.5)
     ev.cov.fill_(1e-4)
-    sec, _ = timed(lambda: render._mlp_forward(ev, params, wpack, st), iters)
+    sec, _ = timed(lambda: f.forward(ev), iters)
     return rows / sec
 
 

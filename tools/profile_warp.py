@@ -43,7 +43,6 @@ import pano_nerf_amd as pn  # noqa: E402
 from oracle import pano_oracle as orc  # noqa: E402
 from pano_nerf_amd import views, _lib  # noqa: E402
 from pano_nerf_amd.cameras import _kind_params  # noqa: E402
-from pano_nerf_amd.rays import _stream  # noqa: E402
 
 HBM_COPY_TB_S = 6.29  # measured float4 copy rate of one MI355X (tools/profile_views.py)
 
@@ -128,7 +127,7 @@ def warp(repeats, iters):
             "reproject_pano_to_pano512x1024": lambda: views.reproject(image, src, pano)}
     # the kernels apart, on the single pinhole frame and on the panorama, max_splat 4
     parts = {}
-    (sk, sp), st = _kind_params(src), _stream(dev)
+    (sk, sp), st = _kind_params(src), _lib.stream(dev)
     z = depth.reshape(1, 512, 1024)
     ms = torch.eye(4, device=dev).reshape(1, 16).contiguous()
     keep = []
@@ -283,7 +282,7 @@ def fill(repeats, iters, other_lib=None):
             getattr(lib, fn_name).restype = _lib._CODES[res]
             getattr(lib, fn_name).argtypes = [_lib._CODES[c] for c in args]
         libs["_per_level_launches"] = lib
-    st = _stream(dev)
+    st = _lib.stream(dev)
     for name, x, z, c in raw + [(f"small{h}x{w_}", torch.rand(1, 3, h, w_, device=dev), 1 + torch.rand(1, h, w_, device=dev),
                                  (torch.rand(1, h, w_, device=dev) < 0.5).float()) for h, w_ in ((15, 20), (16, 32), (30, 40))]:
         h, w_ = x.shape[2:]
