@@ -452,6 +452,49 @@ int pn_sh_volume_irradiance(int nx, int ny, int nz, float x0, float y0, float z0
                             const float* sh, int64_t M, const float* points, const float* normals, float* out,
                             void* stream);
 
+/* ---- image-based lighting: GGX prefilter, environment-BRDF table, engine shading (pn_ibl.hip) -----------------------
+ * The assets of the split-sum approximation (Karis, "Real Shading in Unreal Engine 4") from the light probes above (the
+ * same probe addressing and the same dirs / omega tables).  Every sum is fp64 in a fixed order on fp32 inputs, rounded
+ * once per output, without atomics: repeated calls give the same bits.
+ * Prefilter (pn_prefilter): for directions [K, 3] shared by every probe (per_probe_directions = 0) or [P, K, 3] (1), unit
+ * length, and alpha = roughness^2, roughness in (0, 1]: per probe pixel of direction d and solid angle omega
+ *   c = max(0, n . d),  h2 = (1 + c) / 2 (= NoH^2 with N = V = R),  den = h2 (alpha^2 - 1) + 1,  q = c / den^2
+ *   out[p, n, ch] = (sum (L_ch omega) q) / (sum omega q)  -> out [P, K, 3]
+ * i.e. the GGX D NoL weights, the constant alpha^2 / pi of D cancelling.  A deterministic quadrature over every pixel, not
+ * Monte Carlo.  The pixels are summed in index order within segments of consecutive LDS tiles and the segments in order;
+ * the segmentation depends on H W only, so a probe's result does not depend on P.  work: pn_prefilter_work_doubles(P, H,
+ * W, K) device doubles.  NaN as pn_probe_irradiance: a NaN radiance value makes its channel NaN for every direction of
+ * the probe (weight 0 times NaN included), a NaN dot product stays NaN.  A zero direction gives 0 / 0 = NaN.
+ * Table (pn_brdf_lut): out [size, size, 2] = (A, B) with specular = prefiltered (F0 A + B); row i has roughness r =
+ * (i + 1/2) / size, column j NoV mu = (j + 1/2) / size.  N = z, V = (sqrt(1 - mu^2), 0, mu), alpha = r^2, k = alpha / 2;
+ * midpoint rule on the GGX-warped grid u = (a + 1/2) / n, phi = 2 pi (b + 1/2) / n, a, b < n = samples:
+ *   cos^2 theta_h = (1 - u) / (1 + (alpha^2 - 1) u),  H = (sin theta_h cos phi, sin theta_h sin phi, cos theta_h),
+ *   VoH = V . H,  NoL = 2 VoH NoH - mu,  G1(x) = x / ((1 - k) x + k),  Gv = G1(NoL) G1(mu) VoH / (NoH mu),
+ *   Fc = 2^(-(5.55473 VoH + 6.98316) VoH),  A = sum (1 - Fc) Gv / n^2,  B = sum Fc Gv / n^2   over NoL > 0 and VoH > 0.
+ * One entry per wave: lane l adds the nodes a n + b = l, l + 64, ... in order, then a fixed butterfly.
+ * Shading (pn_ibl_shade), one row per thread, for ONE probe's assets: specular_levels = the levels l < levels of the
+ * prefiltered cube-map chain one after the other, level l a strip [3, 6 S_l, S_l], S_l = size >> l, holding roughness
+ * l / (levels - 1); irradiance a strip [3, 6 Si, Si]; lut [St, St, 2].  viewdirs point from the camera to the surface.
+ *   v = -viewdir / |viewdir|,  nv = n . v,  NoV = max(0, nv),  Rr = 2 nv n - v,  r = roughness[row] or roughness_all
+ *   lambda = clamp(r (levels - 1), 0, levels - 1),  l0 = min(floor lambda, levels - 2),  f = lambda - l0
+ *   light = (1 - f) fetch(level l0, Rr) + f fetch(level l0 + 1, Rr),  E = fetch(irradiance, n)
+ *   fetch: the CUBE lookup of pn_reproject (face, s, t from the component of largest magnitude; bilinear around
+ *     (px - 1/2, py - 1/2), the four taps clamped within the face, ((w00 v00 + w01 v01) + w10 v10) + w11 v11), in fp64;
+ *     NaN for a zero or NaN direction.  No filtering across faces.
+ *   (A, B) bilinear in lut at x = NoV St - 1/2 (columns), y = r St - 1/2 (rows), each clamped to [0, St - 1]
+ *   diffuse = albedo / pi E,  specular = light (f0 A + B),  rgb = diffuse + specular (each rounded once from fp64)
+ * Errors: PN_ERR_BAD_SHAPE (the probe limits of pn_probe_irradiance, K <= 0, roughness outside (0, 1], a table size < 2
+ * or > 4096, samples < 1 or > 4096, levels < 2 or > 13 or size >> (levels - 1) < 1, a cube size < 1 or > 4096). */
+int64_t pn_prefilter_work_doubles(int64_t P, int H, int W, int64_t K);
+int pn_prefilter(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps, const float* dirs,
+                 const float* omega, int64_t K, const float* directions, int per_probe_directions, double roughness,
+                 float* out, double* work, void* stream);
+int pn_brdf_lut(int size, int samples, float* out, void* stream);
+int pn_ibl_shade(int64_t R, int size, int levels, const float* specular_levels, int irradiance_size,
+                 const float* irradiance, int lut_size, const float* lut, const float* albedo, const float* normals,
+                 const float* viewdirs, const float* roughness, float roughness_all, float f0, float* rgb, float* diffuse,
+                 float* specular, void* stream);
+
 /* ---- novel views: pinhole rays (pn_cameras.hip) and viewable frames (pn_views.hip) -------------------------------
  * Pinhole camera: pix2cam [3, 3] fp32 row-major maps pixel (x + 1/2, y + 1/2, 1) (x = column, y = row) to a camera-space
  * direction; the Blender form is ((x + 1/2 - W/2) / f, -(y + 1/2 - H/2) / f, -1): x right, y up, looking along -z

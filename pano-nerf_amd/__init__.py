@@ -14,6 +14,8 @@ Public surface (mirrors the reference's names):
     extract_mesh                  Mesh(vertices, faces, normals, colors) of {sigma > level} over a box
     lighting                      spatially-varying lighting: HDR light probes, SH projection, exact and SH irradiance,
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)
+    ibl                           light probes baked into engine-ready image-based lighting: GGX-prefiltered specular cube-map
+                                  mips, irradiance cubes, the split-sum BRDF table, EXR export and ibl_shade (HIP kernels)
     views                         novel views: perspective cameras and ray pools, camera paths, render_view / render_path
                                   and the reference's viewable uint8 frames, reprojection between cameras and depth-aware
                                   warping of rendered frames to other poses: warp_view, render_path_warped (HIP kernels)
@@ -40,6 +42,7 @@ from .metrics import evaluate_panorama  # noqa
 from . import geometry  # noqa
 from .geometry import extract_mesh  # noqa
 from . import lighting  # noqa
+from . import ibl  # noqa
 from . import views  # noqa
 from . import objects  # noqa
 from . import data  # noqa

@@ -75,6 +75,10 @@ SIGNATURES = {
     "pn_probe_sh": ("i", "liip" + "lll" + "pppp" + "p"),
     "pn_probe_irradiance": ("i", "liip" + "lll" + "pp" + "lpi" + "p" + "p"),
     "pn_sh_volume_irradiance": ("i", "iii" + "f" * 6 + "plppp" + "p"),
+    "pn_prefilter_work_doubles": ("l", "liil"),
+    "pn_prefilter": ("i", "liip" + "lll" + "pp" + "lpid" + "pp" + "p"),
+    "pn_brdf_lut": ("i", "iipp"),
+    "pn_ibl_shade": ("i", "lii" + "pipip" + "pppp" + "ff" + "ppp" + "p"),
     "pn_sample_pinhole_rays": ("i", "liiipppffp" + "p" * 9 + "p"),
     "pn_to_frame": ("i", "iiipllfffppp" + "p"),
     "pn_sample_camera_rays": ("i", "liiiipppffp" + "p" * 9 + "p"),

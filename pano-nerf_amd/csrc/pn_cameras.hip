@@ -122,26 +122,7 @@ __device__ __forceinline__ bool src_pos(int kind, int H, int W, const CamParams&
         }
         return px >= 0.f && px <= (float)W && py >= 0.f && py <= (float)H;
     }
-    // cube: the major axis picks the face, ties to the earlier face of +x -x +y -y +z -z
-    const float ax = fabsf(d[0]), ay = fabsf(d[1]), az = fabsf(d[2]);
-    float s, t, mj;
-    if (ax >= ay && ax >= az) {
-        mj = ax;
-        if (d[0] > 0.f) face = 0, s = -d[2] / mj, t = -d[1] / mj;
-        else face = 1, s = d[2] / mj, t = -d[1] / mj;
-    } else if (ay >= az) {
-        mj = ay;
-        if (d[1] > 0.f) face = 2, s = d[0] / mj, t = d[2] / mj;
-        else face = 3, s = d[0] / mj, t = -d[2] / mj;
-    } else {
-        mj = az;
-        if (d[2] > 0.f) face = 4, s = d[0] / mj, t = -d[1] / mj;
-        else face = 5, s = -d[0] / mj, t = -d[1] / mj;
-    }
-    if (!(mj > 0.f)) return false;
-    px = (s + 1.f) * (0.5f * (float)W);
-    py = (t + 1.f) * (0.5f * (float)W);  // within the face
-    return true;
+    return cube_pos(W, d, px, py, face);  // py within the face
 }
 
 struct Taps {

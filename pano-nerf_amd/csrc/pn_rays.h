@@ -112,6 +112,34 @@ __device__ __forceinline__ void cube_dir(int S, float px, float py, float d[3]) 
     }
 }
 
+// the inverse: direction d -> the strip's face and the continuous position (px, py) within that face of a cube of size
+// S.  The major axis picks the face, ties to the earlier face of +x -x +y -y +z -z; false for a zero or NaN direction.
+// pn_reproject looks up in fp32, the IBL evaluation (pn_ibl.hip) in fp64: one definition, the same faces.
+__device__ __forceinline__ float abs_t(float x) { return fabsf(x); }
+__device__ __forceinline__ double abs_t(double x) { return fabs(x); }
+template <class T>
+__device__ __forceinline__ bool cube_pos(int S, const T d[3], T& px, T& py, int& face) {
+    const T ax = abs_t(d[0]), ay = abs_t(d[1]), az = abs_t(d[2]);
+    T s, t, mj;
+    if (ax >= ay && ax >= az) {
+        mj = ax;
+        if (d[0] > (T)0) face = 0, s = -d[2] / mj, t = -d[1] / mj;
+        else face = 1, s = d[2] / mj, t = -d[1] / mj;
+    } else if (ay >= az) {
+        mj = ay;
+        if (d[1] > (T)0) face = 2, s = d[0] / mj, t = d[2] / mj;
+        else face = 3, s = d[0] / mj, t = -d[2] / mj;
+    } else {
+        mj = az;
+        if (d[2] > (T)0) face = 4, s = d[0] / mj, t = -d[1] / mj;
+        else face = 5, s = -d[0] / mj, t = -d[1] / mj;
+    }
+    if (!(mj > (T)0)) return false;
+    px = (s + (T)1) * ((T)0.5 * (T)S);
+    py = (t + (T)1) * ((T)0.5 * (T)S);
+    return true;
+}
+
 // equidistant fisheye: unit camera-space direction of (px, py) and its angle from the axis
 __device__ __forceinline__ float fisheye_dir(int H, int W, float f, float px, float py, float d[3]) {
     const float u = px - 0.5f * (float)W, v = -(py - 0.5f * (float)H);
