@@ -901,6 +901,62 @@ int pn_texture_hits(int64_t R, const uint8_t* mask, const int32_t* face, const f
                     int roughness_w, const float* normal_tex, int normal_h, int normal_w, int wrap, int flip_v,
                     float* albedo, float* roughness, float* normals, float* lod, void* stream);
 
+/* ---- baking the scene into a texture atlas (pn_atlas.hip): one patch per face, read back by pn_texture_hits --------------
+ * Layout: a square atlas of S x S texels (1 <= S <= PN_TEX_MAX_SIZE) is cut into cells of c x c texels
+ * (PN_ATLAS_MIN_CELL <= c <= S), n = S / c (integer division) per row; texels with a row or column >= n c belong to
+ * nobody.  Cell k = row n + col holds face 2k in its lower-left half (h = 0) and face 2k + 1 in its upper-right half
+ * (h = 1); F <= 2 n^2.  With x along columns and y along rows, texel (li, lj) of a cell has its centre at (lj + 0.5,
+ * li + 0.5), and the corners of face f, in continuous texel coordinates of its cell, are (L = c - 2 PN_ATLAS_MARGIN -
+ * PN_ATLAS_DIAG = c - 4, the leg)
+ *     h = 0:  P0 = (1, 1)          P1 = (1 + L, 1)          P2 = (1, 1 + L)
+ *     h = 1:  P0 = (c - 1, c - 1)  P1 = (c - 1 - L, c - 1)  P2 = (c - 1, c - 1 - L)
+ * corner Pi for vertex i of the face: a margin of PN_ATLAS_MARGIN texel to the cell's border, and PN_ATLAS_DIAG texels
+ * between the two hypotenuses.
+ * pn_atlas_uv writes uv [3F, 2] (row 3f + i: corner i of face f; face_uv[f] = (3f, 3f + 1, 3f + 2)) in the OBJ convention
+ * pn_texture_hits reads with flip_v = 1: U = X / S, V = 1 - Y / S, (X, Y) = (col c, row c) + Pi, in fp64, rounded once.
+ * Ownership of texel (li, lj) of cell k: h = (li + lj + 1 >= c), f = 2k + h; unowned when f >= F.  Its barycentrics are
+ * those of the texel's centre (x, y) in the face's affine map - h = 0: u = (x - 1) / L, v = (y - 1) / L; h = 1:
+ * u = (c - 1 - x) / L, v = (c - 1 - y) / L - extrapolated outside the triangle, never clamped: a gutter texel carries the
+ * continuation of its own triangle's plane, so no dilation pass is needed.
+ * Tap property (c >= 6): at any point of the closed UV triangle of a face, every level-0 bilinear tap of pn_texture_hits
+ * (x = U S - 0.5, ...) with a non-zero weight is a texel that face owns.  A tap's centre is within one texel of the
+ * sample in x and in y, so it stays inside the cell (margin 1); on triangle 0 the sample has x + y <= c - 2, its taps'
+ * centres x + y <= c, with equality only for the far tap of a sample at integer x - 0.5 and y - 0.5, whose weight is 0:
+ * every other tap has li + lj + 1 < c.  Triangle 1 mirrors it: x + y >= c + 2 and every tap has li + lj + 1 >= c.
+ * Mip levels above 0 mix neighbouring cells, as with every per-triangle atlas: a baked asset is sampled at level 0 (radii
+ * NULL) or re-atlased by the engine.
+ * pn_atlas_texels, per texel t = i S + j of the image (fp64 on the fp32 inputs, rounded once per output): face [S, S]
+ * int32 (-1: unowned), bary [S, S, 2] = (u, v), points [S, S, 3] = w0 v0 + u v1 + v v2 (w0 = 1 - u - v), normals_g =
+ * (e1 x e2) / A_w (e1 = v1 - v0, e2 = v2 - v0, A_w = |e1 x e2|), normals_s = the barycentric blend of vertex_normals
+ * divided by max(its norm, 1e-30) as pn_object_hits defines it, NOT flipped (normals_g when vertex_normals is NULL), and
+ * var [S, S] = A_w / (12 L^2): the face's world area over its L^2 / 2 texels is the area of a texel's footprint, and a
+ * square of that area has this second moment per axis.  Unowned texels get zeros in every float output; so do the texels
+ * of a face with an index outside [0, V) or a non-finite vertex coordinate (face keeps f).  A face with A_w == 0 keeps
+ * face, bary and points; its normals (both) and var are 0.
+ * pn_atlas_encode_normals, per texel: (0.5, 0.5, 1) where face is outside [0, F); otherwise 0.5 m + 0.5 with m = (n . T',
+ * n . B', n . N), n = world_normals[t], N = normals_s[t] and T', B' the Gram-Schmidt frame of pn_texture_hits built
+ * from the face's edges and uv rows 3f .. 3f + 2 (as pn_atlas_uv wrote them) - the same expressions, so the sampler's
+ * n = normalize(m.x T' + m.y B' + m.z N) returns the baked normal.  (0.5, 0.5, 1) also where that frame does not exist
+ * (det == 0, a norm < 1e-12, anything non-finite, a vertex index outside [0, V)) or n . N <= 0: the sampler decodes it
+ * to N bit for bit.
+ * pn_atlas_quantize: x [count, C] fp32 (1 <= C <= 4) -> uint8.  With table (256 device floats, increasing, table[0] = 0:
+ * the decode table of pn_tex_ingest) the code i whose table[i] is nearest to clamp(x, 0, 1), compared in fp64, the lower
+ * code on a tie; without, round-half-even(255 clamp(x, 0, 1)).  NaN gives 0.
+ * One face / texel / value per thread, no LDS, no atomics: repeated calls give the same bits.  F = 0 or count = 0 launch
+ * nothing in pn_atlas_uv / pn_atlas_quantize.
+ * Errors: PN_ERR_BAD_SHAPE (S or c outside their range, F < 0 or F > 2 n^2, V < 0, C outside [1, 4]), PN_ERR_NULL. */
+#define PN_ATLAS_MARGIN 1
+#define PN_ATLAS_DIAG 2
+#define PN_ATLAS_MIN_CELL 6
+int pn_atlas_uv(int64_t F, int S, int c, float* uv, void* stream);
+int pn_atlas_texels(int S, int c, int64_t F, int64_t V, const float* vertices, const int32_t* faces,
+                    const float* vertex_normals, int32_t* face, float* bary, float* points, float* normals_g,
+                    float* normals_s, float* var, void* stream);
+int pn_atlas_encode_normals(int S, int c, int64_t F, int64_t V, const float* vertices, const int32_t* faces,
+                            const float* uv, const int32_t* face, const float* normals_s, const float* world_normals,
+                            float* out, void* stream);
+int pn_atlas_quantize(int64_t count, int C, const float* x, const float* table, uint8_t* out, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -10,7 +10,8 @@ Public surface (mirrors the reference's names):
     metrics, io_exr               utils/metrics.py (calc_* / calc_ws_*, SSIM, depth, calc_simse), utils/io_exr.py:6-47
     evaluate_panorama             every metric of one render_image output against its ground truths (HIP kernels)
     geometry                      field queries (sigma, albedo, rgb, normal at 3-D points), sigma volumes, marching-tetrahedra
-                                  meshes and PLY output of a trained model (HIP kernels)
+                                  meshes and PLY output of a trained model; bake_textures / write_obj / export_scene: the
+                                  field baked onto a mesh as albedo and normal maps over a per-triangle atlas (HIP kernels)
     extract_mesh                  Mesh(vertices, faces, normals, colors) of {sigma > level} over a box
     lighting                      spatially-varying lighting: HDR light probes, SH projection, exact and SH irradiance,
                                   the model's own irradiance estimate at any point and SH irradiance volumes (HIP kernels)

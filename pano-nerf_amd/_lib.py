@@ -104,6 +104,10 @@ SIGNATURES = {
     "pn_tex_ingest": ("i", "iiiipppp"),
     "pn_tex_pyramid": ("i", "iipp"),
     "pn_texture_hits": ("i", "l" + "p" * 7 + "lplp" + "lpp" + "pii" * 3 + "ii" + "pppp" + "p"),
+    "pn_atlas_uv": ("i", "liipp"),
+    "pn_atlas_texels": ("i", "iill" + "ppp" + "pppppp" + "p"),
+    "pn_atlas_encode_normals": ("i", "iill" + "pp" + "ppppp" + "p"),
+    "pn_atlas_quantize": ("i", "lippp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

@@ -12,8 +12,16 @@ fallback.  The only host synchronisation is the copy of the two mesh totals that
     write_ply(path, vertices, faces, normals, colors)  binary little-endian PLY
     read_ply(path)                              Mesh of host numpy arrays from such a file (binary or ASCII)
     read_obj(path)                              ObjMesh of host numpy arrays from a Wavefront OBJ (+ MTL) file
+    triangle_atlas(faces, size)                 Atlas(uv, face_uv, size, cell): half a cell of a square image per face
+    atlas_texels(vertices, faces, atlas)        per texel: face, bary, points, normals_g, normals_s, var
+    atlas_rays(texels, offset)                  one short ray per owned texel, for bake_textures(method="ray")
+    bake_textures(model, mesh, size, maps)      BakedMesh(vertices, faces, normals, uv, face_uv, maps): the field on a mesh
+    write_obj(path, baked)                      OBJ + MTL + PNG / EXR images that read_obj and VirtualObject.from_obj read
+    export_scene(model, bounds, resolution, level, path)   extract_mesh -> bake_textures -> write_obj
 
-The mesh contract (edge ids, vertex and face order, winding) is stated in include/panonerf_hip.h.
+The mesh contract (edge ids, vertex and face order, winding) and the atlas layout are stated in include/panonerf_hip.h.
+Out of scope of the baking: chart-based UV unwrapping, mesh decimation, several materials, and mip levels above 0 (a
+per-triangle atlas mixes neighbouring faces there: sample a baked asset at level 0, or let the engine re-atlas it).
 """
 import collections
 import os
@@ -33,6 +41,7 @@ FIELD_OUTPUTS = ("sigma", "albedo", "rgb", "normal", "grad")
 # the chains keep ~0.7 KB (gate words, encoding, raw outputs), +1 KB for the density-gradient slot
 _CHUNK_LAYERWISE = 1 << 16
 _CHUNK_CHAIN = 1 << 19
+_CHUNK_RAYS = 1 << 15  # rays per renderer call of bake_textures(method="ray")
 
 
 def _device_of(*tensors):
@@ -544,3 +553,338 @@ def read_obj(path):
         n = np.linalg.norm(acc, axis=1, keepdims=True)
         normals = np.where(n > 0, acc / np.where(n > 0, n, 1.0), 0.0).astype(np.float32)
     return ObjMesh(verts, faces, uv, face_uv, normals, np.asarray(fm, np.int32), materials)
+
+
+# ---------------------------------------------------------------------------------------- baking textures on a mesh
+Atlas = collections.namedtuple("Atlas", ["uv", "face_uv", "size", "cell"])
+BakedMesh = collections.namedtuple("BakedMesh", ["vertices", "faces", "normals", "uv", "face_uv", "maps"])
+
+ATLAS_MIN_CELL = 6   # PN_ATLAS_MIN_CELL
+ATLAS_MAX_SIZE = 16384  # PN_TEX_MAX_SIZE
+BAKE_MAPS = ("albedo", "radiance", "normal", "normal_world", "coverage")
+
+
+def atlas_cell(num_faces, size):
+    """The cell size of the per-triangle atlas of `num_faces` faces in a size x size image: the largest c >= 6 with
+    2 (size // c)^2 >= num_faces.  ValueError, naming the smallest size that would do, when there is none."""
+    F, S = int(num_faces), int(size)
+    if not 1 <= S <= ATLAS_MAX_SIZE:
+        raise ValueError(f"the atlas size must be in [1, {ATLAS_MAX_SIZE}]; got {size!r}")
+    if F < 0:
+        raise ValueError(f"the number of faces must be >= 0; got {num_faces!r}")
+    n = 1
+    while 2 * n * n < F:  # cells per row needed: the smallest n with 2 n^2 >= F
+        n += 1
+    c = S // n  # the largest c with S // c >= n
+    if c < ATLAS_MIN_CELL:
+        need = ATLAS_MIN_CELL * n
+        hint = f"size >= {need} would do" if need <= ATLAS_MAX_SIZE else \
+            f"that takes size {need}, above the largest texture ({ATLAS_MAX_SIZE}): bake a coarser mesh"
+        raise ValueError(f"an atlas of {S} x {S} texels is too small for {F} faces ({n} x {n} cells of at least "
+                         f"{ATLAS_MIN_CELL} texels): {hint}")
+    return c
+
+
+def _atlas_args(faces, size, cell):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be an [F, 3] tensor; got {getattr(faces, 'shape', type(faces))}")
+    F, S = int(faces.shape[0]), int(size)
+    c = atlas_cell(F, S)
+    if cell is not None:
+        if not ATLAS_MIN_CELL <= int(cell) <= c:
+            raise ValueError(f"cell must be in [{ATLAS_MIN_CELL}, {c}] for {F} faces in {S} x {S} texels; got {cell!r}")
+        c = int(cell)
+    return F, S, c
+
+
+def triangle_atlas(faces, size, cell=None):
+    """Atlas(uv [3F, 2] fp32, face_uv [F, 3] int32, size, cell) of the per-triangle atlas (include/panonerf_hip.h, "baking"):
+    every face gets half a cell of cell x cell texels of a size x size image, with a one-texel gutter that carries the
+    continuation of the face's own plane, so that a level-0 bilinear sample anywhere on the face reads its own texels only.
+    cell: None picks the largest that fits (atlas_cell).  Works on any triangle soup; needs no connectivity."""
+    dev = _device_of(faces)
+    F, S, c = _atlas_args(faces, size, cell)
+    with torch.no_grad(), torch.cuda.device(dev):
+        uv = torch.empty(3 * F, 2, dtype=torch.float32, device=dev)
+        _lib.call("pn_atlas_uv", F, S, c, _lib.ptr(uv) if F else None, _lib.stream(dev))
+        face_uv = torch.arange(3 * F, dtype=torch.int32, device=dev).view(F, 3)
+    return Atlas(uv, face_uv, S, c)
+
+
+def _mesh_tensors(vertices, faces, normals):
+    dev = _device_of(vertices, faces, *([normals] if normals is not None else []))
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3] and faces [F, 3]; got {tuple(vertices.shape)}, {tuple(faces.shape)}")
+    v = vertices.detach().to(torch.float32).contiguous()
+    f = faces.detach().to(torch.int32).contiguous()
+    n = None
+    if normals is not None:
+        if tuple(normals.shape) != tuple(v.shape):
+            raise ValueError(f"normals must be [V, 3] like the vertices; got {tuple(normals.shape)}")
+        n = normals.detach().to(torch.float32).contiguous()
+    return dev, v, f, n
+
+
+def atlas_texels(vertices, faces, atlas, normals=None):
+    """What every texel of the atlas shows, as a dict of [S, S, ...] device tensors: face (int32, -1: unowned), bary [.., 2]
+    (the texel centre in its face, extrapolated in the gutter), points [.., 3], normals_g (geometric), normals_s (the
+    blend of the vertex `normals`, not flipped; normals_g without them) and var (the per-axis second moment of the
+    texel's square footprint on the face, for the integrated encoding)."""
+    dev, v, f, n = _mesh_tensors(vertices, faces, normals)
+    S, c = int(atlas.size), int(atlas.cell)
+    e = lambda *s: torch.empty(S, S, *s, dtype=torch.float32, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = dict(face=torch.empty(S, S, dtype=torch.int32, device=dev), bary=e(2), points=e(3), normals_g=e(3),
+                   normals_s=e(3), var=e())
+        _lib.call("pn_atlas_texels", S, c, int(f.shape[0]), int(v.shape[0]), _lib.ptr(v), _lib.ptr(f), _lib.ptr(n),
+                  out["face"].data_ptr(), out["bary"].data_ptr(), out["points"].data_ptr(), out["normals_g"].data_ptr(),
+                  out["normals_s"].data_ptr(), out["var"].data_ptr(), _lib.stream(dev))
+    return out
+
+
+def _median_texel_side(var):
+    """the side of the median owned texel's footprint: var = side^2 / 12"""
+    return float(torch.sqrt(12.0 * var.median())) if var.numel() else 0.0
+
+
+def atlas_rays(texels, offset=None):
+    """(Rays of the M owned texels, their flat indices [M] into the S x S image): one short ray per texel, from
+    points + offset normals_g along -normals_g, near = 0, far = 2 offset, radii = sqrt(12 var) / (2 offset) - a cone one
+    texel wide where it meets the face.  offset: None is four sides of the median texel (read back from the device).
+    Synchronises for the count of owned texels."""
+    face = texels["face"]
+    dev = _device_of(face)
+    with torch.no_grad(), torch.cuda.device(dev):
+        idx = torch.nonzero(face.reshape(-1) >= 0).reshape(-1)
+        return _atlas_rays(texels, idx, offset, dev), idx
+
+
+def _atlas_rays(texels, idx, offset, dev):
+    from .rays import Rays
+    var = texels["var"].reshape(-1)[idx]
+    if offset is None:
+        offset = 4.0 * _median_texel_side(var)
+    offset = float(offset)
+    if not offset > 0.0:
+        raise ValueError(f"offset must be positive; got {offset!r} (a mesh of zero-area faces has no default)")
+    ng = texels["normals_g"].reshape(-1, 3)[idx]
+    o = texels["points"].reshape(-1, 3)[idx] + offset * ng
+    d = -ng
+    col = lambda x: torch.full((idx.shape[0], 1), float(x), dtype=torch.float32, device=dev)
+    radii = (torch.sqrt(12.0 * var) / (2.0 * offset)).reshape(-1, 1)
+    return Rays(o, d, d.clone(), radii, col(1.0), col(0.0), col(2.0 * offset), col(0.0))
+
+
+def _bake_values(source, want, method, idx, pts, var, ns, tex, offset, chunk_rows, env_rays):
+    """name -> [M, 3] for the names in `want` ("albedo", "radiance", "normal") at the owned texels"""
+    if callable(source) and not isinstance(source, torch.nn.Module):
+        got = source(pts, var, ns)
+        missing = [k for k in want if k not in got]
+        if missing:
+            raise ValueError(f"the field callable returned {sorted(got)}; the maps asked for need {missing} too")
+        for k in want:
+            if tuple(got[k].shape) != tuple(pts.shape):
+                raise ValueError(f"the field callable's {k!r} must be [M, 3] like the points; got {tuple(got[k].shape)}")
+        return {k: got[k].to(torch.float32) for k in want}
+    model = source
+    if "albedo" in want and model._NC != 5:
+        raise ValueError(f"albedo needs a 5-channel density head (PanoMipNeRF); {type(model).__name__} has {model._NC}")
+    if method == "point":
+        var3 = var[:, None].expand(-1, 3).contiguous()
+        outs = tuple(k for k in ("albedo", "normal") if k in want)
+        res = query_field(model, pts, var3, outputs=outs, chunk_rows=chunk_rows) if outs else {}
+        if "radiance" in want:
+            res["radiance"] = query_field(model, pts, var3, viewdirs=-ns, outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
+        return res
+    # method == "ray": one short ray per owned texel through the renderer; the fine level's rgb, normal and albedo
+    rays = _atlas_rays(tex, idx, offset, pts.device)
+    M = int(pts.shape[0])
+    chunk = int(chunk_rows) if chunk_rows else _CHUNK_RAYS
+    if chunk <= 0:
+        raise ValueError(f"chunk_rows must be positive; got {chunk_rows!r}")
+    surf = "albedo" in want
+    if surf and env_rays is None:
+        raise ValueError("method='ray' composites the albedo in the renderer's surface pass, which needs env_rays "
+                         "(rays.generate_lit_rays); pass env_rays=, or bake the albedo with method='point'")
+    parts = {k: [] for k in want}
+    for first in range(0, M, chunk):
+        sub = type(rays)(*[x[first:first + chunk] for x in rays])
+        if model._NC == 5:
+            _, fine = model(rays=sub, env_rays=env_rays if surf else None, randomized=False, white_bkgd=False,
+                            enable_surf=surf, use_ort_loss=False)
+        else:  # a MipNeRF composites its normals only with the orientation term on
+            _, fine = model(rays=sub, randomized=False, white_bkgd=False, use_ort_loss=True)
+        for k, v in (("radiance", fine[0]), ("normal", fine[3]), ("albedo", fine[4] if surf else None)):
+            if k in want:
+                parts[k].append(v)
+    return {k: (torch.cat(v) if len(v) > 1 else v[0]) for k, v in parts.items()}
+
+
+def bake_textures(model, mesh, size=1024, maps=("albedo", "normal"), method="point", offset=None, cell=None,
+                  chunk_rows=None, env_rays=None):
+    """Bake the field onto `mesh` (anything with vertices, faces and normals | None, e.g. extract_mesh's Mesh):
+    BakedMesh(vertices, faces, normals, uv, face_uv, maps) with maps a dict of [S, S, 3] fp32 device images over the
+    per-triangle atlas of triangle_atlas(faces, size, cell).
+
+    maps: "albedo" (PanoMipNeRF only), "radiance" (the HDR rgb seen along -normals_s), "normal" (the field's normal in the
+    tangent space objects.VirtualObject decodes; (0.5, 0.5, 1) where it faces away from the mesh's own normal),
+    "normal_world" (the same before encoding) and "coverage" ([S, S, 1]: 1 on owned texels).  Unowned texels are 0.
+    method="point" is query_field at the owned texels' points with their footprint variance - bit for bit.
+    method="ray" renders one short ray per owned texel (atlas_rays: from `offset` above the face to `offset` below it, a
+    cone one texel wide at the face; offset None = four sides of the median texel) and takes the fine level's rgb, normal
+    and albedo (the radiance is then seen along the ray, -normals_g) - bit for bit the model called on atlas_rays(...).  It
+    is the mode for a coarse mesh that sits off the true level set.  The renderer composites the albedo in its surface
+    pass, so "albedo" then needs env_rays (as the model's forward does); chunk_rows counts rays per call here.
+    `model` may be a callable f(points [M, 3], var [M], normals [M, 3]) -> dict of [M, 3] tensors under the names
+    "albedo", "radiance", "normal" instead.  Mip levels above 0 of a per-triangle atlas mix neighbouring faces: sample the
+    result at level 0 (hit_attributes(radii=None)).  One host synchronisation: the count of owned texels (and, for
+    method="ray" without an offset, the median texel's side)."""
+    maps = tuple(maps)
+    bad = [m for m in maps if m not in BAKE_MAPS]
+    if bad or not maps:
+        raise ValueError(f"unknown maps {bad}; choose from {BAKE_MAPS}")
+    is_model = isinstance(model, torch.nn.Module)
+    if not is_model and not callable(model):
+        raise ValueError(f"model must be a MipNeRF / PanoMipNeRF or a callable; got {type(model).__name__}")
+    if is_model and "albedo" in maps and model._NC != 5:
+        raise ValueError(f"albedo needs a 5-channel density head (PanoMipNeRF); {type(model).__name__} has {model._NC}")
+    if method not in ("point", "ray"):
+        raise ValueError(f"method must be 'point' or 'ray'; got {method!r}")
+    dev, v, f, n = _mesh_tensors(mesh.vertices, mesh.faces, getattr(mesh, "normals", None))
+    if is_model and _model_device(model) != dev:
+        raise RuntimeError(f"the mesh is on {dev}, the model on {_model_device(model)}")
+    atlas = triangle_atlas(f, size, cell)
+    tex = atlas_texels(v, f, atlas, n)
+    S = atlas.size
+    want = tuple(k for k, users in (("albedo", ("albedo",)), ("radiance", ("radiance",)), ("normal", ("normal", "normal_world")))
+                 if any(u in maps for u in users))
+    with torch.no_grad(), torch.cuda.device(dev):
+        idx = torch.nonzero(tex["face"].reshape(-1) >= 0).reshape(-1)  # the one host sync
+        out = {}
+        vals = {}
+        if want and idx.numel():
+            vals = _bake_values(model, want, method, idx, tex["points"].reshape(-1, 3)[idx], tex["var"].reshape(-1)[idx],
+                                tex["normals_s"].reshape(-1, 3)[idx], tex, offset, chunk_rows, env_rays)
+        images = {}
+        for k in want:
+            img = torch.zeros(S * S, 3, dtype=torch.float32, device=dev)
+            if k in vals:
+                img[idx] = vals[k]
+            images[k] = img.view(S, S, 3)
+        for m in maps:
+            if m in ("albedo", "radiance"):
+                out[m] = images[m]
+            elif m == "normal_world":
+                out[m] = images["normal"]
+            elif m == "normal":
+                enc = torch.empty(S, S, 3, dtype=torch.float32, device=dev)
+                _lib.call("pn_atlas_encode_normals", S, atlas.cell, int(f.shape[0]), int(v.shape[0]), _lib.ptr(v),
+                          _lib.ptr(f), _lib.ptr(atlas.uv), tex["face"].data_ptr(), tex["normals_s"].data_ptr(),
+                          images["normal"].data_ptr(), enc.data_ptr(), _lib.stream(dev))
+                out[m] = enc
+            else:
+                out[m] = (tex["face"] >= 0).to(torch.float32).view(S, S, 1)
+    return BakedMesh(v, f, n, atlas.uv, atlas.face_uv, out)
+
+
+def quantize_image(image, srgb=False, table=True):
+    """fp32 device image [..., C] (C <= 4) -> uint8 of the same shape through pn_atlas_quantize: the code whose decoded
+    value (objects.Texture's table: the sRGB EOTF, or i / 255) is nearest, so that Texture(bytes, srgb=srgb) inverts it as
+    well as 8 bits allow; table=False is round-half-even(255 clamp(x))."""
+    from .objects import _decode_table
+    dev = _device_of(image)
+    x = image.detach().to(torch.float32).contiguous()
+    C = int(x.shape[-1]) if x.dim() else 0
+    if not 1 <= C <= 4:
+        raise ValueError(f"image must be [..., C] with 1 <= C <= 4; got {tuple(image.shape)}")
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty(x.shape, dtype=torch.uint8, device=dev)
+        tab = torch.from_numpy(_decode_table(srgb)).to(dev) if table else None
+        _lib.call("pn_atlas_quantize", x.numel() // C, C, _lib.ptr(x) if x.numel() else None, _lib.ptr(tab),
+                  _lib.ptr(out) if x.numel() else None, _lib.stream(dev))
+        if tab is not None:
+            tab.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def _image_bytes(img, srgb):
+    """a map as uint8 host bytes: uint8 is taken as it is, fp32 goes through the device quantiser"""
+    if isinstance(img, torch.Tensor):
+        if img.dtype == torch.uint8:
+            return img.detach().cpu().numpy()
+        return quantize_image(img, srgb=srgb).cpu().numpy()
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        raise RuntimeError("a floating map on the host cannot be written as PNG: the quantiser runs on the HIP device "
+                           "(there is no CPU fallback); pass a device tensor, uint8 bytes, or image_format='exr'")
+    return a
+
+
+def _image_f32(img):
+    a = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    if a.dtype == np.uint8:
+        raise ValueError("a uint8 map cannot be written as EXR; pass image_format='png'")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def write_obj(path, baked, image_format="png", srgb=True):
+    """Write a BakedMesh as Wavefront OBJ + MTL + images, and return {map name: image path}: `path` (v, vn when there are
+    normals, vt, f v/vt[/vn], mtllib, usemtl; floats as %.9g, which round-trips fp32), <stem>.mtl (map_Kd for "albedo",
+    norm for "normal", map_Ke for "radiance") and <stem>_albedo / <stem>_normal as .png (8 bits through pn_atlas_quantize:
+    the albedo against the sRGB table when `srgb`, the normal map linear) or .exr (fp32) by image_format; "radiance" is HDR
+    and always goes to <stem>_radiance.exr.  "normal_world" and "coverage" are not written.  read_obj and
+    objects.VirtualObject.from_obj read the result with their defaults."""
+    from . import io_exr
+    if image_format not in ("png", "exr"):
+        raise ValueError(f"image_format must be 'png' or 'exr'; got {image_format!r}")
+    v = _host(baked.vertices, np.float32, "vertices")
+    f = _host(baked.faces, np.int32, "faces")
+    n = None if baked.normals is None else _host(baked.normals, np.float32, "normals")
+    uv = baked.uv.detach().cpu().numpy() if isinstance(baked.uv, torch.Tensor) else np.asarray(baked.uv)
+    uv = np.ascontiguousarray(uv, dtype=np.float32)
+    fuv = _host(baked.face_uv, np.int32, "face_uv")
+    if uv.ndim != 2 or uv.shape[1] != 2 or fuv.shape != f.shape:
+        raise ValueError(f"uv must be [T, 2] and face_uv [F, 3] like the faces; got {uv.shape}, {fuv.shape}")
+    if n is not None and n.shape != v.shape:
+        raise ValueError(f"normals must be [V, 3] like the vertices; got {n.shape}")
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    written = {}
+    for key, statement in (("albedo", "map_Kd"), ("normal", "norm"), ("radiance", "map_Ke")):
+        img = baked.maps.get(key)
+        if img is None:
+            continue
+        ext = "exr" if key == "radiance" else image_format
+        file = f"{stem}_{key}.{ext}"
+        if ext == "exr":
+            io_exr.write_exr(file, _image_f32(img))
+        else:
+            io_exr.write_png(file, _image_bytes(img, srgb and key == "albedo"))
+        written[key] = (statement, file)
+    with open(stem + ".mtl", "w") as fh:
+        fh.write(f"newmtl {name}\nKd 1 1 1\n")
+        for key, (statement, file) in written.items():
+            fh.write(f"{statement} {os.path.basename(file)}\n")
+    g = lambda row: " ".join("%.9g" % x for x in row)
+    lines = [f"mtllib {name}.mtl"]
+    lines += ["v " + g(r) for r in v]
+    if n is not None:
+        lines += ["vn " + g(r) for r in n]
+    lines += ["vt " + g(r) for r in uv]
+    lines.append(f"usemtl {name}")
+    if n is not None:
+        lines += ["f " + " ".join(f"{a + 1}/{t + 1}/{a + 1}" for a, t in zip(fa, ft)) for fa, ft in zip(f, fuv)]
+    else:
+        lines += ["f " + " ".join(f"{a + 1}/{t + 1}" for a, t in zip(fa, ft)) for fa, ft in zip(f, fuv)]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return {k: file for k, (_, file) in written.items()}
+
+
+def export_scene(model, bounds, resolution, level, path, size=1024, image_format="png", srgb=True, **bake_kw):
+    """extract_mesh -> bake_textures -> write_obj: the scene as a textured mesh at `path`; returns the BakedMesh.
+    bake_kw goes to bake_textures (maps, method, offset, cell, chunk_rows, env_rays)."""
+    mesh = extract_mesh(model, bounds, resolution, level, colors=None, chunk_rows=bake_kw.get("chunk_rows"))
+    baked = bake_textures(model, mesh, size=size, **bake_kw)
+    write_obj(path, baked, image_format=image_format, srgb=srgb)
+    return baked

@@ -500,6 +500,17 @@ class VirtualObject:
             albedo = mesh.colors if mesh.colors is not None else (0.8, 0.8, 0.8)
         return cls(mesh.vertices, mesh.faces, mesh.normals, albedo, roughness, device)
 
+    @classmethod
+    def from_baked(cls, baked, roughness=None):
+        """The object of a geometry.BakedMesh: its atlas UVs, its "albedo" map ("radiance" without one) as the albedo
+        texture and its "normal" map as the normal map, built from the fp32 images as they are (no 8-bit step).  Sample
+        it at level 0 (hit_attributes(radii=None)): the higher mip levels of a per-triangle atlas mix faces."""
+        col = baked.maps.get("albedo", baked.maps.get("radiance"))
+        nrm = baked.maps.get("normal")
+        return cls(baked.vertices, baked.faces, baked.normals, (0.8, 0.8, 0.8), roughness, uv=baked.uv,
+                   face_uv=baked.face_uv, albedo_map=None if col is None else Texture(col),
+                   normal_map=None if nrm is None else Texture(nrm))
+
     def transformed(self, matrix):
         """The object moved by a 4x4 matrix (points: M x; normals: the inverse transpose of its 3x3 part, renormalised).
         UVs and texture maps come along (the Texture objects are shared, not copied)."""
