@@ -957,6 +957,55 @@ int pn_atlas_encode_normals(int S, int c, int64_t F, int64_t V, const float* ver
                             float* out, void* stream);
 int pn_atlas_quantize(int64_t count, int C, const float* x, const float* table, uint8_t* out, void* stream);
 
+/* ---- relighting: virtual point and spot lights with omnidirectional shadow maps (pn_relight.hip) ----------------------
+ * Rows are rays with what the renderer found along them, so every camera works (the stereo panorama included):
+ * origins, directions [R, 3] as the ray generators give them (directions NOT normalised), depth [R] = t along that ray
+ * (the renderer's `distance`), normals [R, 3] or NULL, albedo and rgb [R, 3] (both, or neither when only visibility is
+ * wanted).  Lights: L device rows of PN_LIGHT_FLOATS = 16 floats: position p (0-2), RGB radiant intensity I (3-5), spot
+ * axis (6-8; all zero: an omni light; taken as given, pass a unit vector), cos_inner (9), cos_outer (10), r_min (11),
+ * reserved zeros (12-15).  Shadow maps: maps [L, Hm, Wm] fp32, one per light, of kind PN_CAM_PANO (Hm, Wm >= 2) or
+ * PN_CAM_CUBE (Hm = 6 Wm): the picture an identity-rotation camera of that kind at p takes of the EUCLIDEAN distance to
+ * the nearest surface along each pixel's unit ray.  Outputs, each optional: out [R, 3], direct [R, 3], visibility [R, L].
+ * Everything below is fp64 on the fp32 inputs (the scalars are fp32 too), operations in the written order, dot products
+ * (a0 b0 + a1 b1) + a2 b2, every output rounded once (as pn_shade).
+ * Row: valid iff 0 < t < +inf and, with normals, n finite and |n| > 1e-12; then n^ = n / |n| (n^ = 0 without normals).
+ *   X = o + t d.
+ * Light l, in index order:  w = p - X, r2 = w . w; the light contributes nothing (V = 0) unless r2 > 0.
+ *   l = w / sqrt(r2);  NoL = max(0, n^ . l), or 1 without normals;
+ *   s = clamp(((-(l . axis)) - cos_outer) / (cos_inner - cos_outer), 0, 1), spot = (s s) (3 - 2 s), or 1 for a zero axis;
+ *   g = NoL spot.  If g is not > 0 (NaN included): V = 0 and no texel is read.
+ * Visibility: Y = X + normal_offset n^, v = Y - p, rho = |v|; V = 0 unless 0 < rho < +inf.
+ *   (qx, qy, face) = the position of direction v by pn_reproject's inverse projection, in fp64: PANO phi = atan2(hypot(vx,
+ *   vz), vy), theta = atan2(vx, vz), u = -theta / (2 pi), qx = (u - floor u) Wm, qy = phi / pi Hm; CUBE the table of that
+ *   section with S = Wm (cube_pos of pn_rays.h), qy within the face.
+ *   tan = min(sqrt(max(0, 1 - NoL NoL)) / NoL, 10);  delta = pi / Hm (PANO) or 2 / Wm (CUBE): the angular size of a texel;
+ *   slope = ((((bias_slope rho) delta) tan) (k + 1)) / 2, or 0 without normals;  k = pcf, odd, <= PN_RELIGHT_MAX_PCF.
+ *   Samples: for b < k (outer), a < k (inner): position (qx + (a - (k - 1) / 2), qy + (b - (k - 1) / 2)), and around
+ *   (x - 1/2, y - 1/2) the four bilinear taps of pn_reproject's rule: x0 = floor, x1 = x0 + 1, weights wx = the fraction;
+ *   a panorama's columns wrap and its rows clamp (so at a pole the window repeats the last row, and does not cross to the
+ *   opposite meridian), a cube's taps clamp within the face (nothing is filtered across a seam).
+ *   Tap with texel z: dark (c = 0) iff z is finite, z > 0 and rho > ((z (1 + bias_rel)) + bias_abs) + slope; else c = 1:
+ *   a NaN, Inf, zero or negative texel is "no surface" and lights.
+ *   Sample = ((w00 c00 + w01 c01) + w10 c10) + w11 c11, w00 = (1 - wy)(1 - wx), w01 = (1 - wy) wx, w10 = wy (1 - wx),
+ *   w11 = wy wx;  V = (the samples summed in that order) / (k k).
+ * Shading: where V > 0, E_c = E_c + ((I_c g) V) / max(r2, r_min r_min) (a light with V = 0 adds nothing);
+ *   direct_c = (albedo_c / pi) E_c: Lambert, the convention of pn_shade's diffuse = albedo / pi shading, with I in radiance
+ *   units x length^2 (radiant intensity: a light of intensity I at distance r facing the surface gives E = I / r^2);
+ *   out_c = fl(ambient rgb_c + direct_c), visibility[r, l] = fl(V).
+ * An invalid row: direct = 0, V = 0 for every light, out = fl(ambient rgb).  L = 0 is legal: out = fl(ambient rgb).
+ * One row per thread, the lights in index order, no atomics: repeated calls give the same bits, whatever R and however
+ * the rows are split over calls.  R = 0 launches nothing.
+ * Errors: PN_ERR_BAD_SHAPE (R or L < 0, pcf even or outside [1, PN_RELIGHT_MAX_PCF], a non-finite scalar, a negative
+ * bias_abs / bias_rel / bias_slope, Hm or Wm < 2, Hm Wm >= 2^31, a cube with Hm != 6 Wm), PN_ERR_UNSUPPORTED (a map kind
+ * other than PANO and CUBE), PN_ERR_NULL (origins, directions or depth; lights or maps with L > 0; albedo or rgb missing
+ * while out or direct is wanted). */
+#define PN_LIGHT_FLOATS 16
+#define PN_RELIGHT_MAX_PCF 7
+int pn_relight(int64_t R, const float* origins, const float* directions, const float* depth, const float* normals,
+               const float* albedo, const float* rgb, int L, const float* lights, int map_kind, int Hm, int Wm,
+               const float* maps, float ambient, float normal_offset, float bias_abs, float bias_rel, float bias_slope,
+               int pcf, float* out, float* direct, float* visibility, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

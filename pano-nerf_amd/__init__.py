@@ -22,6 +22,8 @@ Public surface (mirrors the reference's names):
                                   warping of rendered frames to other poses: warp_view, render_path_warped (HIP kernels)
     objects                       virtual object insertion: ray / triangle tracing, the reference's Lambertian and microfacet
                                   shading under light probes, cast shadows, insert_object / insert_path (HIP kernels)
+    relight                       virtual point and spot lights on rendered views: shadow maps rendered from the model's own
+                                  depth, per-pixel visibility and Lambert shading, relight_view / relight_path (HIP kernel)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -46,6 +48,7 @@ from . import lighting  # noqa
 from . import ibl  # noqa
 from . import views  # noqa
 from . import objects  # noqa
+from . import relight  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

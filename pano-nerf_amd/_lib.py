@@ -108,6 +108,7 @@ SIGNATURES = {
     "pn_atlas_texels": ("i", "iill" + "ppp" + "pppppp" + "p"),
     "pn_atlas_encode_normals": ("i", "iill" + "pp" + "ppppp" + "p"),
     "pn_atlas_quantize": ("i", "lippp" + "p"),
+    "pn_relight": ("i", "l" + "pppppp" + "ip" + "iiip" + "fffff" + "i" + "ppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),
