@@ -1006,6 +1006,62 @@ int pn_relight(int64_t R, const float* origins, const float* directions, const f
                const float* maps, float ambient, float normal_offset, float bias_abs, float bias_rel, float bias_slope,
                int pcf, float* out, float* direct, float* visibility, void* stream);
 
+/* ---- emitters: the light sources of an HDR probe as connected bright regions with their radiometry (pn_emitters.hip) ----
+ * Probes are read as pn_probe_sh reads them: x[p * probe_stride + c * cs + pix * ps], pix = i W + j row-major over an
+ * H x W equirectangular image, H, W >= 2; dirs [H W, 3] and omega [H W] are the table of the lighting section.
+ * Luminance: Y = ((double)R + G + B) / 3.0, the mean pn_shadow_ratio uses for a probe pixel.
+ * Emitter pixel: Y > threshold[p], strict and in fp64; a NaN Y (or a NaN threshold) is no emitter, Y = +inf is one.
+ * Default threshold (pn_emitter_threshold): fl(ratio exp(sum_pix omega ln max(Y, 1e-6) / sum_pix omega)), the sums over the
+ *   pixels with finite Y, in fp64: ratio times the solid-angle-weighted GEOMETRIC mean, because the arithmetic mean of a
+ *   probe is dominated by the very lamps it is meant to find.  The rule and the usual ratio of 8 are conventions, not
+ *   measurements.  One workgroup of 1024 threads per probe; thread t adds pixels t, t + 1024, ... in order, then a fixed tree.  A probe
+ *   with no finite pixel gets NaN: nothing in it is an emitter.
+ * Adjacency: the 8-neighbourhood with column W - 1 next to column 0, the diagonals across that seam included ((i, 0) touches
+ *   (i + 1, W - 1)); rows 0 and H - 1 are NOT joined across the poles.
+ * Labels: int32 [P, H, W], -1 for background; the components of a probe are numbered 0 .. C - 1 in ascending order of
+ *   their smallest pixel index, which fixes the result whatever the schedule.  Three calls:
+ *   pn_emitter_labels   label equivalence (union-find over pixel indices; 32-bit atomicMin on parent, so the surviving root
+ *                       of a component is its smallest pixel index): parent [P H W] is workspace, roots [P, H, W] gets
+ *                       every pixel's root index within its probe (-1 background), flags [P, H, W] gets 1 at a root, else 0
+ *   (the caller)        prefix = the inclusive running count of flags along each probe, int32 [P, H W]
+ *   pn_emitter_compact  labels (on entry: roots) becomes prefix[root] - 1 in place, count[p] = prefix[p, H W - 1]
+ * Record of component c of probe p (pn_emitter_stats), row s = p Cmax + c of every output; all sums in fp64 on the fp32
+ *   inputs, each output rounded once.  The caller passes the pixels grouped by component: order [N] int64 holds global
+ *   pixel indices p H W + pix, and starts [P Cmax + 1] int64 the offsets of the rows in it, so that order[starts[s] ..
+ *   starts[s + 1]) are the pixels of row s in ascending order (a stable sort by label).  One wave per row: lane l adds
+ *   elements l, l + 64, ... in order and the lanes meet in the xor butterfly 32, 16, .., 1: a fixed order, no floating-point
+ *   atomics, the same bits on every call.  The work is proportional to the pixels listed plus the rows, not to C x H W.
+ *     pixels          the number of pixels
+ *     omega           sum omega_pix
+ *     flux [3]        sum L_c omega_pix
+ *     lum_flux        sum Y omega_pix
+ *     direction [3]   normalize(sum Y omega_pix d_pix); where that sum's norm is below 1e-12 lum_flux (or is zero or not
+ *                     finite) the direction of the peak pixel
+ *     peak, peak_index   the largest Y and its pixel index, the lowest index among ties
+ *     spread          the largest angle atan2(|direction x d_pix|, direction . d_pix) over the component's pixels
+ *     angular_radius  acos(1 - min(omega, 4 pi) / (2 pi)): the cap of equal solid angle
+ *     distance        sum Y omega dist / sum Y omega over the pixels with 0 < dist < +inf of distance [P, H W] (contiguous);
+ *                     NaN with no such pixel or with distance = NULL
+ *   A row with starts[s] = starts[s + 1] is not written: zero the outputs first.  Entries of order that are not pixels of
+ *   the row's probe are skipped.
+ * The light a component stands for, in pn_relight's units: position = probe position + direction distance, radius =
+ *   distance sin(min(angular_radius, pi / 2)), intensity[3] = flux distance^2: a point light of that intensity adds `flux`
+ *   to the irradiance of a surface at the probe that faces it, which is what the component adds in pn_probe_irradiance up
+ *   to sum lum_flux 2 sin(spread / 2) (|relu(n . d) - relu(n . u)| <= |d - u|).
+ * Errors: PN_ERR_BAD_SHAPE (P <= 0 or >= 2^25, H or W < 2, H W >= 2^30, P H W >= 2^39, a ratio that is not finite and
+ * positive, Cmax < 0 or > H W, N < 0 or > P H W), PN_ERR_NULL (any pointer but `distance`; `order` may be null with N = 0).
+ * Cmax = 0 launches nothing. */
+int pn_emitter_threshold(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+                         const float* omega, double ratio, float* threshold, void* stream);
+int pn_emitter_labels(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+                      const float* threshold, int32_t* parent, int32_t* roots, int32_t* flags, void* stream);
+int pn_emitter_compact(int64_t P, int H, int W, const int32_t* prefix, int32_t* labels, int32_t* count, void* stream);
+int pn_emitter_stats(int64_t P, int H, int W, const float* x, int64_t probe_stride, int64_t cs, int64_t ps,
+                     const float* dirs, const float* omega, const float* distance, int Cmax, int64_t N,
+                     const int64_t* order, const int64_t* starts, int32_t* pixels, float* omega_out, float* flux,
+                     float* lum_flux, float* direction, float* peak, int32_t* peak_index, float* spread,
+                     float* angular_radius, float* distance_out, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -24,6 +24,9 @@ Public surface (mirrors the reference's names):
                                   shading under light probes, cast shadows, insert_object / insert_path (HIP kernels)
     relight                       virtual point and spot lights on rendered views: shadow maps rendered from the model's own
                                   depth, per-pixel visibility and Lambert shading, relight_view / relight_path (HIP kernel)
+    emitters                      the captured scene's own light sources: connected bright regions of HDR probes (wrapped
+                                  8-connectivity), their flux, direction and distance, as relight.PointLight objects and a
+                                  KHR_lights_punctual-style JSON, and the residual environment without them (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -49,6 +52,7 @@ from . import ibl  # noqa
 from . import views  # noqa
 from . import objects  # noqa
 from . import relight  # noqa
+from . import emitters  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

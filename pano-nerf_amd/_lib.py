@@ -109,6 +109,10 @@ SIGNATURES = {
     "pn_atlas_encode_normals": ("i", "iill" + "pp" + "ppppp" + "p"),
     "pn_atlas_quantize": ("i", "lippp" + "p"),
     "pn_relight": ("i", "l" + "pppppp" + "ip" + "iiip" + "fffff" + "i" + "ppp" + "p"),
+    "pn_emitter_threshold": ("i", "liip" + "lll" + "pdp" + "p"),
+    "pn_emitter_labels": ("i", "liip" + "lll" + "pppp" + "p"),
+    "pn_emitter_compact": ("i", "liippp" + "p"),
+    "pn_emitter_stats": ("i", "liip" + "lll" + "ppp" + "il" + "pp" + "p" * 10 + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),
