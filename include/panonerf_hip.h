@@ -1062,6 +1062,54 @@ int pn_emitter_stats(int64_t P, int H, int W, const float* x, int64_t probe_stri
                      float* lum_flux, float* direction, float* peak, int32_t* peak_index, float* spread,
                      float* angular_radius, float* distance_out, void* stream);
 
+/* ---- TSDF fusion: posed depth images integrated into a truncated signed distance volume (pn_fusion.hip) -----------------
+ * Grid: pn_grid_points' grid (every axis >= 2, nx ny nz < 2^31), vertex v = (i ny + j) nz + k; tsdf and weight are
+ * contiguous fp32 [nx, ny, nz], read and written in place.  weight = 0 marks a voxel no view has seen: the caller zeroes
+ * weight for a fresh volume, and where weight is 0 the content of tsdf is ignored on input.
+ * Views: S depth images of ONE central camera (kind, H, W, params; PANO, PINHOLE, CUBE or FISHEYE as in the camera section,
+ * params a HOST array as for pn_reproject; STEREO_PANO is PN_ERR_UNSUPPORTED) at the poses c2ws, a device array [S, 16] of
+ * row-major c2w (R = c2w[:3,:3], o = c2w[:3, 3]).  depth [S, H, W] is the distance t along the ray the samplers give each
+ * pixel, exactly what pn_warp_splat reads (the renderer's depth output; for a pinhole that ray is not normalised).
+ * confidence [S, H, W] or NULL, view_weights device [S] or NULL.
+ * Everything below is fp64 on the fp32 inputs (the scalars are fp32 too and are widened first), operations in the written
+ * order, dot products (a0 b0 + a1 b1) + a2 b2, every output rounded once (as pn_relight).
+ * Voxel (i, j, k):  X = (x0 + i dx, y0 + j dy, z0 + k dz);  A = B = 0.  Then for each view s in index order:
+ *   1. v = X - o_s,  e_k = (R[0][k] v_0 + R[1][k] v_1) + R[2][k] v_2  (e = R_s^T v),  rho = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2);
+ *      skip the view unless 0 < rho < +inf.
+ *   2. (qx, qy, face) = the position of direction e by pn_reproject's inverse projection, in fp64, with its validity rules:
+ *      PANO     phi = atan2(hypot(e_x, e_z), e_y), theta = atan2(e_x, e_z), u = -theta / (2 pi), qx = (u - floor u) W,
+ *               qy = phi / pi H; always valid.
+ *      PINHOLE  q = cam2pix @ e (params[9..17], row by row); valid iff q_z > 0 and (qx, qy) = (q_x, q_y) / q_z lies in
+ *               [0, W] x [0, H].
+ *      FISHEYE  r = hypot(e_x, e_y), theta = atan2(r, -e_z); valid iff theta <= theta_max and (qx, qy) = (W / 2 + (f theta)
+ *               e_x / r, H / 2 - (f theta) e_y / r) (the centre at r = 0) lies in [0, W] x [0, H].
+ *      CUBE     the table of the camera section with S = W (cube_pos of pn_rays.h), qy within the face; always valid.
+ *      Skip the view where that is invalid.
+ *   3. The NEAREST pixel: column min(max(floor qx, 0), W - 1), row min(max(floor qy, 0), rows - 1) with rows = H, or rows = W
+ *      and the row counted within `face` for a cube.  Depth is not interpolated: a bilinear fetch across a depth
+ *      discontinuity invents a surface between foreground and background that no view saw.
+ *   4. t = depth[s, row, column];  skip unless 0 < t < +inf and t <= depth_max (NaN, 0, negative and Inf are no surface).
+ *   5. w = view_weights[s] (1 if NULL), times confidence[s, row, column] if given;  skip unless 0 < w < +inf.
+ *   6. z = t |dc|, dc the camera-space direction of that pixel's centre as pn_warp_splat defines it: for a PINHOLE
+ *      c_k = (p[3k] (column + 1/2) + p[3k + 1] (row + 1/2)) + p[3k + 2] of pix2cam and |dc| = sqrt((c_0 c_0 + c_1 c_1) + c_2 c_2);
+ *      exactly 1 for the other kinds (z = t).  So z is the Euclidean distance of the surface that pixel saw.
+ *   7. sdf = z - rho: the signed distance along the voxel's own ray (positive in front of the surface).  Skip if
+ *      sdf < -trunc: the voxel is behind the surface and unseen from this view.
+ *   8. d = min(1, sdf / trunc);  A = A + w d,  B = B + w.
+ * After the views: if B == 0 the voxel keeps its bits (tsdf and weight).  Otherwise, with W0 = weight[v] and D0 = tsdf[v]
+ * (D0 = 0 if W0 == 0):  W1 = W0 + B,  tsdf[v] = fl((D0 W0 + A) / W1),  weight[v] = fl(min(W1, max_weight)): the weighted
+ * running mean of the usual TSDF fusion, with the weight capped so that later views can still move an old volume.
+ * One voxel per thread, the views in index order inside the kernel, A and B in registers, no atomics: repeated calls give
+ * the same bits, whatever the launch geometry.  One launch takes all S views, so nothing carries between launches; two
+ * calls over views [0, a) and [a, S) round tsdf and weight to fp32 in between and are NOT the one call over [0, S).
+ * Errors: PN_ERR_UNSUPPORTED (an unknown kind, STEREO_PANO), PN_ERR_BAD_SHAPE (a grid axis < 2, nx ny nz >= 2^31, S <= 0, a
+ * size below the kind's minimum, a cube with H != 6 W, S H W >= 2^31, trunc not positive and finite, depth_max or
+ * max_weight not > 0 (+inf is allowed), fisheye params not positive), PN_ERR_NULL (params_host, c2ws, depth, tsdf, weight). */
+int pn_tsdf_integrate(int nx, int ny, int nz, float x0, float y0, float z0, float dx, float dy, float dz, int S, int kind,
+                      int H, int W, const float* params_host, const float* c2ws, const float* depth, const float* confidence,
+                      const float* view_weights, float trunc, float depth_max, float max_weight, float* tsdf, float* weight,
+                      void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -27,6 +27,9 @@ Public surface (mirrors the reference's names):
     emitters                      the captured scene's own light sources: connected bright regions of HDR probes (wrapped
                                   8-connectivity), their flux, direction and distance, as relight.PointLight objects and a
                                   KHR_lights_punctual-style JSON, and the residual environment without them (HIP kernels)
+    fusion                        TSDF fusion: rendered (or captured) depth of posed panorama, pinhole, cube-map and fisheye
+                                  views integrated into a signed distance volume, and the mesh of its zero crossing with
+                                  the field's normals and colours: TSDFVolume, fuse_views, fused_mesh (HIP kernel)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -53,6 +56,8 @@ from . import views  # noqa
 from . import objects  # noqa
 from . import relight  # noqa
 from . import emitters  # noqa
+from . import fusion  # noqa
+from .fusion import TSDFVolume, fuse_views, fused_mesh  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

@@ -113,6 +113,7 @@ SIGNATURES = {
     "pn_emitter_labels": ("i", "liip" + "lll" + "pppp" + "p"),
     "pn_emitter_compact": ("i", "liippp" + "p"),
     "pn_emitter_stats": ("i", "liip" + "lll" + "ppp" + "il" + "pp" + "p" * 10 + "p"),
+    "pn_tsdf_integrate": ("i", "iii" + "f" * 6 + "iiii" + "ppppp" + "fff" + "pp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

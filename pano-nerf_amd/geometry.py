@@ -9,6 +9,7 @@ fallback.  The only host synchronisation is the copy of the two mesh totals that
     density_grid(model, bounds, resolution)     sigma on an [nx, ny, nz] vertex grid
     marching_tetrahedra(sigma, level, bounds)   (vertices [V, 3], faces [F, 3] int32) of {sigma > level}
     extract_mesh(model, bounds, resolution, level)  Mesh(vertices, faces, normals, colors)
+                                                (fusion.fused_mesh: the same Mesh from fused depth instead of a density level)
     write_ply(path, vertices, faces, normals, colors)  binary little-endian PLY
     read_ply(path)                              Mesh of host numpy arrays from such a file (binary or ASCII)
     read_obj(path)                              ObjMesh of host numpy arrays from a Wavefront OBJ (+ MTL) file
@@ -246,17 +247,37 @@ def marching_tetrahedra(sigma, level, bounds=None):
     return verts, faces
 
 
-def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, colors="auto", chunk_rows=None):
-    """Mesh(vertices [V, 3], faces [F, 3] int32, normals [V, 3] | None, colors [V, 3] | None) of {sigma > level} on the
-    model's device: density_grid -> marching_tetrahedra, then the field queried at the vertices with the grid's
-    variance.  normals: the model's normals (-grad sigma, normalised).  colors: "auto" (albedo for PanoMipNeRF, radiance
-    for MipNeRF), "albedo", "radiance" (rgb seen along -normal) or None."""
+def _mesh_colors(model, colors):
+    """the colour rule of extract_mesh and fusion.fused_mesh, with "auto" resolved for the model"""
     if colors not in ("auto", "albedo", "radiance", None):
         raise ValueError(f"colors must be 'auto', 'albedo', 'radiance' or None; got {colors!r}")
     if colors == "auto":
         colors = "albedo" if model._NC == 5 else "radiance"
     if colors == "albedo" and model._NC != 5:
         raise ValueError(f"colors='albedo' needs a PanoMipNeRF (5 density channels); {type(model).__name__} has none")
+    return colors
+
+
+def _field_mesh(model, verts, faces, variance, normals, colors, chunk_rows):
+    """Mesh of (verts, faces) with the field queried at the vertices: the model's normals, and `colors` (_mesh_colors')"""
+    nrm = col = None
+    want = (("normal",) if (normals or colors == "radiance") else ()) + (("albedo",) if colors == "albedo" else ())
+    if want:
+        q = query_field(model, verts, variance, outputs=want, chunk_rows=chunk_rows)
+        nrm, col = q.get("normal"), q.get("albedo")
+        if colors == "radiance":
+            col = query_field(model, verts, variance, viewdirs=-nrm, outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
+        if not normals:
+            nrm = None
+    return Mesh(verts, faces, nrm, col)
+
+
+def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, colors="auto", chunk_rows=None):
+    """Mesh(vertices [V, 3], faces [F, 3] int32, normals [V, 3] | None, colors [V, 3] | None) of {sigma > level} on the
+    model's device: density_grid -> marching_tetrahedra, then the field queried at the vertices with the grid's
+    variance.  normals: the model's normals (-grad sigma, normalised).  colors: "auto" (albedo for PanoMipNeRF, radiance
+    for MipNeRF), "albedo", "radiance" (rgb seen along -normal) or None."""
+    colors = _mesh_colors(model, colors)
     if level is None:
         raise ValueError("level is required")
     res = _resolution(resolution)
@@ -268,16 +289,7 @@ def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, 
     sigma = density_grid(model, bounds, res, variance, chunk_rows)
     verts, faces = marching_tetrahedra(sigma, level, bounds)
     del sigma
-    nrm = col = None
-    want = (("normal",) if (normals or colors == "radiance") else ()) + (("albedo",) if colors == "albedo" else ())
-    if want:
-        q = query_field(model, verts, variance, outputs=want, chunk_rows=chunk_rows)
-        nrm, col = q.get("normal"), q.get("albedo")
-        if colors == "radiance":
-            col = query_field(model, verts, variance, viewdirs=-nrm, outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
-        if not normals:
-            nrm = None
-    return Mesh(verts, faces, nrm, col)
+    return _field_mesh(model, verts, faces, variance, normals, colors, chunk_rows)
 
 
 def write_ply(path, vertices, faces, normals=None, colors=None):
