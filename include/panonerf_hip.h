@@ -1110,6 +1110,94 @@ int pn_tsdf_integrate(int nx, int ny, int nz, float x0, float y0, float z0, floa
                       const float* view_weights, float trunc, float depth_max, float max_weight, float* tsdf, float* weight,
                       void* stream);
 
+/* ---- mesh operations: connected components and quadric vertex clustering of triangle meshes (pn_meshops.hip) -----------
+ * A mesh is vertices [V, 3] fp32 and faces [F, 3] int32, both contiguous, V and F < 2^31.  Every kernel checks the indices
+ * it reads: a face with a corner outside [0, V) takes no part anywhere (pn_mesh_check reports it so that the caller can
+ * raise first).  Sorts, scans and compactions are the caller's; everything that computes is here.  All floating-point
+ * work is fp64 on the fp32 inputs, operations in the written order (dot products (a0 b0 + a1 b1) + a2 b2, cross products
+ * (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0)), each output rounded once; no floating-point atomics; the same bits on
+ * every call.
+ *
+ * pn_mesh_check: bad[0] = 1 if a coordinate is not finite, bad[1] = 1 if a face index is outside [0, V); else 0.
+ *   vertices may be NULL: then only the faces are judged.
+ *
+ * Components.  Two faces are connected if they share a vertex INDEX.  Union-find over vertex indices (pn_unionfind.h, the
+ * loop of the emitters; termination: DESIGN.md 6j): a vertex some face uses starts as its own parent, every other vertex
+ * as -1; one thread per face unites v0-v1 and v1-v2 with 32-bit atomicMin, so the root of a component is its smallest
+ * vertex index whatever the schedule.  Three steps:
+ *   pn_mesh_components  parent [V] is workspace; roots [V] gets every vertex's root (-1: no face uses it), flags [V] 1 at a root
+ *   (the caller)        prefix = the inclusive running count of flags, int32 [V]
+ *   pn_mesh_labels      vertex_label [V] = prefix[root] - 1 (-1 for an unused vertex), face_label [F] = the label of the
+ *                       face's first corner, count[0] = prefix[V - 1]: labels 0 .. C - 1 in ascending order of the root
+ * pn_mesh_component_stats: the record of every component.  The caller passes the faces grouped by label: order [F] int64
+ *   (a STABLE sort of the face indices by face_label) and starts [C + 1] int64, so that order[starts[c] .. starts[c + 1])
+ *   are the faces of component c in ascending index.  That list is cut into chunks of 4096: chunk j holds its elements
+ *   [4096 j, 4096 (j + 1)).  chunk_starts [C + 1] int64 is the running count of ceil(n_c / 4096), from 0; B >= chunk_starts[C]
+ *   is the number of workgroups launched (F / 4096 + C bounds it without a host copy) and work holds 10 B doubles.
+ *   One workgroup of 256 threads per chunk: thread t adds elements t, t + 256, ... of the chunk in order, starting from
+ *   0.0; the 64 lanes of a wave meet in the xor butterfly 32, 16, .., 1; thread 0 adds waves 0, 1, 2, 3 in order.  Then one
+ *   thread per component adds its chunks' sums in ascending j, sequentially, from 0.0.  The work is one visit of every face
+ *   plus one workgroup per chunk and one thread per component, not
+ *   C x F.  With n = (b - a) x (c - a) of a face (a, b, c):
+ *     nfaces    the number of faces                      nverts   the number of vertices with that label (integer atomics)
+ *     area      fl((sum sqrt((n0 n0 + n1 n1) + n2 n2)) / 2)
+ *     volume    fl((sum (a0 x0 + a1 x1) + a2 x2) / 6) with x = b x c: the signed volume, positive for outward winding
+ *     bbox [6]  min x, y, z then max x, y, z over the faces' corners (fp32, exact)
+ *   All five outputs must be zeroed by the caller; a component without a valid face is not written.
+ *
+ * Quadric vertex clustering (Lindstrom 2000 on Rossignac-Borrel cells).
+ *   Cells: lo is fp32 per axis, cell one fp32 scalar > 0, n per axis >= 1.  The cell index of a coordinate v on an axis is
+ *     floor((double(v) - double(lo)) / double(cell)) clamped to [0, n - 1] (the clamp in fp64), and the key of a vertex is
+ *     (ix ny + iy) nz + iz, int64 (nx ny nz must fit 63 bits).  pn_cluster_keys writes keys [V].  A cluster is an occupied
+ *     cell; clusters are ordered by ascending key (the caller sorts the keys STABLY, takes the unique ones - cluster_keys [K]
+ *     - and with them rank [V] int32, vertex_order [V] = the vertices grouped by cluster in ascending index, and
+ *     vertex_starts [K + 1]).
+ *   Faces (pn_cluster_faces, K < 2^21): out_faces [F, 3] = rank of each corner, winding and corner order kept; face_keys
+ *     [F] = (s0 << 42) | (s1 << 21) | s2 of the sorted triple s0 < s1 < s2, or 2^63 - 1 where two corners are equal (the
+ *     face is dropped).  Faces of equal key have the same unordered vertex set, whatever their winding: the caller keeps
+ *     the lowest face index of each key (a stable sort), survivors in their original order.
+ *   Solve (pn_cluster_solve), ONE THREAD PER CLUSTER, everything sequential.  With c = the cell centre,
+ *     c_a = double(lo_a) + (double(i_a) + 0.5) double(cell):
+ *     1. for the vertices v of the cluster in ascending index (vertex_order[vertex_starts[k] .. vertex_starts[k + 1])):
+ *        m += double(v) - c per axis, and the sums of the rows of normals and colors (where given); cnt counts them.
+ *        xbar = m / cnt.  out_normals = the mean g / cnt divided by its norm sqrt((g0 g0 + g1 g1) + g2 g2), or 0 where that
+ *        norm is below 1e-12; out_colors = the mean.
+ *     2. for the incidences i = 3 f + corner whose corner's vertex lies in the cluster, in ascending i (incidence_order
+ *        [3 F] = a stable sort of i by the cluster rank of faces[i], incidence_starts [K + 1]): with the face (a, b, c_),
+ *        u = b - a, w = c_ - a, n = u x w (unnormalised: weights of area squared, no sqrt), d = -((n0 (a0 - c0) + n1 (a1 - c1))
+ *        + n2 (a2 - c2)):  A00 += n0 n0, A01 += n0 n1, A02 += n0 n2, A11 += n1 n1, A12 += n1 n2, A22 += n2 n2, b_k += n_k d.
+ *        A face with two corners in the cluster is added twice; a zero-area face adds zeros.
+ *     3. t = (A00 + A11) + A22.  If t == 0: x = xbar, flags = 2.  Otherwise s = lam t, q_kk = A_kk + s, r_k = s xbar_k - b_k,
+ *        and LDL^T with + - * / only:
+ *          l10 = A01 / q00, l20 = A02 / q00, d1 = q11 - l10 A01, u12 = A12 - l20 A01, l21 = u12 / d1,
+ *          d2 = (q22 - l20 A02) - l21 u12, y1 = r1 - l10 r0, y2 = (r2 - l20 r0) - l21 y1,
+ *          x2 = y2 / d2, x1 = y1 / d1 - l21 x2, x0 = (r0 / q00 - l10 x1) - l20 x2.
+ *        x is accepted (flags = 0) iff every component is finite and |x_k| <= double(cell) 0.5; otherwise x = xbar and
+ *        flags = 1 (Lindstrom's fallback).  lam (1e-3 by convention) makes the system SPD with a condition number of
+ *        about 1 / lam: a flat or creased cluster is pulled to xbar along its free directions only.
+ *     4. out_vertices[k] = fl(c + x) per axis.
+ * Errors: PN_ERR_BAD_SHAPE (V or F negative or >= 2^31, C or K outside [0, V], B negative, K >= 2^21 in pn_cluster_faces, lo or cell not
+ * finite, cell <= 0, n < 1, nx ny nz beyond 63 bits, lam negative or not finite), PN_ERR_NULL (a required pointer; normals
+ * and colors and their outputs are optional, but an output needs its input).  V = 0, C = 0, K = 0 launch nothing. */
+int pn_mesh_check(int64_t V, int64_t F, const float* vertices, const int32_t* faces, int32_t* bad, void* stream);
+int pn_mesh_components(int64_t V, int64_t F, const int32_t* faces, int32_t* parent, int32_t* roots, int32_t* flags,
+                       void* stream);
+int pn_mesh_labels(int64_t V, int64_t F, const int32_t* faces, const int32_t* roots, const int32_t* prefix,
+                   int32_t* vertex_label, int32_t* face_label, int32_t* count, void* stream);
+int pn_mesh_component_stats(int64_t V, int64_t F, int64_t C, const float* vertices, const int32_t* faces,
+                            const int64_t* order, const int64_t* starts, const int64_t* chunk_starts, int64_t B,
+                            double* work, const int32_t* vertex_label, int32_t* nfaces, int32_t* nverts, float* area,
+                            float* volume, float* bbox, void* stream);
+int pn_cluster_keys(int64_t V, const float* vertices, float lox, float loy, float loz, float cell, int64_t nx, int64_t ny,
+                    int64_t nz, int64_t* keys, void* stream);
+int pn_cluster_faces(int64_t F, int64_t V, int64_t K, const int32_t* faces, const int32_t* rank, int32_t* out_faces,
+                     int64_t* face_keys, void* stream);
+int pn_cluster_solve(int64_t K, int64_t V, int64_t F, const float* vertices, const int32_t* faces, const float* normals,
+                     const float* colors, float lox, float loy, float loz, float cell, int64_t nx, int64_t ny, int64_t nz,
+                     const int64_t* cluster_keys, const int64_t* vertex_order, const int64_t* vertex_starts,
+                     const int64_t* incidence_order, const int64_t* incidence_starts, double lam, float* out_vertices,
+                     float* out_normals, float* out_colors, uint8_t* flags, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -30,6 +30,8 @@ Public surface (mirrors the reference's names):
     fusion                        TSDF fusion: rendered (or captured) depth of posed panorama, pinhole, cube-map and fisheye
                                   views integrated into a signed distance volume, and the mesh of its zero crossing with
                                   the field's normals and colours: TSDFVolume, fuse_views, fused_mesh (HIP kernel)
+    meshops                       cleaning exported meshes: connected components and debris removal, quadric vertex
+                                  clustering with the face count as a target, and an honest edge census (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -58,6 +60,8 @@ from . import relight  # noqa
 from . import emitters  # noqa
 from . import fusion  # noqa
 from .fusion import TSDFVolume, fuse_views, fused_mesh  # noqa
+from . import meshops  # noqa
+from .meshops import mesh_components, filter_components, simplify_mesh  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

@@ -114,6 +114,13 @@ SIGNATURES = {
     "pn_emitter_compact": ("i", "liippp" + "p"),
     "pn_emitter_stats": ("i", "liip" + "lll" + "ppp" + "il" + "pp" + "p" * 10 + "p"),
     "pn_tsdf_integrate": ("i", "iii" + "f" * 6 + "iiii" + "ppppp" + "fff" + "pp" + "p"),
+    "pn_mesh_check": ("i", "llppp" + "p"),
+    "pn_mesh_components": ("i", "llpppp" + "p"),
+    "pn_mesh_labels": ("i", "ll" + "p" * 6 + "p"),
+    "pn_mesh_component_stats": ("i", "lll" + "ppppp" + "lp" + "pppppp" + "p"),
+    "pn_cluster_keys": ("i", "lp" + "ffff" + "lll" + "p" + "p"),
+    "pn_cluster_faces": ("i", "lll" + "pppp" + "p"),
+    "pn_cluster_solve": ("i", "lll" + "pppp" + "ffff" + "lll" + "ppppp" + "d" + "pppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

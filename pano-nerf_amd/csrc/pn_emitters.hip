@@ -9,6 +9,7 @@
 // does not depend on the order in which they land.  Two calls on the same inputs give the same bits.  Radiance is read in
 // place through (probe, channel, pixel) strides, as pn_lighting.hip and pn_shade read it.
 #include "pn_common.h"
+#include "pn_unionfind.h"
 
 namespace {
 
@@ -77,46 +78,7 @@ __global__ __launch_bounds__(kThreads) void k_emitter_init(int64_t P, int64_t HW
     parent[e] = y > (double)threshold[p] ? (int32_t)pix : -1;  // strict; a NaN on either side compares false
 }
 
-__device__ __forceinline__ int32_t load_parent(const int32_t* parent, int32_t i) {
-    return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root above i.  Ends: by (P1) every step either stops (parent[i] == i) or moves to a strictly smaller index >= 0, so
-// there are at most i steps, whatever other waves write meanwhile.
-__device__ __forceinline__ int32_t find_root(const int32_t* parent, int32_t i) {
-    for (;;) {
-        const int32_t q = load_parent(parent, i);
-        if (q == i) return i;
-        i = q;
-    }
-}
-
-// Join the trees of a and b; the smaller root survives.  The standard label-equivalence form: try to hang the larger root
-// a under the smaller b with atomicMin; if a had stopped being a root in between (the atomic returned old != a), the edge
-// a -> old it held has been replaced by a -> min(old, b), so what is still owed is the union of old and b: retry from the
-// value the atomic returned.
-// Ends: let (a, b) be the pair after the two find_root calls and the swap, a > b.  A retry continues with (old, b) where
-// old = the value the atomic returned != a, hence old < a by (P1); find_root never raises an index.  So the sum a + b of
-// the pair falls by at least 1 per retry and is bounded below by 0: at most a + b retries, each of finitely many steps,
-// independent of the schedule.
-// Result: edges always point from a larger to a smaller index of the same component and every owed union is carried by
-// the wave that owes it until it is paid, so when the launch is over every component is one tree whose root is its
-// smallest pixel index - whatever the order in which the atomics landed.
-__device__ void unite(int32_t* parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        const int32_t old = atomicMin(parent + a, b);
-        if (old == a) return;  // a was a root and now hangs under b
-        a = old;
-    }
-}
+// load_parent / find_root / unite: pn_unionfind.h (shared with pn_meshops.hip), with the termination argument
 
 // every emitter pixel (i, j) unites with the emitters among (i, j - 1), (i - 1, j - 1), (i - 1, j), (i - 1, j + 1), columns
 // modulo W: each adjacent pair of the wrapped 8-neighbourhood exactly once (twice where W = 2 makes j - 1 and j + 1 one

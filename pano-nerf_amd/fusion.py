@@ -23,8 +23,7 @@ include/panonerf_hip.h, section "TSDF fusion".  Three conventions, not measureme
 depth_max = 0.98 far in fuse_views, and unknown = "solid" (space carving).
 
 Out of scope: colour fusion in the volume (colours come from the field, or from bake_textures on the mesh), hashed or
-sparse volumes, per-pixel footprint weighting, gradients, stereo panoramas (not a central projection), and any change to
-extract_mesh or export_scene.
+sparse volumes, per-pixel footprint weighting, gradients, and stereo panoramas (not a central projection).
 """
 import math
 
@@ -242,12 +241,15 @@ def fuse_views(model, camera, poses, bounds, resolution, trunc=None, env_rays=No
     return vol
 
 
-def fused_mesh(model, *volume_or_args, normals=True, colors="auto", unknown="solid", cull=False, chunk_rows=None, **fuse_kw):
+def fused_mesh(model, *volume_or_args, normals=True, colors="auto", unknown="solid", cull=False, chunk_rows=None,
+               simplify=None, min_component_faces=None, **fuse_kw):
     """geometry.Mesh(vertices, faces, normals, colors) of a fused volume: fused_mesh(model, volume) meshes a TSDFVolume,
     fused_mesh(model, camera, poses, bounds, resolution, **fuse_kw) runs fuse_views first.  Normals and colours are the
     field's at the vertices, by extract_mesh's rules (query_field with the grid's variance; colors "auto", "albedo",
     "radiance" or None), so the result goes straight into bake_textures, write_ply and write_obj.  Without a model,
-    TSDFVolume.mesh() is the model-free route."""
+    TSDFVolume.mesh() is the model-free route.  min_component_faces / simplify (a cell size or a dict of
+    meshops.simplify_mesh's keywords) run meshops.clean_mesh on the mesh first - cull=True keeps every island a view
+    happened to see - and the field is queried at the new vertices; with both None nothing of meshops runs."""
     colors = _mesh_colors(model, colors)
     _unknown(unknown)
     if len(volume_or_args) == 1 and isinstance(volume_or_args[0], TSDFVolume):
@@ -261,4 +263,7 @@ def fused_mesh(model, *volume_or_args, normals=True, colors="auto", unknown="sol
     if _model_device(model) != vol.device:
         raise RuntimeError(f"the volume is on {vol.device}, the model on {_model_device(model)}")
     verts, faces = vol.mesh(unknown, cull)
+    if simplify is not None or min_component_faces is not None:
+        from .meshops import clean_mesh
+        verts, faces = clean_mesh(verts, faces, simplify, min_component_faces)
     return _field_mesh(model, verts, faces, float(_variance(model, None, vol.step)), normals, colors, chunk_rows)

@@ -21,8 +21,9 @@ fallback.  The only host synchronisation is the copy of the two mesh totals that
     export_scene(model, bounds, resolution, level, path)   extract_mesh -> bake_textures -> write_obj
 
 The mesh contract (edge ids, vertex and face order, winding) and the atlas layout are stated in include/panonerf_hip.h.
-Out of scope of the baking: chart-based UV unwrapping, mesh decimation, several materials, and mip levels above 0 (a
-per-triangle atlas mixes neighbouring faces there: sample a baked asset at level 0, or let the engine re-atlas it).
+Out of scope of the baking: chart-based UV unwrapping, several materials, and mip levels above 0 (a per-triangle atlas
+mixes neighbouring faces there: sample a baked asset at level 0, or let the engine re-atlas it).  Removing debris and
+decimating a mesh before it is baked is ``meshops`` (export_scene's simplify / min_component_faces).
 """
 import collections
 import os
@@ -272,11 +273,14 @@ def _field_mesh(model, verts, faces, variance, normals, colors, chunk_rows):
     return Mesh(verts, faces, nrm, col)
 
 
-def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, colors="auto", chunk_rows=None):
+def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, colors="auto", chunk_rows=None,
+                 simplify=None, min_component_faces=None):
     """Mesh(vertices [V, 3], faces [F, 3] int32, normals [V, 3] | None, colors [V, 3] | None) of {sigma > level} on the
     model's device: density_grid -> marching_tetrahedra, then the field queried at the vertices with the grid's
     variance.  normals: the model's normals (-grad sigma, normalised).  colors: "auto" (albedo for PanoMipNeRF, radiance
-    for MipNeRF), "albedo", "radiance" (rgb seen along -normal) or None."""
+    for MipNeRF), "albedo", "radiance" (rgb seen along -normal) or None.  min_component_faces / simplify (a cell size or a
+    dict of simplify_mesh's keywords): meshops.clean_mesh between the extraction and the field query, so the normals and
+    colours are the field's at the NEW vertices; with both None nothing of meshops runs."""
     colors = _mesh_colors(model, colors)
     if level is None:
         raise ValueError("level is required")
@@ -289,6 +293,9 @@ def extract_mesh(model, bounds, resolution, level, variance=None, normals=True, 
     sigma = density_grid(model, bounds, res, variance, chunk_rows)
     verts, faces = marching_tetrahedra(sigma, level, bounds)
     del sigma
+    if simplify is not None or min_component_faces is not None:
+        from .meshops import clean_mesh
+        verts, faces = clean_mesh(verts, faces, simplify, min_component_faces)
     return _field_mesh(model, verts, faces, variance, normals, colors, chunk_rows)
 
 
@@ -893,10 +900,15 @@ def write_obj(path, baked, image_format="png", srgb=True):
     return {k: file for k, (_, file) in written.items()}
 
 
-def export_scene(model, bounds, resolution, level, path, size=1024, image_format="png", srgb=True, **bake_kw):
+def export_scene(model, bounds, resolution, level, path, size=1024, image_format="png", srgb=True, simplify=None,
+                 min_component_faces=None, **bake_kw):
     """extract_mesh -> bake_textures -> write_obj: the scene as a textured mesh at `path`; returns the BakedMesh.
-    bake_kw goes to bake_textures (maps, method, offset, cell, chunk_rows, env_rays)."""
-    mesh = extract_mesh(model, bounds, resolution, level, colors=None, chunk_rows=bake_kw.get("chunk_rows"))
+    bake_kw goes to bake_textures (maps, method, offset, cell, chunk_rows, env_rays).  min_component_faces drops the
+    components with fewer faces and simplify (a cell size, or a dict of meshops.simplify_mesh's keywords such as
+    {"target_faces": 20000}) decimates the mesh before it is baked: the normal map then carries the detail the
+    decimation removed.  With both None the result is what it was without them, bit for bit."""
+    mesh = extract_mesh(model, bounds, resolution, level, colors=None, chunk_rows=bake_kw.get("chunk_rows"),
+                        simplify=simplify, min_component_faces=min_component_faces)
     baked = bake_textures(model, mesh, size=size, **bake_kw)
     write_obj(path, baked, image_format=image_format, srgb=srgb)
     return baked
