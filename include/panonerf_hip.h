@@ -1198,6 +1198,86 @@ int pn_cluster_solve(int64_t K, int64_t V, int64_t F, const float* vertices, con
                      const int64_t* incidence_order, const int64_t* incidence_starts, double lam, float* out_vertices,
                      float* out_normals, float* out_colors, uint8_t* flags, void* stream);
 
+/* ---- mesh distance: the closest point of a triangle mesh to arbitrary points, and surface sampling (pn_meshdist.hip) -----
+ * A mesh is vertices [V, 3] fp32 and faces [F, 3] int32, contiguous, V and F < 2^31; points [P, 3] fp32.  Everything is
+ * fp64 on the fp32 inputs, separate operations in the written order (dot (a0 b0 + a1 b1) + a2 b2; cross (u1 w2 - u2 w1,
+ * u2 w0 - u0 w2, u0 w1 - u1 w0); "s + e t" is fl(s + fl(e t)) per axis), each output rounded to fp32 once.
+ * Valid faces: a face with an index outside [0, V) or a vertex coordinate that is not finite is never a candidate (the
+ * rule that gives it the empty box in pn_bvh_boxes).  The corners a, b, c are read from vertices and faces themselves, not
+ * from the tracer's tris rows.
+ * Point / triangle distance d2(p, f), with the closest point q and its barycentrics (u, v) in pn_trace_mesh's convention,
+ * q = (1 - u - v) a + u b + v c - Ericson's region classification ("Real-Time Collision Detection", 5.1.5):
+ *   ab = b - a, ac = c - a, n = ab x ac.  If n . n == 0 the face is its three edge segments, see below.  Otherwise, the
+ *   first rule that holds decides:
+ *   ap = p - a, d1 = ab . ap, d2 = ac . ap;            d1 <= 0 and d2 <= 0:              q = a, (u, v) = (0, 0)
+ *   bp = p - b, d3 = ab . bp, d4 = ac . bp;            d3 >= 0 and d4 <= d3:             q = b, (1, 0)
+ *   vc = d1 d4 - d3 d2;                                vc <= 0, d1 >= 0, d3 <= 0:        t = d1 / (d1 - d3), q = a + ab t, (t, 0)
+ *   cp = p - c, d5 = ab . cp, d6 = ac . cp;            d6 >= 0 and d5 <= d6:             q = c, (0, 1)
+ *   vb = d5 d2 - d1 d6;                                vb <= 0, d2 >= 0, d6 <= 0:        t = d2 / (d2 - d6), q = a + ac t, (0, t)
+ *   va = d3 d6 - d5 d4, g = d4 - d3, h = d5 - d6;      va <= 0, g >= 0, h >= 0:          t = g / (g + h), q = b + (c - b) t, (1 - t, t)
+ *   otherwise den = 1 / ((va + vb) + vc), u = vb den, v = vc den, q = (a + ab u) + ac v.
+ *   d2 = r . r with r = p - q.
+ *   Segment s .. e: se = e - s, L = se . se; t = 0 when L is not > 0 (a segment of length 0 is its end point s), else
+ *   t = ((p - s) . se) / L clamped to [0, 1]; q = s + se t.  A face without area takes the nearest of ab, bc, ca in that
+ *   order, a later segment replacing an earlier one only when its d2 is smaller (<): (u, v) = (t, 0), (1 - t, t), (0, 1 - t).
+ * Answer for point p: the lexicographic minimum of (d2, f) over the candidates - equal fp64 d2 keeps the lowest face
+ * index.  The search starts at best = max_distance^2 (the fp32 scalar squared in fp64; +inf: no limit), INCLUSIVE, with no
+ * face held; a candidate replaces the held one when d2 < best, or d2 == best and no face is held or its index is lower.
+ * Outputs: distance = fl(sqrt(d2)), face, closest = fl(q), bary = fl(u, v) of the winner.  No answer - a point with a
+ * coordinate that is not finite, F = 0, no candidate within reach: face = -1, distance = +inf, closest = bary = 0.
+ * pn_closest_point: brute force.  Every face in ascending index, staged through LDS in tiles of PN_MESHDIST_TILE; every
+ *   valid face is taken as a candidate.
+ * pn_closest_point_bvh: a walk of the nodes pn_bvh_tree wrote (layout above, unchanged), one point per thread, 64 threads
+ *   per workgroup, the traversal stack [PN_BVH_MAX_DEPTH][64] in LDS as the tracer's; no scratch.
+ *   Box bound: lb(p, box) = fl(((gx gx + gy gy) + gz gz) (1 - 2^-40)), g = max(max(lo - p, 0), p - hi) per axis, fp64 on
+ *   the fp32 box; an empty box (lo.x > hi.x) is infinitely far and is never entered.
+ *   Candidate rule: face f counts for p iff f is valid and lb(p, padded box of f) <= d2(p, f) (the box of pn_bvh_boxes).
+ *   The walk starts at row 0.  A child is skipped only when its box is empty or lb > best (strict); a leaf that is not
+ *   skipped is evaluated, must pass the candidate rule and then meets the replacement rule above; of two children to
+ *   enter, the one with the smaller bound is entered first (the left one on a tie) and the other pushed.  The walk ends
+ *   after F iterations at the latest (every internal node is entered at most once), also over a buffer that is no tree.
+ *   The tree cannot matter: a node's box is the exact min / max union of its children's, down to the padded triangle
+ *   boxes, and every operation of lb - fp64 subtraction from or of a fixed p, max, the square of a non-negative number,
+ *   addition, the final factor - is monotone, so a parent's bound never exceeds a child's.  For the winner (d2*, f*):
+ *   lb of every ancestor <= lb(f*) <= d2* <= best at all times, so every ancestor is entered whatever the topology and the
+ *   order, and the replacement rule is a minimum over a set, which no order changes.
+ *   The BVH result is the brute-force result wherever every valid face is a candidate.  The pad sees to that: q lies in the
+ *   unpadded box up to the rounding of "s + e t" (a few 2^-53 of the coordinates), so the padded box is nearer to p than q
+ *   is by at least about PN_BVH_PAD_ABS x mag = 4e-6 mag per axis it is outside on, and the factor 1 - 2^-40 covers lb's own
+ *   three roundings; the margin is many orders above fp64 rounding.  tests/test_meshdist_cpu.py counts the violations on
+ *   its scenes instead of trusting this (0), and reports the smallest margin.
+ * Surface sampling, the choice of face in integers:
+ *   pn_face_areas    area [F] fp64 = 0.5 sqrt(n . n), n = (b - a) x (c - a); 0 for a face that is not valid
+ *   (the caller)     largest = the maximum of area (exact), 1 device double
+ *   pn_face_weights  weight [F] int64 = floor(area / largest * 2^31) (the division first; 2^31 = PN_MESHDIST_WEIGHT_ONE), 0
+ *                    where area is 0 or largest is not positive and finite: 0 <= weight <= 2^31
+ *   (the caller)     cum_weight = the inclusive running sum of weight, int64 (exact), W = cum_weight[F - 1] <= F 2^31 < 2^62
+ *   pn_sample_surface  sample i of count (systematic sampling): threshold t_i = floor(i W / count), computed as
+ *                    i (W / count) + (i (W % count)) / count in int64 (i, count < 2^31: no product reaches 2^63); its face
+ *                    is the first f with cum_weight[f] > t_i (binary search), so face f gets floor or ceil of
+ *                    count weight[f] / W samples and a face of weight 0 none.  Barycentrics from the R2 sequence:
+ *                    r_k = x_k - floor(x_k), x_k = 0.5 + A_k double(i), A_1 = PN_MESHDIST_R2_A1, A_2 = PN_MESHDIST_R2_A2 (1 / g
+ *                    and 1 / g^2 of the plastic number g = 1.3247179572447460); when r_1 + r_2 > 1 both become 1 - r.
+ *                    (u, v) = (r_1, r_2), point = (a + (b - a) u) + (c - a) v.  Outputs points [count, 3], face [count]
+ *                    int32, bary [count, 2], rounded once.  A face that is not valid (cum_weight not of this mesh):
+ *                    face = -1, zeros.
+ * No atomics; the same bits on every call.  P = 0, count = 0 and F = 0 (areas, weights) launch nothing.
+ * Errors: PN_ERR_BAD_SHAPE (a negative count, V, F or count >= 2^31, max_distance negative or NaN, F = 0 in
+ * pn_closest_point_bvh and pn_sample_surface, W outside [1, 2^62]), PN_ERR_NULL. */
+#define PN_MESHDIST_TILE 256
+#define PN_MESHDIST_WEIGHT_ONE 2147483648.0
+#define PN_MESHDIST_R2_A1 0.7548776662466927
+#define PN_MESHDIST_R2_A2 0.5698402909980532
+int pn_closest_point(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,
+                     float max_distance, float* distance, int32_t* face, float* closest, float* bary, void* stream);
+int pn_closest_point_bvh(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,
+                         const float* nodes, float max_distance, float* distance, int32_t* face, float* closest,
+                         float* bary, void* stream);
+int pn_face_areas(int64_t F, int64_t V, const float* vertices, const int32_t* faces, double* area, void* stream);
+int pn_face_weights(int64_t F, const double* area, const double* largest, int64_t* weight, void* stream);
+int pn_sample_surface(int64_t count, int64_t W, int64_t F, int64_t V, const float* vertices, const int32_t* faces,
+                      const int64_t* cum_weight, float* points, int32_t* face, float* bary, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -32,6 +32,9 @@ Public surface (mirrors the reference's names):
                                   the field's normals and colours: TSDFVolume, fuse_views, fused_mesh (HIP kernel)
     meshops                       cleaning exported meshes: connected components and debris removal, quadric vertex
                                   clustering with the face count as a target, and an honest edge census (HIP kernels)
+    meshdist                      distances between surfaces: the closest point of a mesh to arbitrary points through the BVH,
+                                  area-weighted surface samples, Chamfer / Hausdorff / F-score / normal consistency of two
+                                  meshes and unsigned distance grids (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -62,6 +65,8 @@ from . import fusion  # noqa
 from .fusion import TSDFVolume, fuse_views, fused_mesh  # noqa
 from . import meshops  # noqa
 from .meshops import mesh_components, filter_components, simplify_mesh  # noqa
+from . import meshdist  # noqa
+from .meshdist import closest_point, sample_surface, compare_meshes  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

@@ -121,6 +121,11 @@ SIGNATURES = {
     "pn_cluster_keys": ("i", "lp" + "ffff" + "lll" + "p" + "p"),
     "pn_cluster_faces": ("i", "lll" + "pppp" + "p"),
     "pn_cluster_solve": ("i", "lll" + "pppp" + "ffff" + "lll" + "ppppp" + "d" + "pppp" + "p"),
+    "pn_closest_point": ("i", "lplplp" + "f" + "pppp" + "p"),
+    "pn_closest_point_bvh": ("i", "lplplpp" + "f" + "pppp" + "p"),
+    "pn_face_areas": ("i", "llppp" + "p"),
+    "pn_face_weights": ("i", "lppp" + "p"),
+    "pn_sample_surface": ("i", "llll" + "ppp" + "ppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),
