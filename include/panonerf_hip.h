@@ -1278,6 +1278,61 @@ int pn_face_weights(int64_t F, const double* area, const double* largest, int64_
 int pn_sample_surface(int64_t count, int64_t W, int64_t F, int64_t V, const float* vertices, const int32_t* faces,
                       const int64_t* cum_weight, float* points, int32_t* face, float* bary, void* stream);
 
+/* ---- winding number: the generalized winding number of a triangle mesh at arbitrary points (pn_winding.hip) -------------
+ * w(p) = (1 / 4 pi) sum_f Omega(p, f), the signed solid angles of the faces as seen from p (Jacobson et al. 2013): 1 inside
+ * and 0 outside a closed mesh wound so that (b - a) x (c - a) points outside, and a smooth blend of the two over holes,
+ * soups and duplicated faces.  Meshes, points, valid faces and the arithmetic are the "mesh distance" section's: fp64 on
+ * the fp32 inputs, separate operations in the written order, that section's dot and cross, each output rounded to fp32 once.
+ * A face that is not valid contributes nothing anywhere.
+ * Triangle term (van Oosterom and Strackee 1983), corners a, b, c of face f:
+ *   A = a - p, B = b - p, C = c - p;  num = A . (B x C);  if num == 0: Omega = 0.  Otherwise
+ *   la = sqrt(A . A), lb = sqrt(B . B), lc = sqrt(C . C),
+ *   den = ((la lb) lc + (A . B) lc) + ((B . C) la + (C . A) lb),  Omega = 2 atan2(num, den).
+ *   num == 0 is a point in the face's plane (on the face, an edge or a corner included): it takes the principal value 0, so
+ *   a signed zero never decides between +2 pi and -2 pi, and w on a closed surface is the mean of its two sides.
+ * w(p) = fl32(S / PN_WINDING_FOUR_PI), S the fp64 sum of the terms in the order stated below.  A point with a coordinate
+ * that is not finite gets NaN; F = 0 gives 0.
+ * pn_winding: the exact sum, brute force.  One point per thread, every face in ascending index staged through LDS in tiles
+ *   of PN_WINDING_TILE as pn_closest_point does; S takes the valid faces' terms in that order.
+ * pn_bvh_moments: one fp64 row per internal node of the nodes pn_bvh_tree wrote (layout unchanged), moments
+ *   [max(F - 1, 1), 8] = (g[3], r2, N[3], A).  A leaf of face f hands up its vector area m = 0.5 ((b - a) x (c - a)) (0.5
+ *   times each component), A_f = sqrt(m . m) and its centroid g_f = ((a + b) + c) / 3 per axis; zeros for a face that is not
+ *   valid.  A node, from its left and right child in that order:
+ *     N = N_left + N_right, A = A_left + A_right;
+ *     box = the fp32 min / max union of the two child boxes of its nodes row; an empty box (lo.x > hi.x) gives a zero row;
+ *     g = (A_left g_left + A_right g_right) / A per axis when A > 0, else (lo + hi) 0.5 of the box, in fp64;
+ *     r2 = (ex ex + ey ey) + ez ez, e = max(g - lo, hi - g) per axis: the squared distance from g to the farthest corner
+ *     of the box, so every vertex below the node lies within sqrt(r2) of g.
+ *   Bottom-up in one launch, no host synchronisation and no floating-point atomics: one thread per internal node arrives
+ *   at its own node for its leaf children, a thread that has written a row arrives at the parent (an atomicAdd on
+ *   counters behind a fence, as pn_bvh_tree's refit), and the arrival that completes a node writes its row.  Every row is
+ *   written once from the same operands in the same order, and every operation is an IEEE + - * / sqrt: two calls give
+ *   the same bits, which are those of tests/_winding_ref.py.  F = 1 has no internal node: row 0 is zero.
+ *   Work: counters [max(F - 1, 1)] int32 (zeroed by pn_bvh_moments itself).
+ * pn_winding_bvh: a Barnes-Hut walk (in the manner of Barill et al. 2018, dipole term only), one point per thread, 64
+ *   threads per workgroup, the traversal stack [PN_BVH_MAX_DEPTH][64] in LDS as pn_closest_point_bvh's; no scratch.
+ *   Visiting a reference: a leaf adds Omega(p, f) if f is valid.  An internal node j takes x = g_j - p, d2 = x . x; if
+ *   d2 > 0 and d2 >= beta2 r2_j (beta2 = the fp32 beta squared in fp64) it adds (N_j . x) / (d2 sqrt(d2)) and descends no
+ *   further; otherwise it visits its left child next and pushes the right one.  The walk starts at row 0 (F = 1: at the
+ *   single leaf), S takes the terms in visiting order - pre-order, left first, is part of the contract, the sum is not
+ *   associative - and it ends after 2 F visits at the latest (a tree has 2 F - 1 references), also over a buffer that is
+ *   no tree.  beta is finite and in [1, 1e6]: with beta >= 1 a point inside a node's box (d2 <= r2) does not take that
+ *   node's far field, short of equality at the farthest corner.
+ *   Unlike the tracer's and the distance walk's, this result DOES depend on the tree: it is an approximation, whose error
+ *   falls as beta^-2.  It promises the same bits on every call and every build of the same mesh (tree and moments are
+ *   deterministic), the exact sum's terms for beta so large that no node is far (1e6 on any mesh whose points lie within
+ *   1e6 of its size), and the error table of tests/test_winding_cpu.py, recorded in DESIGN.md 6n.
+ * Errors: PN_ERR_BAD_SHAPE (a negative count, V or F >= 2^31, F = 0 in pn_bvh_moments and pn_winding_bvh, beta outside
+ * [1, 1e6] or NaN), PN_ERR_NULL.  P = 0 launches nothing. */
+#define PN_WINDING_TILE 256
+#define PN_WINDING_FOUR_PI 12.566370614359172
+int pn_winding(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,
+               float* winding, void* stream);
+int pn_bvh_moments(int64_t F, int64_t V, const float* vertices, const int32_t* faces, const float* nodes, double* moments,
+                   int32_t* counters, void* stream);
+int pn_winding_bvh(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,
+                   const float* nodes, const double* moments, float beta, float* winding, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -35,6 +35,9 @@ Public surface (mirrors the reference's names):
     meshdist                      distances between surfaces: the closest point of a mesh to arbitrary points through the BVH,
                                   area-weighted surface samples, Chamfer / Hausdorff / F-score / normal consistency of two
                                   meshes and unsigned distance grids (HIP kernels)
+    winding                       generalized winding numbers of open or closed meshes: a robust inside test, signed
+                                  distance and its grids, and a watertight remesh of what a mesh encloses: winding_number,
+                                  inside, signed_distance, remesh (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -67,6 +70,8 @@ from . import meshops  # noqa
 from .meshops import mesh_components, filter_components, simplify_mesh  # noqa
 from . import meshdist  # noqa
 from .meshdist import closest_point, sample_surface, compare_meshes  # noqa
+from . import winding  # noqa
+from .winding import winding_number, signed_distance, remesh  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

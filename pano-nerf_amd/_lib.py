@@ -126,6 +126,9 @@ SIGNATURES = {
     "pn_face_areas": ("i", "llppp" + "p"),
     "pn_face_weights": ("i", "lppp" + "p"),
     "pn_sample_surface": ("i", "llll" + "ppp" + "ppp" + "p"),
+    "pn_winding": ("i", "lplplp" + "p" + "p"),
+    "pn_bvh_moments": ("i", "llpp" + "ppp" + "p"),
+    "pn_winding_bvh": ("i", "lplplp" + "pp" + "f" + "p" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

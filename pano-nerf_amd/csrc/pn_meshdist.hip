@@ -10,21 +10,19 @@
 // keeps (best, face) only; the kernel evaluates the winner once more for the closest point and its barycentrics, which
 // gives the same fp64 values as the evaluation that won.
 #include "pn_common.h"
+#include "pn_mesh64.h"
 #include "pn_tri.h"
 #include <math.h>
 
 namespace {
 
 using pn_tri::kDepth;
+using pn_mesh64::P3;
+using pn_mesh64::sub3;
+using pn_mesh64::dot3;
+using pn_mesh64::cross3;
+using pn_mesh64::load_tri;
 
-struct P3 {
-    double x, y, z;
-};
-__device__ __forceinline__ P3 sub3(const P3 a, const P3 b) { return P3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot3(const P3 a, const P3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ P3 cross3(const P3 u, const P3 w) {
-    return P3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
 // s + e t per axis: fl(s + fl(e t))
 __device__ __forceinline__ P3 along(const P3 s, const P3 e, double t) { return P3{s.x + e.x * t, s.y + e.y * t, s.z + e.z * t}; }
 __device__ __forceinline__ double dist2(const P3 p, const P3 q) {
@@ -103,22 +101,6 @@ __device__ __forceinline__ double point_tri(const P3 p, const P3 a, const P3 b, 
     u = vb * den, v = vc * den;
     q = along(along(a, ab, u), ac, v);
     return dist2(p, q);
-}
-
-// the corners of face f as fp64; false for a face that is never a candidate (an index outside [0, V), a coordinate that
-// is not finite: pn_bvh_boxes' rule for the empty box)
-__device__ __forceinline__ bool load_tri(int64_t f, int64_t V, const float* vertices, const int32_t* faces, P3& a, P3& b,
-                                         P3& c) {
-    const int64_t ia = faces[f * 3], ib = faces[f * 3 + 1], ic = faces[f * 3 + 2];
-    if (!(ia >= 0 && ia < V && ib >= 0 && ib < V && ic >= 0 && ic < V)) return false;
-    const float *pa = vertices + ia * 3, *pb = vertices + ib * 3, *pc = vertices + ic * 3;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ok = ok && isfinite(pa[k]) && isfinite(pb[k]) && isfinite(pc[k]);
-    a = P3{(double)pa[0], (double)pa[1], (double)pa[2]};
-    b = P3{(double)pb[0], (double)pb[1], (double)pb[2]};
-    c = P3{(double)pc[0], (double)pc[1], (double)pc[2]};
-    return ok;
 }
 
 struct Near {

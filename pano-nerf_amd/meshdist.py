@@ -26,9 +26,10 @@ accel=None) builds a MeshBVH for the call, accel=<a MeshBVH of this mesh> reuses
 faces.  The walk's result does not depend on the tree and is the brute-force result wherever every face passes the header's
 candidate rule, which the triangle boxes' padding provides for; tests/test_meshdist_cpu.py counts the exceptions (none).
 
-Out of scope: signed distance (it needs angle-weighted pseudo-normals and closed, consistently wound meshes, which culled
-TSDF meshes are not); point-cloud (vertex-only) targets; the k nearest faces; gradients; tuning the walk (its 24 KB LDS
-stack caps a compute unit at 6 waves, as it does for the tracer).
+Signed distance is ``winding.signed_distance``: the sign comes from the generalized winding number, which does not need the
+closed, consistently wound mesh that angle-weighted pseudo-normals would (culled TSDF meshes are neither).  Out of scope
+here: point-cloud (vertex-only) targets; the k nearest faces; gradients; tuning the walk (its 24 KB LDS stack caps a compute
+unit at 6 waves, as it does for the tracer).
 """
 import math
 
