@@ -1333,6 +1333,67 @@ int pn_bvh_moments(int64_t F, int64_t V, const float* vertices, const int32_t* f
 int pn_winding_bvh(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,
                    const float* nodes, const double* moments, float beta, float* winding, void* stream);
 
+/* ---- radiance volume: the field baked into a voxel volume and ray-marched with no network (pn_volume.hip) -------------
+ * data [nx, ny, nz, C] fp32 on pn_grid_points' vertex grid: vertex v = (i ny + j) nz + k at (x0 + i dx, ...), each axis
+ * >= 2 vertices, fewer than 2^31 vertices, lo finite and steps positive and finite.  C = 1 + 3 K + E: channel 0 is sigma;
+ * then K = (sh_degree + 1)^2 RGB triples (channel 1 + 3 k + c), real SH coefficients in the lighting section's order with
+ * the constants below (sh_degree 0, 1 or 2); then E <= PN_VOLUME_MAX_ATTR attribute channels.  A vertex is one
+ * contiguous run of C floats, so a trilinear tap reads 8 runs.
+ * Occupancy: a cell is the cube between 8 neighbouring vertices, cells are grouped in bricks of PN_VOLUME_BRICK^3 cells
+ * (partial bricks at the upper faces), nb_a = ceil((n_a - 1) / PN_VOLUME_BRICK) bricks per axis, brick
+ * (bi nby + bj) nbz + bk.  pn_volume_occupancy writes ONE BYTE per brick: 1 iff a vertex of the brick (i in
+ * [8 bi, min(8 bi + 8, nx - 1)], both ends included, likewise j, k) has sigma > 0, which is: iff a cell of the brick has a
+ * corner with sigma > 0.  A NaN is not > 0.  pn_volume_bricks is the byte count (< 0: a bad grid).
+ * Baking directions (volume.fibonacci_directions, fp64 on the host): for i = 0..D-1, y = 1 - (2 i + 1) / D,
+ * r = sqrt(1 - y y), phi = i PN_VOLUME_GOLDEN_ANGLE, direction (r cos phi, y, r sin phi).  The bake's default D = 4 K, the
+ * marcher's default step of half the smallest grid step, t_min = 1e-3 and the brick size are conventions, not measurements.
+ *
+ * pn_volume_march, rows r < R.  All arithmetic is fp64 on the fp32 inputs, separate operations in the written order
+ * (-ffp-contract=off), each output rounded to fp32 once; one launch, no atomics: two calls give the same bits.
+ * Lattice: len = sqrt((dx dx + dy dy) + dz dz) of the direction, dt = step / len, n = ceil((far - near) / dt) points,
+ *   t_k = near + (k + 0.5) dt for 0 <= k < n, computed from k.  A row with a non-finite origin, direction, near or far,
+ *   with len == 0, far <= near or n >= 2^31 writes 0 to every output and marches nothing.  The lattice does not depend on
+ *   the volume or on the jumps.
+ * Sample k: g_a = ((o_a + t_k d_a) - lo_a) / step_a per axis.  If g_a < 0 or g_a > n_a - 1 on any axis the sample adds
+ *   nothing.  Otherwise c_a = min(floor(g_a), n_a - 2), f_a = g_a - c_a, corner weights w = (wx wy) wz with
+ *   wx = 1 - f_x (low) or f_x (high), and trilinear(ch) = the sum of w v over the corners in the order i, j, k, low corner
+ *   first, starting from 0.  sigma = trilinear(0); if !(sigma > 0) (a NaN included) the sample adds nothing.
+ * Colour: Y_0..Y_{K-1} once per row at u = d / len (each component divided): PN_SH_C0, PN_SH_C1 {y, z, x},
+ *   PN_SH_C2 (x y), PN_SH_C2 (y z), PN_SH_C3 (3 (z z) - 1), PN_SH_C2 (x z), PN_SH_C4 (x x - y y).  Per sample and channel
+ *   s = sum_k Y_k trilinear(1 + 3 k + c) in k order from 0, colour = s > 0 ? s : 0.  Attributes are trilinear(1 + 3 K + e)
+ *   as stored (a composited normal is not re-normalised).
+ * Composite, ascending k from T = 1: alpha = 1 - exp(-sigma (dt len)), w = T alpha, rgb_c += w colour_c, attr_e += w a_e,
+ *   acc += w, wt += w t_k, T = T (1 - alpha); then stop if T < t_min (t_min = 0 never stops).
+ *   depth = min(max(q, near), far), q = wt / acc with a NaN quotient replaced by 0: k_composite_fwd's rule for fine_dep.
+ *   There is no background term.
+ * Jumps.  The coordinate g_a of sample k is a chain of correctly rounded operations on (k + 0.5) and so a monotone function
+ *   of k.  (1) A sample beyond a box face on axis a: if the ray does not move towards the box on that axis (d_a of the wrong
+ *   sign or 0) the march ends; otherwise k moves past kl, the largest proposal for which g_a(kl), evaluated by the sample
+ *   formula, is still beyond the same face.  (2) With an occupancy table, a sample whose cell lies in an unoccupied brick:
+ *   k moves past kl if the sample formula puts kl inside the box with its cell in the same brick.  Proposals come from the
+ *   exit plane (an axis with d_a == 0 proposes nothing: no division), floor((t_plane - near) / dt - 0.5), then one less,
+ *   then no jump.  By monotonicity every skipped sample is outside the box or in a cell of an unoccupied brick, whose
+ *   corners are all <= 0 or NaN, and adds nothing: the outputs are the same bits with and without the table.
+ * Outputs (null: not written): rgb [R, 3], depth [R], acc [R], attrs [R, E], and the diagnostic taps [R, 2] int32: the
+ *   samples whose trilinear sigma was evaluated, and of those the ones with sigma > 0 (which read the colour too).  With a
+ *   table the first count drops; the second does not change.
+ * Errors: PN_ERR_BAD_SHAPE (a bad grid, sh_degree outside 0..2, E outside 0..PN_VOLUME_MAX_ATTR, step or a grid step not
+ * positive and finite, t_min negative or not finite, R < 0), PN_ERR_NULL.  R = 0 launches nothing. */
+#define PN_VOLUME_BRICK 8
+#define PN_VOLUME_MAX_ATTR 8
+#define PN_VOLUME_GOLDEN_ANGLE 2.399963229728653
+#define PN_SH_C0 0.28209479177387814
+#define PN_SH_C1 0.48860251190291992
+#define PN_SH_C2 1.0925484305920792
+#define PN_SH_C3 0.31539156525252005
+#define PN_SH_C4 0.54627421529603959
+int64_t pn_volume_bricks(int nx, int ny, int nz);
+int pn_volume_occupancy(int nx, int ny, int nz, int channels, const float* data, uint8_t* occupancy, void* stream);
+int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float* data, const uint8_t* occupancy,
+                    float x0, float y0, float z0, float dx, float dy, float dz, const float* origins,
+                    const float* directions, const float* near, const float* far, float step, float t_min, float* rgb,
+                    float* depth, float* acc, float* attrs, int32_t* taps, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -38,6 +38,9 @@ Public surface (mirrors the reference's names):
     winding                       generalized winding numbers of open or closed meshes: a robust inside test, signed
                                   distance and its grids, and a watertight remesh of what a mesh encloses: winding_number,
                                   inside, signed_distance, remesh (HIP kernels)
+    volume                        the field baked into a radiance volume (density, SH radiance, albedo / normal attributes) and
+                                  marched with no network in the loop, with brick skipping: RadianceVolume, bake_volume,
+                                  march_rays, render_volume, render_volume_path, volume_probes (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -72,6 +75,8 @@ from . import meshdist  # noqa
 from .meshdist import closest_point, sample_surface, compare_meshes  # noqa
 from . import winding  # noqa
 from .winding import winding_number, signed_distance, remesh  # noqa
+from . import volume  # noqa
+from .volume import RadianceVolume, bake_volume, march_rays, render_volume, volume_probes  # noqa
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

@@ -129,6 +129,9 @@ SIGNATURES = {
     "pn_winding": ("i", "lplplp" + "p" + "p"),
     "pn_bvh_moments": ("i", "llpp" + "ppp" + "p"),
     "pn_winding_bvh": ("i", "lplplp" + "pp" + "f" + "p" + "p"),
+    "pn_volume_bricks": ("l", "iii"),
+    "pn_volume_occupancy": ("i", "iiii" + "pp" + "p"),
+    "pn_volume_march": ("i", "liiiii" + "pp" + "ffffff" + "pppp" + "ff" + "ppppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

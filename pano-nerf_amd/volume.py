@@ -1,0 +1,459 @@
+"""The field baked into a radiance volume, and that volume ray-marched with no network in the loop.
+
+Every other view of a trained model goes through the MLP.  This module exports the field as the asset NeRF toolchains use
+for previews, viewers and fast probes (PlenOctrees / "baked" NeRF style): one dense voxel volume of density, view-dependent
+radiance as real spherical harmonics, and optional attributes (albedo, normal), marched directly by ``pn_volume.hip`` with
+empty-space skipping over 8^3-cell bricks.  Everything runs on the HIP device under ``torch.no_grad()`` on the current
+stream; CPU tensors raise, there is no host fallback.
+
+    RadianceVolume(data, bounds, sh_degree, attributes)   data [nx, ny, nz, C] on geometry's vertex grid
+      .sigma / .coeff / .attributes             views: [nx, ny, nz], [nx, ny, nz, K, 3], name -> [nx, ny, nz, w]
+      .occupancy / .refresh()                   one byte per brick (pn_volume_occupancy), built lazily; refresh after edits
+      .save(path) / RadianceVolume.load(path, device)   volume.json + volume.bin, bit for bit
+    fibonacci_directions(D)                     the fp64 spherical Fibonacci set the bake evaluates the colour along
+    sh_basis(directions, sh_degree)             numpy fp64 [D, K] in lighting's order and constants
+    bake_volume(model, bounds, resolution, ...) density_grid pruned at sigma_min, SH fitted to query_field's rgb, attributes
+    march_rays(vol, origins, directions, near, far, ...)   dict of rgb [R, 3], depth [R, 1], acc [R, 1], attributes [R, w]
+    render_volume(vol, camera, c2w, ...)        dict of [1, C, H, W] images for any camera of cameras.py
+    render_volume_path(vol, camera, poses, ...) dict kind -> frames (or PNG / EXR files), as views.render_path
+    volume_probes(vol, positions, ...)          [P, 3, H, W] HDR probes with lighting.light_probes' pixel directions
+
+The contract of the marcher is stated in include/panonerf_hip.h, section "radiance volume", and argued in DESIGN.md 6o.
+Conventions, not measurements: D = 4 K baking directions, a marching step of half the smallest grid step, t_min = 1e-3 and
+bricks of 8 cells.  sigma_min = 0.01 / |box diagonal| is derived: pruning removes at most 0.01 of optical depth from any
+ray through the box.
+
+Out of scope: fp16 or compressed storage, sparse or hashed volumes, an fp32-arithmetic marcher, gradients or fine-tuning of
+the volume, cone-aware (mip) filtering, baking the surface / shading branch, and stereo baking.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .cameras import FisheyeCamera, PanoCamera, _c2w_stack, _camera
+from .geometry import _model_device, _placement, _resolution, _variance, density_grid, grid_points, query_field
+from .rays import CameraRig
+
+BRICK = 8          # PN_VOLUME_BRICK
+MAX_ATTR = 8       # PN_VOLUME_MAX_ATTR
+GOLDEN_ANGLE = 2.399963229728653  # PN_VOLUME_GOLDEN_ANGLE = pi (3 - sqrt 5)
+_SH_C = (0.28209479177387814, 0.48860251190291992, 1.0925484305920792, 0.31539156525252005, 0.54627421529603959)
+_BAKE_ATTRIBUTES = ("albedo", "normal")
+_CORE = ("rgb", "depth", "acc")
+_TAPS = "taps"  # march_rays' diagnostic output
+_PATH_KINDS = {"ldr": ("rgb", "ldr"), "hdr": ("rgb", None), "depth": ("depth", "depth"), "albedo": ("albedo", "albedo"),
+               "normal": ("normal", "normal")}
+_PATH_GROUP_RAYS = 1 << 22  # rays marched per group of frames in render_volume_path
+
+
+def fibonacci_directions(count):
+    """fp64 [D, 3] unit directions of the spherical Fibonacci set: y_i = 1 - (2 i + 1) / D, r = sqrt(1 - y^2),
+    phi = i GOLDEN_ANGLE, (r cos phi, y, r sin phi)."""
+    D = int(count)
+    if D < 1:
+        raise ValueError(f"a direction set needs at least one direction; got {count!r}")
+    i = np.arange(D, dtype=np.float64)
+    y = 1.0 - (2.0 * i + 1.0) / D
+    r = np.sqrt(1.0 - y * y)
+    phi = i * GOLDEN_ANGLE
+    return np.stack([r * np.cos(phi), y, r * np.sin(phi)], 1)
+
+
+def sh_basis(directions, sh_degree):
+    """numpy fp64 [.., K] real SH basis, K = (sh_degree + 1)^2, at directions [.., 3]: the first K entries of
+    lighting._sh_basis, with the header's constants, written as the marcher evaluates them."""
+    n = np.asarray(directions, dtype=np.float64)
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    c0, c1, c2, c3, c4 = _SH_C
+    cols = [np.full_like(x, c0), c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z), c3 * (3.0 * (z * z) - 1.0),
+            c2 * (x * z), c4 * (x * x - y * y)]
+    return np.stack(cols[:_sh_count(sh_degree)], -1)
+
+
+def _sh_count(sh_degree):
+    if sh_degree not in (0, 1, 2) or isinstance(sh_degree, bool):
+        raise ValueError(f"sh_degree must be 0, 1 or 2; got {sh_degree!r}")
+    return (int(sh_degree) + 1) ** 2
+
+
+def _attributes(attributes):
+    """((name, width), ...) of names (width 3) or (name, width) pairs"""
+    out = []
+    for a in attributes:
+        name, width = (a, 3) if isinstance(a, str) else (a[0], int(a[1]))
+        if not isinstance(name, str) or name in _CORE or width < 1 or name in [n for n, _ in out]:
+            raise ValueError(f"attributes must be distinct names other than {_CORE}, each with a positive width; got {a!r}")
+        out.append((name, width))
+    if sum(w for _, w in out) > MAX_ATTR:
+        raise ValueError(f"a volume carries at most {MAX_ATTR} attribute channels; got {out}")
+    return tuple(out)
+
+
+def _bounds(bounds):
+    b = tuple(tuple(float(v) for v in c) for c in bounds)
+    if len(b) != 2 or len(b[0]) != 3 or len(b[1]) != 3:
+        raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)); got {bounds!r}")
+    return b
+
+
+def _grid(bounds, res):
+    lo, step = _placement(bounds, res)
+    if not all(math.isfinite(s) and s > 0.0 for s in step) or not all(math.isfinite(v) for v in lo):
+        raise ValueError(f"bounds must be finite with x0 < x1, y0 < y1, z0 < z1; got {bounds!r}")
+    return lo, step
+
+
+# ------------------------------------------------------------------------------------------------------------ files
+def write_volume_files(path, data, bounds, sh_degree, attributes=()):
+    """Write a host array data [nx, ny, nz, C] as path/volume.json + path/volume.bin (raw little-endian fp32)."""
+    a = np.asarray(data)
+    attrs = _attributes(attributes)
+    if a.ndim != 4 or a.dtype != np.float32 or a.shape[3] != 1 + 3 * _sh_count(sh_degree) + sum(w for _, w in attrs):
+        raise ValueError(f"data must be fp32 [nx, ny, nz, 1 + 3 K + E]; got {a.dtype} {a.shape}")
+    res = _resolution(a.shape[:3])
+    b = _bounds(bounds)
+    lo, step = _grid(b, res)
+    os.makedirs(path, exist_ok=True)
+    meta = dict(format="pano_nerf_amd.radiance_volume", version=1, bounds=[list(c) for c in b], resolution=list(res),
+                sh_degree=int(sh_degree), attributes=[[n, w] for n, w in attrs], channels=int(a.shape[3]), lo=list(lo),
+                step=list(step), dtype="<f4", order="[nx, ny, nz, C], C fastest")
+    with open(os.path.join(path, "volume.json"), "w") as fh:
+        json.dump(meta, fh, indent=1)
+    with open(os.path.join(path, "volume.bin"), "wb") as fh:
+        fh.write(np.ascontiguousarray(a, dtype="<f4").tobytes())
+
+
+def read_volume_files(path):
+    """-> (data fp32 [nx, ny, nz, C] host array, bounds, sh_degree, attributes) of what write_volume_files wrote"""
+    with open(os.path.join(path, "volume.json")) as fh:
+        meta = json.load(fh)
+    if meta.get("format") != "pano_nerf_amd.radiance_volume" or meta.get("version") != 1:
+        raise ValueError(f"{path}: not a radiance volume (format {meta.get('format')!r}, version {meta.get('version')!r})")
+    res = _resolution(meta["resolution"])
+    attrs = _attributes([tuple(a) for a in meta["attributes"]])
+    C = 1 + 3 * _sh_count(meta["sh_degree"]) + sum(w for _, w in attrs)
+    raw = np.fromfile(os.path.join(path, "volume.bin"), dtype="<f4")
+    if raw.size != res[0] * res[1] * res[2] * C:
+        raise ValueError(f"{path}: volume.bin holds {raw.size} floats, the header asks for {res} x {C}")
+    return raw.astype(np.float32, copy=False).reshape(*res, C), _bounds(meta["bounds"]), int(meta["sh_degree"]), attrs
+
+
+# ----------------------------------------------------------------------------------------------------------- volume
+class RadianceVolume:
+    """One packed fp32 tensor data [nx, ny, nz, C] on the vertex grid of geometry.density_grid (bounds are the inclusive
+    corner vertices, vertex (i ny + j) nz + k): channel 0 sigma, then K = (sh_degree + 1)^2 RGB coefficient triples in
+    lighting's SH order, then the attribute channels.  `attributes`: names (width 3) or (name, width) pairs, e.g.
+    (("albedo", 3), ("normal", 3)).  The tensor is held, not copied: edit it in place and call refresh()."""
+
+    def __init__(self, data, bounds, sh_degree, attributes=()):
+        K = _sh_count(sh_degree)
+        self.sh_degree = int(sh_degree)
+        self._attrs = _attributes(attributes)
+        if not isinstance(data, torch.Tensor) or data.dim() != 4:
+            raise ValueError(f"data must be an [nx, ny, nz, C] tensor; got {getattr(data, 'shape', type(data))}")
+        if data.device.type != "cuda":
+            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the data is on %s); there is no CPU "
+                               "fallback" % data.device)
+        C = 1 + 3 * K + sum(w for _, w in self._attrs)
+        if data.shape[3] != C:
+            raise ValueError(f"data has {data.shape[3]} channels; sh_degree {sh_degree} with attributes {self._attrs} "
+                             f"takes 1 + 3 K + E = {C}")
+        if data.dtype != torch.float32 or not data.is_contiguous():
+            raise ValueError("data must be a contiguous fp32 tensor (it is held and read in place)")
+        self.resolution = _resolution(tuple(int(s) for s in data.shape[:3]))
+        self.bounds = _bounds(bounds)
+        self.lo, self.step = _grid(self.bounds, self.resolution)
+        self.data = data.detach()
+        self.device = data.device
+        self.attribute_names = tuple(n for n, _ in self._attrs)
+        self._occ = None
+
+    @property
+    def channels(self):
+        return int(self.data.shape[3])
+
+    @property
+    def sigma(self):
+        return self.data[..., 0]
+
+    @property
+    def coeff(self):
+        K = _sh_count(self.sh_degree)
+        return self.data[..., 1:1 + 3 * K].unflatten(-1, (K, 3))
+
+    @property
+    def attributes(self):
+        out, first = {}, 1 + 3 * _sh_count(self.sh_degree)
+        for name, w in self._attrs:
+            out[name] = self.data[..., first:first + w]
+            first += w
+        return out
+
+    @property
+    def occupancy(self):
+        """uint8 [nbx, nby, nbz], one byte per brick of 8^3 cells: 1 iff a vertex of the brick has sigma > 0"""
+        if self._occ is None:
+            self.refresh()
+        return self._occ
+
+    def refresh(self):
+        """Rebuild the occupancy from data (one launch of pn_volume_occupancy); call it after editing data.  Returns self."""
+        nb = tuple((n + BRICK - 2) // BRICK for n in self.resolution)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            occ = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            _lib.call("pn_volume_occupancy", *self.resolution, self.channels, self.data.data_ptr(), occ.data_ptr(),
+                      _lib.stream(self.device))
+        self._occ = occ
+        return self
+
+    def save(self, path):
+        """path/volume.json (bounds, resolution, sh_degree, attribute names and widths; lo / step for information) and
+        path/volume.bin (the raw little-endian fp32 data)"""
+        write_volume_files(path, self.data.cpu().numpy(), self.bounds, self.sh_degree, self._attrs)
+
+    @classmethod
+    def load(cls, path, device=None):
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (device=%s); there is no CPU fallback" % dev)
+        data, bounds, sh_degree, attrs = read_volume_files(path)
+        return cls(torch.from_numpy(np.ascontiguousarray(data)).to(dev), bounds, sh_degree, attrs)
+
+
+# ------------------------------------------------------------------------------------------------------------- bake
+def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_min=None, attributes=("albedo", "normal"),
+                variance=None, chunk_rows=None):
+    """Bake `model` into a RadianceVolume on the grid of density_grid(model, bounds, resolution, variance).
+
+    sigma is density_grid's, bit for bit, where it is > sigma_min and exactly 0 elsewhere (pruned; every channel of a pruned
+    vertex is 0).  sigma_min None is 0.01 / |box diagonal|: trilinear interpolation is a convex combination, so pruning
+    lowers the interpolated sigma by at most sigma_min anywhere, and no chord of the box is longer than its diagonal.
+    sigma_min = 0 keeps everything positive.  Only the surviving vertices are evaluated further (one host synchronisation
+    for their count): query_field(..., viewdirs=d_i, outputs=("rgb",)) along each of D directions at the grid's variance,
+    and the coefficients are the least-squares fit P @ rgb, P = pinv(Y [D, K]) in fp64 on the host, applied in fp64 in
+    direction order and rounded once.  directions: [D, 3] (numpy or tensor), None = fibonacci_directions(4 K), a convention;
+    they are rounded to fp32 first, and Y is evaluated at what the field sees.  attributes: "albedo" (PanoMipNeRF only)
+    and / or "normal", query_field's at the same rows, bit for bit."""
+    K = _sh_count(sh_degree)
+    attributes = tuple(attributes)
+    bad = [a for a in attributes if a not in _BAKE_ATTRIBUTES]
+    if bad or len(set(attributes)) != len(attributes):
+        raise ValueError(f"unknown attributes {bad or attributes}; choose from {_BAKE_ATTRIBUTES}")
+    if "albedo" in attributes and model._NC != 5:
+        raise ValueError(f"albedo needs a 5-channel density head (PanoMipNeRF); {type(model).__name__} has {model._NC}")
+    res = _resolution(resolution)
+    b = _bounds(bounds)
+    _, step = _grid(b, res)
+    if isinstance(variance, torch.Tensor):
+        raise ValueError("bake_volume takes a scalar variance")
+    variance = float(_variance(model, variance, step))
+    if sigma_min is None:
+        sigma_min = 0.01 / math.sqrt(sum((h - l) ** 2 for l, h in zip(*b)))
+    sigma_min = float(sigma_min)
+    if not sigma_min >= 0.0:
+        raise ValueError(f"sigma_min must be >= 0; got {sigma_min!r}")
+    if directions is None:
+        dirs = fibonacci_directions(4 * K)
+    else:
+        dirs = directions.detach().cpu().numpy() if isinstance(directions, torch.Tensor) else np.asarray(directions)
+        if dirs.ndim != 2 or dirs.shape[1] != 3 or dirs.shape[0] < K:
+            raise ValueError(f"directions must be [D, 3] with D >= K = {K}; got {dirs.shape}")
+    dirs32 = np.ascontiguousarray(dirs, dtype=np.float32)
+    P = np.linalg.pinv(sh_basis(dirs32.astype(np.float64), sh_degree))  # [K, D]
+    dev = _model_device(model)
+    E = 3 * len(attributes)
+    N = res[0] * res[1] * res[2]
+    with torch.no_grad(), torch.cuda.device(dev):
+        sigma = density_grid(model, b, res, variance, chunk_rows).view(-1)
+        data = torch.zeros(N, 1 + 3 * K + E, dtype=torch.float32, device=dev)
+        idx = torch.nonzero(sigma > sigma_min).reshape(-1)  # the one host sync: the survivors size everything below
+        M = int(idx.shape[0])
+        if M:
+            data[idx, 0] = sigma[idx]
+            pts = grid_points(b, res, 0.0, dev)[0][idx]
+            dirs_t = torch.from_numpy(dirs32).to(dev)
+            P_t = torch.from_numpy(P).to(dev)
+            coef = torch.zeros(M, K, 3, dtype=torch.float64, device=dev)
+            for i in range(dirs32.shape[0]):
+                rgb = query_field(model, pts, variance, viewdirs=dirs_t[i], outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
+                coef += P_t[:, i].view(1, K, 1) * rgb.to(torch.float64).view(M, 1, 3)
+            data[idx, 1:1 + 3 * K] = coef.to(torch.float32).view(M, 3 * K)
+            if attributes:
+                q = query_field(model, pts, variance, outputs=attributes, chunk_rows=chunk_rows)
+                for j, name in enumerate(attributes):
+                    data[idx, 1 + 3 * K + 3 * j:4 + 3 * K + 3 * j] = q[name]
+    return RadianceVolume(data.view(*res, -1), b, sh_degree, tuple((a, 3) for a in attributes))
+
+
+# ------------------------------------------------------------------------------------------------------------ march
+def default_step(vol):
+    """half the smallest grid step, as the fp32 value the kernel takes: a convention"""
+    return float(np.float32(0.5 * min(vol.step)))
+
+
+def _rows(t, R, width, what, dev):
+    if isinstance(t, torch.Tensor):
+        if t.device.type != "cuda":
+            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (%s is on %s); there is no CPU fallback"
+                               % (what, t.device))
+        if t.device != dev:
+            raise ValueError(f"{what} is on {t.device} but the volume on {dev}")
+        if t.numel() != R * width:
+            raise ValueError(f"{what} must hold {R} rows of {width}; got {tuple(t.shape)}")
+        return t.detach().to(torch.float32).reshape(R, width).contiguous()
+    if width != 1:
+        raise ValueError(f"{what} must be an [R, {width}] tensor; got {type(t).__name__}")
+    return torch.full((R, 1), float(t), dtype=torch.float32, device=dev)
+
+
+def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=True, outputs=("rgb", "depth", "acc")):
+    """March rows of rays through `vol` in one launch of pn_volume_march: dict of rgb [R, 3], depth [R, 1], acc [R, 1] and
+    one [R, w] per requested attribute name, fp32 on the volume's device.
+
+    origins, directions: [R, 3] device tensors (directions need not be unit: t runs along them as given, as in Rays); near,
+    far: floats or [R] / [R, 1] tensors.  step: the world distance between samples, None = half the smallest grid step (a
+    convention); t_min: stop once the transmittance falls below it (0 never stops).  skip=True jumps over unoccupied
+    bricks and gives the same bits as skip=False.  depth is the renderer's expected distance by its own rule
+    (clamp(wt / acc, near, far), 0 / 0 -> 0), so it feeds warp_view, fusion and relight unchanged; there is no background
+    term: callers have acc.  A diagnostic besides: "taps" [R, 2] int32, the samples whose sigma was interpolated and, of
+    those, the ones that read the colour too (what tools/profile_volume.py counts the gathered bytes with)."""
+    if not isinstance(vol, RadianceVolume):
+        raise ValueError(f"vol must be a RadianceVolume; got {type(vol).__name__}")
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in _CORE + vol.attribute_names + (_TAPS,)]
+    if bad or not outputs:
+        raise ValueError(f"outputs must be a non-empty subset of {_CORE + vol.attribute_names}; got {outputs!r}")
+    for t, what in ((origins, "origins"), (directions, "directions")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
+    dev = vol.device
+    R = int(origins.shape[0])
+    step = default_step(vol) if step is None else float(np.float32(step))
+    t_min = float(np.float32(t_min))
+    if not (step > 0.0 and math.isfinite(step)) or not (t_min >= 0.0 and math.isfinite(t_min)):
+        raise ValueError(f"step must be positive and finite and t_min >= 0; got {step!r}, {t_min!r}")
+    o = _rows(origins, R, 3, "origins", dev)
+    d = _rows(directions, R, 3, "directions", dev)
+    tn, tf = _rows(near, R, 1, "near", dev), _rows(far, R, 1, "far", dev)
+    E = vol.channels - 1 - 3 * _sh_count(vol.sh_degree)
+    want_attr = any(k in vol.attribute_names for k in outputs)
+    with torch.no_grad(), torch.cuda.device(dev):
+        new = lambda w: torch.empty(R, w, dtype=torch.float32, device=dev)
+        rgb = new(3) if "rgb" in outputs else None
+        depth = new(1) if "depth" in outputs else None
+        acc = new(1) if "acc" in outputs else None
+        attrs = new(E) if want_attr else None
+        taps = torch.empty(R, 2, dtype=torch.int32, device=dev) if _TAPS in outputs else None
+        occ = vol.occupancy if skip else None
+        _lib.call("pn_volume_march", R, *vol.resolution, vol.sh_degree, E, vol.data.data_ptr(), _lib.ptr(occ), *vol.lo,
+                  *vol.step, o.data_ptr(), d.data_ptr(), tn.data_ptr(), tf.data_ptr(), step, t_min,
+                  *[_lib.ptr(x) if R else None for x in (rgb, depth, acc, attrs, taps)], _lib.stream(dev))
+    got = dict(rgb=rgb, depth=depth, acc=acc, taps=taps)
+    first = 0
+    for name, w in vol._attrs:
+        if attrs is not None:
+            got[name] = attrs[:, first:first + w]
+        first += w
+    return {k: got[k] for k in outputs}
+
+
+# --------------------------------------------------------------------------------------------------------- wrappers
+def _march_rig(vol, rig, first, count, near, far, step, t_min, skip, outputs):
+    """march_rays over rows [first, first + count) of a rig; a fisheye writes 0 outside its image circle"""
+    idx = torch.arange(first, first + count, dtype=torch.int64, device=vol.device)
+    rays, _ = rig.sample(idx, near, far)
+    got = march_rays(vol, rays.origins, rays.directions, rays.near, rays.far, step, t_min, skip, outputs)
+    if isinstance(rig.camera, FisheyeCamera):
+        seen = rays.lossmult > 0
+        got = {k: torch.where(seen, v, 0.0) for k, v in got.items()}
+    return got
+
+
+def render_volume(vol, camera, c2w, outputs=("rgb", "depth"), near=0.0, far=10.0, step=None, t_min=1e-3, skip=True):
+    """One view of the volume -> dict of [1, C, H, W] fp32 tensors keyed as `outputs` ("rgb", "depth", "acc" and the volume's
+    attribute names): march_rays on the rays CameraRig.sample gives the camera (what render_view renders), for a panorama,
+    pinhole, cube-map, fisheye (0 outside the image circle) or stereo-panorama camera."""
+    camera = _camera(camera)
+    H, W = camera.h, camera.w
+    with torch.no_grad(), torch.cuda.device(vol.device):
+        rig = CameraRig(camera, _c2w_stack(c2w, single=True), vol.device)
+        got = _march_rig(vol, rig, 0, H * W, near, far, step, t_min, skip, tuple(outputs))
+    return {k: v.reshape(1, H, W, -1).permute(0, 3, 1, 2) for k, v in got.items()}
+
+
+def render_volume_path(vol, camera, poses, kinds=("ldr", "depth"), near=0.0, far=10.0, step=None, t_min=1e-3, skip=True,
+                       exposure=0.0, out_dir=None):
+    """March every pose of poses ([n, 4, 4] or [n, 3, 4] c2ws) and turn the outputs into frames, as views.render_path does:
+    dict kind -> uint8 [n, H, W, 3] device tensor, each frame to_frame of render_volume's output (ldr <- rgb, depth <- depth
+    with near / far, albedo and normal <- the volume's attributes of those names); "hdr" is rgb itself as fp32
+    [n, H, W, 3].  Rays are indexed over (frame, pixel), one march_rays call per group of frames.  With out_dir, frames go
+    to out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr) and the returned dict is empty."""
+    from . import io_exr
+    from .views import to_frame
+    camera = _camera(camera)
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in _PATH_KINDS or _PATH_KINDS[k][0] not in _CORE + vol.attribute_names]
+    if bad or not kinds:
+        have = [k for k, v in _PATH_KINDS.items() if v[0] in _CORE + vol.attribute_names]
+        raise ValueError(f"kinds must be a non-empty subset of {have} for this volume; got {kinds!r}")
+    outputs = tuple(dict.fromkeys(_PATH_KINDS[k][0] for k in kinds))
+    c2ws = _c2w_stack(poses)
+    n, H, W = c2ws.shape[0], camera.h, camera.w
+    HW = H * W
+    group = max(1, min(n, _PATH_GROUP_RAYS // HW))
+    dev = vol.device
+    frames = {}
+    if out_dir is None:
+        frames = {k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev) for k in kinds}
+    else:
+        for k in kinds:
+            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    with torch.no_grad(), torch.cuda.device(dev):
+        rig = CameraRig(camera, c2ws, dev)
+        for g0 in range(0, n, group):
+            nf = min(group, n - g0)
+            got = _march_rig(vol, rig, g0 * HW, nf * HW, near, far, step, t_min, skip, outputs)
+            for f in range(nf):
+                i = g0 + f
+                for k in kinds:
+                    name, kind = _PATH_KINDS[k]
+                    src = got[name][f * HW:(f + 1) * HW].view(H, W, -1)
+                    if kind is None:
+                        frame = src
+                    else:
+                        frame = to_frame(src[None].permute(0, 3, 1, 2), kind, near, far, exposure if kind == "ldr" else 0.0)
+                    if out_dir is None:
+                        frames[k][i].copy_(frame)
+                    elif k == "hdr":
+                        io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
+                    else:
+                        io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
+    return frames
+
+
+def volume_probes(vol, positions, height=32, width=64, near=0.0, far=10.0, step=None, t_min=1e-3, skip=True):
+    """HDR radiance [P, 3, H, W] seen from each of positions [P, 3]: the volume marched along the pixel directions of
+    lighting.light_probes (an identity-rotation panorama camera at the position), all probes in one march_rays call.
+    lighting.sh_project, irradiance, ibl.bake_ibl and emitters take the result as they take light_probes'."""
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
+        raise ValueError(f"positions must be a [P, 3] tensor; got {getattr(positions, 'shape', type(positions))}")
+    if positions.device.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the positions are on %s); there is no CPU "
+                           "fallback" % positions.device)
+    H, W = int(height), int(width)
+    if H < 2 or W < 2:
+        raise ValueError(f"a probe needs height and width >= 2; got {height} x {width}")
+    dev = vol.device
+    P = int(positions.shape[0])
+    with torch.no_grad(), torch.cuda.device(dev):
+        c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
+        c2ws[:, :3, 3] = positions.detach().to(torch.float32)
+        if P == 0:
+            return torch.empty(0, 3, H, W, dtype=torch.float32, device=dev)
+        rig = CameraRig(PanoCamera(H, W), c2ws, dev)
+        rgb = _march_rig(vol, rig, 0, P * H * W, near, far, step, t_min, skip, ("rgb",))["rgb"]
+    return rgb.view(P, H, W, 3).permute(0, 3, 1, 2)
