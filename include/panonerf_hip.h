@@ -1394,6 +1394,49 @@ int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, con
                     const float* directions, const float* near, const float* far, float step, float t_min, float* rgb,
                     float* depth, float* acc, float* attrs, int32_t* taps, void* stream);
 
+/* ---- sparse radiance volume: a brick table and a pool of the present bricks, fp32 or fp16 (pn_volume.hip) -------------
+ * The same volume as above with the unoccupied bricks left out.  Bricks and their linear index are pn_volume_occupancy's:
+ * nb_a = ceil((n_a - 1) / PN_VOLUME_BRICK), brick (bi nby + bj) nbz + bk.  A brick is PRESENT iff pn_volume_occupancy
+ * says 1; its vertex range includes the shared far faces, so a positive vertex on a shared face makes every brick that
+ * shares it present.
+ * table int32 [nbx, nby, nbz]: the brick's slot in the pool, or -1.  Slots are 0 .. B - 1 in ascending brick index (an
+ *   exclusive prefix sum of the occupancy), so the layout never depends on a schedule.
+ * pool [B, 9, 9, 9, C], C fastest, fp32 or fp16 (`half` != 0): slot s, local vertex (li, lj, lk), 0 <= l <= 8, holds the
+ *   global vertex (8 bi + li, 8 bj + lj, 8 bk + lk); local vertices past the grid's last vertex (partial bricks) hold 0.
+ *   Value index (s 729 + (li 9 + lj) 9 + lk) C + ch, 64-bit; B 729 C < 2^40.
+ * Consequences.  The 8 corners of cell c lie in ONE brick (c >> 3 per axis, local c & 7 and that + 1), so a trilinear tap
+ *   is one table read and one base address.  Vertices on shared faces are stored once per present brick that holds them
+ *   (729 / 512 = 1.42 x per brick); pn_volume_pack writes every copy from the same source value, so the copies agree.
+ * fp16: each fp32 value is rounded to nearest even to binary16, subnormal results and fp32 subnormal inputs as IEEE 754
+ *   says (numpy's astype(float16)); values of magnitude >= 65520 become infinities (volume.py refuses them).  Readers widen
+ *   fp16 -> fp32 -> fp64 exactly.
+ * pn_volume_pack writes the pool from `table` and ONE source: data [N, C] (the dense tensor), or rows [M, C] with
+ *   vertex_row int32 [N] (the row of each vertex; an entry outside 0 .. M - 1, by convention -1, means every channel 0);
+ *   the other source's pointers are null.  One workgroup per brick, absent ones leave at once; the lanes stride over the
+ *   brick's 729 C values, so stores are contiguous; no atomics.  B = 0 launches nothing.
+ * pn_volume_unpack writes data [N, C] fp32 from table and pool, one thread per vertex: the vertex is read from the present
+ *   brick of LOWEST index that holds it (up to 8 candidates); a vertex in no present brick gets 0 in every channel.  A
+ *   gather: no write race.  Both kernels treat a table entry outside 0 .. B - 1 as absent.
+ * pn_volume_march_sparse is pn_volume_march, term for term, on the stored values: the same kernel template reads the
+ *   corners through the table.  A sample whose cell lies in an absent brick: with skip != 0 the brick jump of (2) above,
+ *   exactly as pn_volume_march takes it for an unoccupied brick; with skip == 0 it counts as one sigma tap of value 0
+ *   (taps[.., 0] goes up, nothing is read, the next sample is k + 1).  The outputs are the bits pn_volume_march gives on
+ *   the dense expansion (pn_volume_unpack's output): the corners of an absent brick are <= 0 or NaN in the source and 0
+ *   in the expansion, so sigma > 0 fails either way.  With fp32 storage taps are those of pn_volume_march too (with the
+ *   expansion's occupancy for skip != 0, without a table for skip == 0); with fp16 a brick whose positive sigmas all
+ *   round to 0 stays present, and taps[.., 0] may exceed the expansion's.  The table is trusted as data is: every entry is
+ *   -1 or a slot of the pool (volume.py checks it once, when the volume is made); pool may be null if none is present.
+ * Errors: as pn_volume_march; pack / unpack: PN_ERR_BAD_SHAPE (a bad grid, channels < 1 or > 65536, B < 0, B above the
+ *   brick count or B 729 C >= 2^40, M < 0, both sources given), PN_ERR_NULL (table, no source, the output, the pool when B > 0). */
+int pn_volume_pack(int nx, int ny, int nz, int channels, const int32_t* table, int64_t B, const float* data,
+                   const float* rows, int64_t M, const int32_t* vertex_row, int half, void* pool, void* stream);
+int pn_volume_unpack(int nx, int ny, int nz, int channels, const int32_t* table, int64_t B, const void* pool, int half,
+                     float* data, void* stream);
+int pn_volume_march_sparse(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const int32_t* table, const void* pool,
+                           int half, int skip, float x0, float y0, float z0, float dx, float dy, float dz,
+                           const float* origins, const float* directions, const float* near, const float* far, float step,
+                           float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream);
+
 /* ---- launch timing (bench.py roofline leg; off by default) ------------------------------------
  * pn_prof_enable(on): bit 0 switches the timing on or off; while on, every GEMM / chain launch is bracketed by HIP
  * events on its own stream (the other bits are ignored: the ablation switches of the tools/ micro-benchmarks exist only

@@ -40,7 +40,9 @@ Public surface (mirrors the reference's names):
                                   inside, signed_distance, remesh (HIP kernels)
     volume                        the field baked into a radiance volume (density, SH radiance, albedo / normal attributes) and
                                   marched with no network in the loop, with brick skipping: RadianceVolume, bake_volume,
-                                  march_rays, render_volume, render_volume_path, volume_probes (HIP kernels)
+                                  march_rays, render_volume, render_volume_path, volume_probes; and its sparse form, a brick
+                                  table and a pool of the occupied bricks in fp32 or fp16, packed from a dense volume or
+                                  baked directly and marched in place: SparseRadianceVolume, load_volume (HIP kernels)
     data, PanoScene               scene folders: transforms_all.json, train / held-out split, pose conversion and the EXR
                                   materials ingested on the device (datasets/pano_datasets.py:49-131; HIP kernel)
     load_config                   the flat dotted-key hyper-parameter dict of configs/config.py (yaml + KEY VAL overrides)
@@ -76,7 +78,8 @@ from .meshdist import closest_point, sample_surface, compare_meshes  # noqa
 from . import winding  # noqa
 from .winding import winding_number, signed_distance, remesh  # noqa
 from . import volume  # noqa
-from .volume import RadianceVolume, bake_volume, march_rays, render_volume, volume_probes  # noqa
+from .volume import (RadianceVolume, SparseRadianceVolume, bake_volume, load_volume, march_rays, render_volume,  # noqa
+                     volume_probes)
 from . import data  # noqa
 from .data import PanoScene  # noqa
 from .config import load_config  # noqa

@@ -132,6 +132,9 @@ SIGNATURES = {
     "pn_volume_bricks": ("l", "iii"),
     "pn_volume_occupancy": ("i", "iiii" + "pp" + "p"),
     "pn_volume_march": ("i", "liiiii" + "pp" + "ffffff" + "pppp" + "ff" + "ppppp" + "p"),
+    "pn_volume_pack": ("i", "iiii" + "pl" + "pplp" + "ip" + "p"),
+    "pn_volume_unpack": ("i", "iiii" + "pl" + "pi" + "p" + "p"),
+    "pn_volume_march_sparse": ("i", "liiiii" + "pp" + "ii" + "ffffff" + "pppp" + "ff" + "ppppp" + "p"),
     "pn_mfma_probe": ("i", "piip"),
     "pn_prof_enable": ("i", "i"),
     "pn_prof_read": ("i", "ippp"),

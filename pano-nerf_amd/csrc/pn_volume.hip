@@ -15,6 +15,11 @@
 // skipped point kl from the exit plane and then EVALUATES point kl with the sampling formula itself: if k and kl are both in
 // the brick (or both beyond the same box face), so is every point between them.  A proposal that fails falls back to kl - 1,
 // then to no jump at all.
+//
+// The marching loop exists once, as a template over a storage policy: the dense fp32 tensor with its occupancy bytes, or the
+// brick pool (fp32 or fp16) behind its table, section "sparse radiance volume" of the header.  A policy answers two
+// questions, "is this cell's brick present" and "corner q, channel ch, as fp64", and carries nothing across samples.
+// k_volume_pack / k_volume_unpack move a volume between the two layouts.
 #include "pn_common.h"
 
 namespace {
@@ -23,6 +28,10 @@ constexpr int kThreads = 64;
 constexpr int kBrick = PN_VOLUME_BRICK;
 constexpr int kShift = 3;  // log2(kBrick)
 static_assert(kBrick == 1 << kShift, "brick size");
+
+constexpr int kEdge = kBrick + 1;                  // vertices along a brick's edge, the shared far face included
+constexpr int kBrickVerts = kEdge * kEdge * kEdge;  // 729
+constexpr int kCopyThreads = 256;                   // pack and unpack
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
@@ -46,13 +55,127 @@ __global__ __launch_bounds__(kThreads) void k_volume_occupancy(int nx, int ny, i
     if (threadIdx.x == 0) occ[brick] = hit ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------------ pack / unpack
+// one workgroup per brick (an absent one leaves at once); the lanes stride over the brick's 729 C values: contiguous stores
+template <typename T>
+__global__ __launch_bounds__(kCopyThreads) void k_volume_pack(int nx, int ny, int nz, int C, const int32_t* __restrict__ table,
+                                                              int64_t B, const float* __restrict__ data,
+                                                              const float* __restrict__ rows, int64_t M,
+                                                              const int32_t* __restrict__ vertex_row, int nby, int nbz,
+                                                              T* __restrict__ pool) {
+    const int64_t brick = blockIdx.x;
+    const int64_t slot = table[brick];
+    if (slot < 0 || slot >= B) return;
+    const int bk = (int)(brick % nbz), bj = (int)((brick / nbz) % nby), bi = (int)(brick / ((int64_t)nbz * nby));
+    const int total = kBrickVerts * C;
+    T* out = pool + slot * total;
+    for (int t = threadIdx.x; t < total; t += kCopyThreads) {
+        const int lv = t / C, ch = t - lv * C;
+        const int i = bi * kBrick + lv / (kEdge * kEdge), j = bj * kBrick + (lv / kEdge) % kEdge, k = bk * kBrick + lv % kEdge;
+        float v = 0.f;  // a local vertex past the grid's last vertex
+        if (i < nx && j < ny && k < nz) {
+            const int64_t vtx = ((int64_t)i * ny + j) * nz + k;
+            if (data) {
+                v = data[vtx * C + ch];
+            } else {
+                const int64_t row = vertex_row[vtx];
+                if (row >= 0 && row < M) v = rows[row * C + ch];
+            }
+        }
+        out[t] = (T)v;  // fp16: round to nearest even
+    }
+}
+
+// one thread per dense vertex: read from the present brick of lowest index that holds it, 0 if none does
+template <typename T>
+__global__ __launch_bounds__(kCopyThreads) void k_volume_unpack(int nx, int ny, int nz, int C, const int32_t* __restrict__ table,
+                                                                int64_t B, const T* __restrict__ pool, int nbx, int nby,
+                                                                int nbz, float* __restrict__ data) {
+    const int64_t v = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x;
+    if (v >= (int64_t)nx * ny * nz) return;
+    const int g[3] = {(int)(v / ((int64_t)nz * ny)), (int)((v / nz) % ny), (int)(v % nz)};
+    const int nb[3] = {nbx, nby, nbz};
+    // per axis the lower candidate (brick b - 1, local 8: a shared face) and the upper one (brick b, local g & 7)
+    int cb[3][2], cl[3][2];
+    bool ok[3][2];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        const int b = g[x] >> kShift, l = g[x] & (kBrick - 1);
+        cb[x][0] = b - 1, cl[x][0] = kBrick, ok[x][0] = l == 0 && b >= 1;
+        cb[x][1] = b, cl[x][1] = l, ok[x][1] = b < nb[x];
+    }
+    int64_t src = -1;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {  // ascending brick index: x slowest
+        const int si = s >> 2, sj = (s >> 1) & 1, sk = s & 1;
+        if (src < 0 && ok[0][si] && ok[1][sj] && ok[2][sk]) {
+            const int64_t slot = table[((int64_t)cb[0][si] * nby + cb[1][sj]) * nbz + cb[2][sk]];
+            if (slot >= 0 && slot < B)
+                src = (slot * kBrickVerts + (cl[0][si] * kEdge + cl[1][sj]) * kEdge + cl[2][sk]) * C;
+        }
+    }
+    for (int ch = 0; ch < C; ++ch) data[v * C + ch] = src >= 0 ? (float)pool[src + ch] : 0.f;
+}
+
 // -------------------------------------------------------------------------------------------------------------- march
+// Storage policies.  present() says whether the cell's brick can hold a positive sigma, locate() prepares the tap of a
+// cell in a present brick, value() is corner q (order i, j, k, low first), channel ch.  Tap is all a policy keeps, and only
+// from present() to the end of the sample.
+struct DenseStore {
+    static constexpr bool kBricks = false;
+    const float* data;
+    const uint8_t* occ;  // null: no brick jumps
+    struct Tap {
+        int64_t off[8];
+    };
+    __device__ __forceinline__ bool jumps() const { return occ != nullptr; }
+    __device__ __forceinline__ bool present(const int (&c)[3], const int (&n)[3], Tap&) const {
+        if (!occ) return true;
+        const int nb1 = (n[1] + kBrick - 2) >> kShift, nb2 = (n[2] + kBrick - 2) >> kShift;
+        return occ[((int64_t)(c[0] >> kShift) * nb1 + (c[1] >> kShift)) * nb2 + (c[2] >> kShift)] != 0;
+    }
+    __device__ __forceinline__ void locate(const int (&c)[3], const int (&n)[3], int C, Tap& tap) const {
+        const int64_t base = ((int64_t)c[0] * n[1] + c[1]) * n[2] + c[2];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            tap.off[q] = (base + ((int64_t)(q >> 2) * n[1] + ((q >> 1) & 1)) * n[2] + (q & 1)) * C;
+    }
+    __device__ __forceinline__ double value(const Tap& tap, int q, int ch) const { return (double)data[tap.off[q] + ch]; }
+};
+
+template <typename T>
+struct BrickStore {
+    static constexpr bool kBricks = true;
+    const int32_t* table;
+    const T* pool;
+    int skip;
+    struct Tap {
+        int64_t base;  // the slot from present(), the value index of the low corner from locate()
+        int C;
+    };
+    __device__ __forceinline__ bool jumps() const { return skip != 0; }
+    __device__ __forceinline__ bool present(const int (&c)[3], const int (&n)[3], Tap& tap) const {
+        const int nb1 = (n[1] + kBrick - 2) >> kShift, nb2 = (n[2] + kBrick - 2) >> kShift;
+        tap.base = table[((int64_t)(c[0] >> kShift) * nb1 + (c[1] >> kShift)) * nb2 + (c[2] >> kShift)];
+        return tap.base >= 0;
+    }
+    __device__ __forceinline__ void locate(const int (&c)[3], const int (&)[3], int C, Tap& tap) const {
+        constexpr int m = kBrick - 1;
+        tap.base = (tap.base * kBrickVerts + ((c[0] & m) * kEdge + (c[1] & m)) * kEdge + (c[2] & m)) * C;
+        tap.C = C;
+    }
+    __device__ __forceinline__ double value(const Tap& tap, int q, int ch) const {
+        const int corner = ((q >> 2) * kEdge + ((q >> 1) & 1)) * kEdge + (q & 1);  // a constant once unrolled
+        return (double)(float)pool[tap.base + (int64_t)corner * tap.C + ch];
+    }
+};
+
+template <class Store>
 struct MarchArgs {
     int64_t R;
     int n[3];  // vertices per axis
     int E;     // attribute channels
-    const float* data;
-    const uint8_t* occ;  // null: no brick jumps
+    Store store;
     double lo[3], st[3];
     const float *origins, *directions, *near, *far;
     double step, t_min;
@@ -69,8 +192,8 @@ __device__ __forceinline__ int propose(double s, int k, int n) {
     return (int)floor(s);
 }
 
-template <int kDeg, int kEmax>
-__global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs a) {
+template <class Store, int kDeg, int kEmax>
+__global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs<Store> a) {
     constexpr int K = (kDeg + 1) * (kDeg + 1);
     const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (r >= a.R) return;
@@ -171,55 +294,53 @@ __global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs a) {
                 c[x] = imin((int)fl, a.n[x] - 2);
                 f[x] = g[x] - (double)c[x];
             }
-            if (a.occ) {
-                const int b0 = c[0] >> kShift, b1 = c[1] >> kShift, b2 = c[2] >> kShift;
-                const int nb1 = (a.n[1] + kBrick - 2) >> kShift, nb2 = (a.n[2] + kBrick - 2) >> kShift;
-                if (a.occ[((int64_t)b0 * nb1 + b1) * nb2 + b2] == 0) {
-                    // every cell of this brick has corners <= 0 or NaN only: skip to the last lattice point still in it
-                    const int b[3] = {b0, b1, b2};
-                    double s = (double)(n - 1);
-#pragma unroll
-                    for (int x = 0; x < 3; ++x) {
-                        if (d[x] != 0.0) {  // an axis the ray does not move along never leaves the brick: no division
-                            const int up = imin((b[x] + 1) * kBrick, a.n[x] - 1);
-                            const double sx = plane(x, d[x] > 0.0 ? (double)up : (double)(b[x] * kBrick));
-                            s = sx < s ? sx : s;
-                        }
-                    }
-                    int cand = propose(s, k, n);
-#pragma unroll 1
-                    for (int tries = 0; tries < 2 && cand > k; ++tries) {
-                        bool same = true;
-#pragma unroll
-                        for (int x = 0; x < 3; ++x) {
-                            const double gc = coord(x, cand);
-                            const bool in = gc >= 0.0 && gc <= (double)(a.n[x] - 1);
-                            const int cc = in ? imin((int)floor(gc), a.n[x] - 2) : -kBrick;
-                            same = same && (cc >> kShift) == b[x];
-                        }
-                        if (same) break;
-                        cand = tries == 0 ? cand - 1 : k;
-                    }
-                    k = cand + 1;
+            typename Store::Tap tap;
+            if (!a.store.present(c, a.n, tap)) {
+                if (Store::kBricks && !a.store.jumps()) {  // an absent brick without jumps: one sigma tap of value 0
+                    ++n_sigma;
+                    ++k;
                     continue;
                 }
+                // every cell of this brick has corners <= 0 or NaN only: skip to the last lattice point still in it
+                const int b[3] = {c[0] >> kShift, c[1] >> kShift, c[2] >> kShift};
+                double s = (double)(n - 1);
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    if (d[x] != 0.0) {  // an axis the ray does not move along never leaves the brick: no division
+                        const int up = imin((b[x] + 1) * kBrick, a.n[x] - 1);
+                        const double sx = plane(x, d[x] > 0.0 ? (double)up : (double)(b[x] * kBrick));
+                        s = sx < s ? sx : s;
+                    }
+                }
+                int cand = propose(s, k, n);
+#pragma unroll 1
+                for (int tries = 0; tries < 2 && cand > k; ++tries) {
+                    bool same = true;
+#pragma unroll
+                    for (int x = 0; x < 3; ++x) {
+                        const double gc = coord(x, cand);
+                        const bool in = gc >= 0.0 && gc <= (double)(a.n[x] - 1);
+                        const int cc = in ? imin((int)floor(gc), a.n[x] - 2) : -kBrick;
+                        same = same && (cc >> kShift) == b[x];
+                    }
+                    if (same) break;
+                    cand = tries == 0 ? cand - 1 : k;
+                }
+                k = cand + 1;
+                continue;
             }
             // ---- the trilinear tap: weights (wx wy) wz, corners in the order i, j, k, low corner first
             double w[8];
-            int64_t off[8];
-            {
-                const int64_t base = ((int64_t)c[0] * a.n[1] + c[1]) * a.n[2] + c[2];
+            a.store.locate(c, a.n, C, tap);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int qi = q >> 2, qj = (q >> 1) & 1, qk = q & 1;
-                    w[q] = ((qi ? f[0] : 1.0 - f[0]) * (qj ? f[1] : 1.0 - f[1])) * (qk ? f[2] : 1.0 - f[2]);
-                    off[q] = (base + ((int64_t)qi * a.n[1] + qj) * a.n[2] + qk) * C;
-                }
+            for (int q = 0; q < 8; ++q) {
+                const int qi = q >> 2, qj = (q >> 1) & 1, qk = q & 1;
+                w[q] = ((qi ? f[0] : 1.0 - f[0]) * (qj ? f[1] : 1.0 - f[1])) * (qk ? f[2] : 1.0 - f[2]);
             }
             ++n_sigma;
             double sigma = 0.0;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) sigma = sigma + w[q] * (double)a.data[off[q]];
+            for (int q = 0; q < 8; ++q) sigma = sigma + w[q] * a.store.value(tap, q, 0);
             if (!(sigma > 0.0)) {
                 ++k;
                 continue;
@@ -231,9 +352,8 @@ __global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs a) {
                 double tri[3] = {0.0, 0.0, 0.0};
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const float* p = a.data + off[q] + 1 + 3 * kk;
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) tri[ch] = tri[ch] + w[q] * (double)p[ch];
+                    for (int ch = 0; ch < 3; ++ch) tri[ch] = tri[ch] + w[q] * a.store.value(tap, q, 1 + 3 * kk + ch);
                 }
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) col[ch] = col[ch] + Y[kk] * tri[ch];
@@ -247,7 +367,7 @@ __global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs a) {
                 if (e < a.E) {
                     double tri = 0.0;
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) tri = tri + w[q] * (double)a.data[off[q] + 1 + 3 * K + e];
+                    for (int q = 0; q < 8; ++q) tri = tri + w[q] * a.store.value(tap, q, 1 + 3 * K + e);
                     at[e] = at[e] + wgt * tri;
                 }
             }
@@ -281,13 +401,47 @@ bool grid_ok(int nx, int ny, int nz) {
     return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
 }
 
-template <int kDeg>
-void launch_march(const MarchArgs& a, bool attrs, hipStream_t s) {
+template <class Store, int kDeg>
+void launch_march(const MarchArgs<Store>& a, bool attrs, hipStream_t s) {
     const dim3 grid(nblk(a.R, kThreads)), block(kThreads);
     if (attrs)
-        hipLaunchKernelGGL((k_volume_march<kDeg, PN_VOLUME_MAX_ATTR>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((k_volume_march<Store, kDeg, PN_VOLUME_MAX_ATTR>), grid, block, 0, s, a);
     else
-        hipLaunchKernelGGL((k_volume_march<kDeg, 0>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((k_volume_march<Store, kDeg, 0>), grid, block, 0, s, a);
+}
+
+// what pn_volume_march and pn_volume_march_sparse share: the argument checks and the dispatch over the SH degree
+template <class Store>
+int march(const Store& store, bool have_store, int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float (&lo)[3],
+          const float (&st)[3], const float* origins, const float* directions, const float* near, const float* far,
+          float step, float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
+    bool ok = R >= 0 && R < ((int64_t)1 << 31) * kThreads && grid_ok(nx, ny, nz) && sh_degree >= 0 && sh_degree <= 2 &&
+              E >= 0 && E <= PN_VOLUME_MAX_ATTR && step > 0.f && step < INFINITY && t_min >= 0.f && t_min < INFINITY;
+    for (int x = 0; x < 3; ++x) ok = ok && lo[x] - lo[x] == 0.f && st[x] > 0.f && st[x] < INFINITY;
+    if (!ok) return PN_ERR_BAD_SHAPE;
+    if (R == 0) return PN_OK;
+    if (!have_store || !origins || !directions || !near || !far) return PN_ERR_NULL;
+    MarchArgs<Store> a{R, {nx, ny, nz}, E, store, {}, {}, origins, directions, near, far, (double)step, (double)t_min,
+                       rgb, depth, acc, attrs, taps};
+    for (int x = 0; x < 3; ++x) a.lo[x] = (double)lo[x], a.st[x] = (double)st[x];
+    const bool with_attrs = E > 0 && attrs;
+    switch (sh_degree) {
+        case 0: launch_march<Store, 0>(a, with_attrs, ST(stream)); break;
+        case 1: launch_march<Store, 1>(a, with_attrs, ST(stream)); break;
+        default: launch_march<Store, 2>(a, with_attrs, ST(stream)); break;
+    }
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int64_t brick_count(int nx, int ny, int nz) {
+    return (int64_t)((nx + kBrick - 2) >> kShift) * ((ny + kBrick - 2) >> kShift) * ((nz + kBrick - 2) >> kShift);
+}
+
+// the checks pack and unpack share; B 729 C < 2^40 keeps every value index far inside 64 bits
+bool pool_ok(int nx, int ny, int nz, int channels, int64_t B) {
+    if (!grid_ok(nx, ny, nz) || channels < 1 || channels > 65536 || B < 0) return false;
+    return B <= brick_count(nx, ny, nz) && B * kBrickVerts * channels < ((int64_t)1 << 40);
 }
 
 }  // namespace
@@ -296,7 +450,7 @@ extern "C" {
 
 int64_t pn_volume_bricks(int nx, int ny, int nz) {
     if (!grid_ok(nx, ny, nz)) return -1;
-    return (int64_t)((nx + kBrick - 2) >> kShift) * ((ny + kBrick - 2) >> kShift) * ((nz + kBrick - 2) >> kShift);
+    return brick_count(nx, ny, nz);
 }
 
 int pn_volume_occupancy(int nx, int ny, int nz, int channels, const float* data, uint8_t* occupancy, void* stream) {
@@ -314,23 +468,55 @@ int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, con
                     const float* directions, const float* near, const float* far, float step, float t_min, float* rgb,
                     float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
     const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
-    bool ok = R >= 0 && R < ((int64_t)1 << 31) * kThreads && grid_ok(nx, ny, nz) && sh_degree >= 0 && sh_degree <= 2 &&
-              E >= 0 && E <= PN_VOLUME_MAX_ATTR && step > 0.f && step < INFINITY && t_min >= 0.f && t_min < INFINITY;
-    for (int x = 0; x < 3; ++x) ok = ok && lo[x] - lo[x] == 0.f && st[x] > 0.f && st[x] < INFINITY;
-    if (!ok) return PN_ERR_BAD_SHAPE;
-    if (R == 0) return PN_OK;
-    if (!data || !origins || !directions || !near || !far) return PN_ERR_NULL;
-    MarchArgs a{R, {nx, ny, nz}, E, data, occupancy, {}, {}, origins, directions, near, far, (double)step, (double)t_min,
-                rgb, depth, acc, attrs, taps};
-    for (int x = 0; x < 3; ++x) a.lo[x] = (double)lo[x], a.st[x] = (double)st[x];
-    const bool with_attrs = E > 0 && attrs;
-    switch (sh_degree) {
-        case 0: launch_march<0>(a, with_attrs, ST(stream)); break;
-        case 1: launch_march<1>(a, with_attrs, ST(stream)); break;
-        default: launch_march<2>(a, with_attrs, ST(stream)); break;
-    }
+    return march(DenseStore{data, occupancy}, data != nullptr, R, nx, ny, nz, sh_degree, E, lo, st, origins, directions, near,
+                 far, step, t_min, rgb, depth, acc, attrs, taps, stream);
+}
+
+int pn_volume_pack(int nx, int ny, int nz, int channels, const int32_t* table, int64_t B, const float* data,
+                   const float* rows, int64_t M, const int32_t* vertex_row, int half, void* pool, void* stream) {
+    const bool dense = data != nullptr, by_rows = rows != nullptr || vertex_row != nullptr;
+    if (!pool_ok(nx, ny, nz, channels, B) || M < 0 || (dense && by_rows)) return PN_ERR_BAD_SHAPE;
+    if (!table || !(dense || by_rows) || (by_rows && (!vertex_row || (M > 0 && !rows)))) return PN_ERR_NULL;
+    if (B == 0) return PN_OK;
+    if (!pool) return PN_ERR_NULL;
+    const int nby = (ny + kBrick - 2) >> kShift, nbz = (nz + kBrick - 2) >> kShift;
+    const dim3 grid((unsigned)brick_count(nx, ny, nz)), block(kCopyThreads);
+    if (half)
+        hipLaunchKernelGGL(k_volume_pack<_Float16>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B, data, rows, M,
+                           vertex_row, nby, nbz, (_Float16*)pool);
+    else
+        hipLaunchKernelGGL(k_volume_pack<float>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B, data, rows, M,
+                           vertex_row, nby, nbz, (float*)pool);
     PN_CHECK_LAUNCH();
     return PN_OK;
+}
+
+int pn_volume_unpack(int nx, int ny, int nz, int channels, const int32_t* table, int64_t B, const void* pool, int half,
+                     float* data, void* stream) {
+    if (!pool_ok(nx, ny, nz, channels, B)) return PN_ERR_BAD_SHAPE;
+    if (!table || !data || (B > 0 && !pool)) return PN_ERR_NULL;
+    const int nbx = (nx + kBrick - 2) >> kShift, nby = (ny + kBrick - 2) >> kShift, nbz = (nz + kBrick - 2) >> kShift;
+    const dim3 grid(nblk((int64_t)nx * ny * nz, kCopyThreads)), block(kCopyThreads);
+    if (half)
+        hipLaunchKernelGGL(k_volume_unpack<_Float16>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B,
+                           (const _Float16*)pool, nbx, nby, nbz, data);
+    else
+        hipLaunchKernelGGL(k_volume_unpack<float>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B,
+                           (const float*)pool, nbx, nby, nbz, data);
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_volume_march_sparse(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const int32_t* table, const void* pool,
+                           int half, int skip, float x0, float y0, float z0, float dx, float dy, float dz,
+                           const float* origins, const float* directions, const float* near, const float* far, float step,
+                           float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
+    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
+    if (half)
+        return march(BrickStore<_Float16>{table, (const _Float16*)pool, skip}, table != nullptr, R, nx, ny, nz, sh_degree, E,
+                     lo, st, origins, directions, near, far, step, t_min, rgb, depth, acc, attrs, taps, stream);
+    return march(BrickStore<float>{table, (const float*)pool, skip}, table != nullptr, R, nx, ny, nz, sh_degree, E, lo, st,
+                 origins, directions, near, far, step, t_min, rgb, depth, acc, attrs, taps, stream);
 }
 
 }  // extern "C"

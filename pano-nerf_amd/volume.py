@@ -10,6 +10,13 @@ stream; CPU tensors raise, there is no host fallback.
       .sigma / .coeff / .attributes             views: [nx, ny, nz], [nx, ny, nz, K, 3], name -> [nx, ny, nz, w]
       .occupancy / .refresh()                   one byte per brick (pn_volume_occupancy), built lazily; refresh after edits
       .save(path) / RadianceVolume.load(path, device)   volume.json + volume.bin, bit for bit
+      .to_sparse(dtype)                         the occupied bricks only, as a SparseRadianceVolume
+    SparseRadianceVolume(table, pool, bounds, resolution, sh_degree, attributes)   table int32 [nbx, nby, nbz] (slot or -1),
+                                                pool [B, 9, 9, 9, C] fp32 or fp16: the present bricks, marched in place
+      .from_dense(vol, dtype) / .to_dense()     pn_volume_pack / pn_volume_unpack; fp32 round-trips bit for bit on every
+                                                vertex of a present brick, the rest is 0
+      .nbytes / .dense_nbytes / .bricks / .dtype / .occupancy
+      .save(path) / .load(path, device)         volume.json + table.bin + pool.bin; load_volume(path) takes either kind
     fibonacci_directions(D)                     the fp64 spherical Fibonacci set the bake evaluates the colour along
     sh_basis(directions, sh_degree)             numpy fp64 [D, K] in lighting's order and constants
     bake_volume(model, bounds, resolution, ...) density_grid pruned at sigma_min, SH fitted to query_field's rgb, attributes
@@ -23,8 +30,12 @@ Conventions, not measurements: D = 4 K baking directions, a marching step of hal
 bricks of 8 cells.  sigma_min = 0.01 / |box diagonal| is derived: pruning removes at most 0.01 of optical depth from any
 ray through the box.
 
-Out of scope: fp16 or compressed storage, sparse or hashed volumes, an fp32-arithmetic marcher, gradients or fine-tuning of
-the volume, cone-aware (mip) filtering, baking the surface / shading branch, and stereo baking.
+The sparse form is stated in the header's section "sparse radiance volume" and argued in DESIGN.md 6p: marching it gives
+the bits of marching its dense expansion, because the marcher's arithmetic is fp64 on the stored values either way.
+
+Out of scope: a split sigma / colour pool, quantised or block-compressed storage, hashed tables, bricks other than 8,
+editing a sparse volume in place, an fp32-arithmetic marcher, gradients or fine-tuning of the volume, cone-aware (mip)
+filtering, baking the surface / shading branch, and stereo baking.
 """
 import json
 import math
@@ -39,6 +50,8 @@ from .geometry import _model_device, _placement, _resolution, _variance, density
 from .rays import CameraRig
 
 BRICK = 8          # PN_VOLUME_BRICK
+BRICK_VERTICES = (BRICK + 1) ** 3  # a stored brick: its 8^3 cells' vertices, the shared far faces included
+_SPARSE_FORMAT = "pano_nerf_amd.sparse_radiance_volume"
 MAX_ATTR = 8       # PN_VOLUME_MAX_ATTR
 GOLDEN_ANGLE = 2.399963229728653  # PN_VOLUME_GOLDEN_ANGLE = pi (3 - sqrt 5)
 _SH_C = (0.28209479177387814, 0.48860251190291992, 1.0925484305920792, 0.31539156525252005, 0.54627421529603959)
@@ -142,6 +155,89 @@ def read_volume_files(path):
     return raw.astype(np.float32, copy=False).reshape(*res, C), _bounds(meta["bounds"]), int(meta["sh_degree"]), attrs
 
 
+def _brick_counts(res):
+    return tuple((n + BRICK - 2) // BRICK for n in res)
+
+
+def _check_pool_size(B, C):
+    if B * BRICK_VERTICES * C >= 1 << 40:
+        raise ValueError(f"a pool of {B} bricks x {BRICK_VERTICES} vertices x {C} channels passes the 2^40 values the layout "
+                         "allows")
+
+
+def write_sparse_volume_files(path, table, pool, bounds, resolution, sh_degree, attributes=()):
+    """Write host arrays table int32 [nbx, nby, nbz] and pool fp32 / fp16 [B, 9, 9, 9, C] as path/volume.json +
+    path/table.bin (<i4) + path/pool.bin (<f4 or <f2): the layout of include/panonerf_hip.h, "sparse radiance volume"."""
+    t, p = np.asarray(table), np.asarray(pool)
+    attrs = _attributes(attributes)
+    res = _resolution(resolution)
+    C = 1 + 3 * _sh_count(sh_degree) + sum(w for _, w in attrs)
+    if t.dtype != np.int32 or t.shape != _brick_counts(res):
+        raise ValueError(f"table must be int32 {_brick_counts(res)} for resolution {res}; got {t.dtype} {t.shape}")
+    if p.dtype not in (np.float32, np.float16) or p.ndim != 5 or p.shape[1:] != (BRICK + 1,) * 3 + (C,):
+        raise ValueError(f"pool must be fp32 or fp16 [B, 9, 9, 9, 1 + 3 K + E = {C}]; got {p.dtype} {p.shape}")
+    if int((t >= 0).sum()) != p.shape[0]:
+        raise ValueError(f"table marks {int((t >= 0).sum())} bricks present, the pool holds {p.shape[0]}")
+    b = _bounds(bounds)
+    lo, step = _grid(b, res)
+    os.makedirs(path, exist_ok=True)
+    dtype = "<f4" if p.dtype == np.float32 else "<f2"
+    meta = dict(format=_SPARSE_FORMAT, version=1, bounds=[list(c) for c in b], resolution=list(res),
+                sh_degree=int(sh_degree), attributes=[[n, w] for n, w in attrs], channels=C, bricks=int(p.shape[0]),
+                dtype=dtype, lo=list(lo), step=list(step), brick=BRICK,
+                order="table [nbx, nby, nbz] slot or -1; pool [B, 9, 9, 9, C], C fastest")
+    with open(os.path.join(path, "volume.json"), "w") as fh:
+        json.dump(meta, fh, indent=1)
+    with open(os.path.join(path, "table.bin"), "wb") as fh:
+        fh.write(np.ascontiguousarray(t, dtype="<i4").tobytes())
+    with open(os.path.join(path, "pool.bin"), "wb") as fh:
+        fh.write(np.ascontiguousarray(p, dtype=dtype).tobytes())
+
+
+def read_sparse_volume_files(path):
+    """-> (table int32 [nbx, nby, nbz], pool [B, 9, 9, 9, C] fp32 or fp16, bounds, resolution, sh_degree, attributes): host
+    arrays of what write_sparse_volume_files wrote"""
+    with open(os.path.join(path, "volume.json")) as fh:
+        meta = json.load(fh)
+    if meta.get("format") != _SPARSE_FORMAT or meta.get("version") != 1:
+        raise ValueError(f"{path}: not a sparse radiance volume (format {meta.get('format')!r}, version "
+                         f"{meta.get('version')!r})")
+    res = _resolution(meta["resolution"])
+    attrs = _attributes([tuple(a) for a in meta["attributes"]])
+    C = 1 + 3 * _sh_count(meta["sh_degree"]) + sum(w for _, w in attrs)
+    B = int(meta["bricks"])
+    if meta.get("dtype") not in ("<f4", "<f2"):
+        raise ValueError(f"{path}: the pool's dtype must be '<f4' or '<f2'; got {meta.get('dtype')!r}")
+    nb = _brick_counts(res)
+    table = np.fromfile(os.path.join(path, "table.bin"), dtype="<i4")
+    if table.size != nb[0] * nb[1] * nb[2]:
+        raise ValueError(f"{path}: table.bin holds {table.size} entries, resolution {res} has {nb} bricks")
+    pool = np.fromfile(os.path.join(path, "pool.bin"), dtype=meta["dtype"])
+    if B < 0 or pool.size != B * BRICK_VERTICES * C:
+        raise ValueError(f"{path}: pool.bin holds {pool.size} values, the header asks for {B} x {BRICK_VERTICES} x {C}")
+    dtype = np.float32 if meta["dtype"] == "<f4" else np.float16
+    return (table.astype(np.int32, copy=False).reshape(nb), pool.astype(dtype, copy=False).reshape(B, *(BRICK + 1,) * 3, C),
+            _bounds(meta["bounds"]), res, int(meta["sh_degree"]), attrs)
+
+
+def load_volume(path, device=None):
+    """RadianceVolume.load or SparseRadianceVolume.load, by the `format` field of path/volume.json"""
+    with open(os.path.join(path, "volume.json")) as fh:
+        fmt = json.load(fh).get("format")
+    if fmt == _SPARSE_FORMAT:
+        return SparseRadianceVolume.load(path, device)
+    if fmt == "pano_nerf_amd.radiance_volume":
+        return RadianceVolume.load(path, device)
+    raise ValueError(f"{path}: not a radiance volume of either kind (format {fmt!r})")
+
+
+def _load_device(device):
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (device=%s); there is no CPU fallback" % dev)
+    return dev
+
+
 # ----------------------------------------------------------------------------------------------------------- volume
 class RadianceVolume:
     """One packed fp32 tensor data [nx, ny, nz, C] on the vertex grid of geometry.density_grid (bounds are the inclusive
@@ -217,17 +313,178 @@ class RadianceVolume:
 
     @classmethod
     def load(cls, path, device=None):
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (device=%s); there is no CPU fallback" % dev)
+        dev = _load_device(device)
         data, bounds, sh_degree, attrs = read_volume_files(path)
         return cls(torch.from_numpy(np.ascontiguousarray(data)).to(dev), bounds, sh_degree, attrs)
+
+    def to_sparse(self, dtype=torch.float32):
+        """SparseRadianceVolume.from_dense(self, dtype): the occupied bricks only, in fp32 or fp16"""
+        return SparseRadianceVolume.from_dense(self, dtype)
+
+
+# ---------------------------------------------------------------------------------------------------- sparse volume
+def _pool_dtype(dtype):
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"a brick pool is torch.float32 or torch.float16; got {dtype!r}")
+    return dtype
+
+
+def _brick_table(occ):
+    """(table int32 like occ, B): slots 0 .. B - 1 in ascending brick index, -1 where occ is 0 (one host sync for B)"""
+    flat = occ.reshape(-1).to(torch.int64)
+    slots = torch.cumsum(flat, 0) - flat  # exclusive
+    table = torch.where(flat > 0, slots, -1).to(torch.int32).view(occ.shape)
+    return table, int(flat.sum())
+
+
+def _channel_name(ch, sh_degree, attrs):
+    K = _sh_count(sh_degree)
+    if ch == 0:
+        return "sigma"
+    if ch < 1 + 3 * K:
+        return f"coeff[{(ch - 1) // 3}][{'rgb'[(ch - 1) % 3]}]"
+    ch -= 1 + 3 * K
+    for name, w in attrs:
+        if ch < w:
+            return f"{name}[{ch}]"
+        ch -= w
+    return f"channel {ch}"
+
+
+def _pack(res, C, table, B, dtype, dev, data=None, rows=None, vertex_row=None):
+    """the pool [B, 9, 9, 9, C] of `table`, by pn_volume_pack from the dense data or from rows + vertex_row"""
+    _check_pool_size(B, C)
+    pool = torch.empty(B, BRICK + 1, BRICK + 1, BRICK + 1, C, dtype=dtype, device=dev)
+    M = 0 if rows is None else int(rows.shape[0])
+    _lib.call("pn_volume_pack", *res, C, table.data_ptr(), B, _lib.ptr(data), _lib.ptr(rows) if M else None, M,
+              _lib.ptr(vertex_row), int(dtype == torch.float16), pool.data_ptr() if B else None, _lib.stream(dev))
+    return pool
+
+
+class SparseRadianceVolume:
+    """The radiance volume with its unoccupied bricks left out: table int32 [nbx, nby, nbz] (a brick's slot in the pool,
+    or -1; slots ascend with the brick index) and pool [B, 9, 9, 9, C] in fp32 or fp16, a present brick's 9^3 vertices
+    with C fastest (include/panonerf_hip.h, "sparse radiance volume").  Made by RadianceVolume.to_sparse / from_dense or
+    by bake_volume(sparse=True); marched in place by every function that takes a RadianceVolume.  Vertices on shared
+    faces are stored once per present brick, so this is not a volume to edit in place: go through to_dense()."""
+
+    def __init__(self, table, pool, bounds, resolution, sh_degree, attributes=()):
+        K = _sh_count(sh_degree)
+        self.sh_degree = int(sh_degree)
+        self._attrs = _attributes(attributes)
+        self.resolution = _resolution(resolution)
+        for t, what in ((table, "table"), (pool, "pool")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what} must be a tensor; got {type(t).__name__}")
+            if t.device.type != "cuda":
+                raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the %s is on %s); there is no CPU "
+                                   "fallback" % (what, t.device))
+        nb = _brick_counts(self.resolution)
+        if table.dtype != torch.int32 or tuple(table.shape) != nb or not table.is_contiguous():
+            raise ValueError(f"table must be a contiguous int32 {nb} tensor for resolution {self.resolution}; got "
+                             f"{table.dtype} {tuple(table.shape)}")
+        C = 1 + 3 * K + sum(w for _, w in self._attrs)
+        if pool.dim() != 5 or tuple(pool.shape[1:]) != (BRICK + 1,) * 3 + (C,):
+            raise ValueError(f"pool must be [B, 9, 9, 9, C] with 1 + 3 K + E = {C} channels for sh_degree {sh_degree} and "
+                             f"attributes {self._attrs}; got {tuple(pool.shape)}")
+        if pool.dtype not in (torch.float32, torch.float16) or not pool.is_contiguous():
+            raise ValueError("pool must be a contiguous fp32 or fp16 tensor (it is held and read in place)")
+        if pool.device != table.device:
+            raise ValueError(f"table is on {table.device} but pool on {pool.device}")
+        B = int(pool.shape[0])
+        _check_pool_size(B, C)
+        # the marcher trusts the table: every entry is -1 or the next slot, and there are B of them (one host sync)
+        flat = table.detach().reshape(-1)
+        present = flat >= 0
+        want = torch.where(present, torch.cumsum(present.to(torch.int64), 0) - 1, -1)
+        if not bool(((flat == want).all()) & (present.sum() == B)):
+            raise ValueError(f"table must hold -1 or the slots 0 .. {B - 1} of the pool in ascending brick index")
+        self.bounds = _bounds(bounds)
+        self.lo, self.step = _grid(self.bounds, self.resolution)
+        self.table, self.pool = table.detach(), pool.detach()
+        self.device = table.device
+        self.attribute_names = tuple(n for n, _ in self._attrs)
+
+    @property
+    def dtype(self):
+        return self.pool.dtype
+
+    @property
+    def bricks(self):
+        return int(self.pool.shape[0])
+
+    @property
+    def channels(self):
+        return int(self.pool.shape[4])
+
+    @property
+    def occupancy(self):
+        """uint8 [nbx, nby, nbz]: 1 iff the brick is present"""
+        return (self.table >= 0).to(torch.uint8)
+
+    @property
+    def nbytes(self):
+        """bytes of the table and the pool"""
+        return self.table.numel() * 4 + self.pool.numel() * self.pool.element_size()
+
+    @property
+    def dense_nbytes(self):
+        """bytes of the dense fp32 tensor [nx, ny, nz, C] this volume expands to"""
+        return self.resolution[0] * self.resolution[1] * self.resolution[2] * self.channels * 4
+
+    @classmethod
+    def from_dense(cls, vol, dtype=torch.float32):
+        """Pack the occupied bricks of a RadianceVolume (its occupancy is rebuilt from the data first): occupancy, an
+        exclusive prefix sum for the slots (one host sync for B), pn_volume_pack.  With fp16 a finite value of a present
+        brick that rounds to an infinity raises ValueError naming its channel (one more sync)."""
+        if not isinstance(vol, RadianceVolume):
+            raise ValueError(f"from_dense takes a RadianceVolume; got {type(vol).__name__}")
+        dtype = _pool_dtype(dtype)
+        dev = vol.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            table, B = _brick_table(vol.refresh().occupancy)
+            pool = _pack(vol.resolution, vol.channels, table, B, dtype, dev, data=vol.data)
+            out = cls(table, pool, vol.bounds, vol.resolution, vol.sh_degree, vol._attrs)
+            if dtype == torch.float16 and bool(torch.isinf(pool).any()):
+                # rare: tell the infinities the source had from the ones the rounding made
+                bad = torch.isinf(out.to_dense().data) & torch.isfinite(vol.data)
+                chans = torch.nonzero(bad.view(-1, vol.channels).any(0)).view(-1).tolist()
+                if chans:
+                    names = ", ".join(_channel_name(c, vol.sh_degree, vol._attrs) for c in chans)
+                    raise ValueError(f"fp16 storage overflows in {names}: a finite value of a present brick has magnitude "
+                                     ">= 65520")
+        return out
+
+    def to_dense(self):
+        """The RadianceVolume this volume expands to (pn_volume_unpack): the stored value on every vertex of a present
+        brick, fp16 widened exactly, and 0 elsewhere."""
+        with torch.no_grad(), torch.cuda.device(self.device):
+            data = torch.empty(*self.resolution, self.channels, dtype=torch.float32, device=self.device)
+            _lib.call("pn_volume_unpack", *self.resolution, self.channels, self.table.data_ptr(), self.bricks,
+                      self.pool.data_ptr() if self.bricks else None, int(self.dtype == torch.float16), data.data_ptr(),
+                      _lib.stream(self.device))
+        return RadianceVolume(data, self.bounds, self.sh_degree, self._attrs)
+
+    def save(self, path):
+        """path/volume.json, path/table.bin (<i4) and path/pool.bin (<f4 or <f2), by write_sparse_volume_files"""
+        write_sparse_volume_files(path, self.table.cpu().numpy(), self.pool.cpu().numpy(), self.bounds, self.resolution,
+                                  self.sh_degree, self._attrs)
+
+    @classmethod
+    def load(cls, path, device=None):
+        dev = _load_device(device)
+        table, pool, bounds, res, sh_degree, attrs = read_sparse_volume_files(path)
+        return cls(torch.from_numpy(np.ascontiguousarray(table)).to(dev), torch.from_numpy(np.ascontiguousarray(pool)).to(dev),
+                   bounds, res, sh_degree, attrs)
 
 
 # ------------------------------------------------------------------------------------------------------------- bake
 def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_min=None, attributes=("albedo", "normal"),
-                variance=None, chunk_rows=None):
-    """Bake `model` into a RadianceVolume on the grid of density_grid(model, bounds, resolution, variance).
+                variance=None, chunk_rows=None, sparse=False, dtype=torch.float32):
+    """Bake `model` into a RadianceVolume on the grid of density_grid(model, bounds, resolution, variance); with
+    sparse=True into a SparseRadianceVolume of `dtype` (fp32 or fp16) whose to_dense() is that RadianceVolume bit for bit
+    (fp32), without ever allocating the dense tensor: the survivors' rows [M, C] are evaluated by the same calls in the
+    same order and packed into the present bricks through a vertex -> row map (pn_volume_pack).
 
     sigma is density_grid's, bit for bit, where it is > sigma_min and exactly 0 elsewhere (pruned; every channel of a pruned
     vertex is 0).  sigma_min None is 0.01 / |box diagonal|: trilinear interpolation is a convex combination, so pruning
@@ -239,6 +496,8 @@ def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_m
     they are rounded to fp32 first, and Y is evaluated at what the field sees.  attributes: "albedo" (PanoMipNeRF only)
     and / or "normal", query_field's at the same rows, bit for bit."""
     K = _sh_count(sh_degree)
+    if sparse:
+        dtype = _pool_dtype(dtype)
     attributes = tuple(attributes)
     bad = [a for a in attributes if a not in _BAKE_ATTRIBUTES]
     if bad or len(set(attributes)) != len(attributes):
@@ -267,26 +526,57 @@ def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_m
     dev = _model_device(model)
     E = 3 * len(attributes)
     N = res[0] * res[1] * res[2]
+    C = 1 + 3 * K + E
+    attrs = tuple((a, 3) for a in attributes)
+
+    def fill(dst, sel, idx):
+        """the survivors' channels into dst[sel]: the dense tensor at rows idx, or the compact rows themselves"""
+        M = int(idx.shape[0])
+        dst[sel, 0] = sigma[idx]
+        pts = grid_points(b, res, 0.0, dev)[0][idx]
+        dirs_t = torch.from_numpy(dirs32).to(dev)
+        P_t = torch.from_numpy(P).to(dev)
+        coef = torch.zeros(M, K, 3, dtype=torch.float64, device=dev)
+        for i in range(dirs32.shape[0]):
+            rgb = query_field(model, pts, variance, viewdirs=dirs_t[i], outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
+            coef += P_t[:, i].view(1, K, 1) * rgb.to(torch.float64).view(M, 1, 3)
+        dst[sel, 1:1 + 3 * K] = coef.to(torch.float32).view(M, 3 * K)
+        if attributes:
+            q = query_field(model, pts, variance, outputs=attributes, chunk_rows=chunk_rows)
+            for j, name in enumerate(attributes):
+                dst[sel, 1 + 3 * K + 3 * j:4 + 3 * K + 3 * j] = q[name]
+
     with torch.no_grad(), torch.cuda.device(dev):
         sigma = density_grid(model, b, res, variance, chunk_rows).view(-1)
-        data = torch.zeros(N, 1 + 3 * K + E, dtype=torch.float32, device=dev)
-        idx = torch.nonzero(sigma > sigma_min).reshape(-1)  # the one host sync: the survivors size everything below
+        if not sparse:
+            data = torch.zeros(N, C, dtype=torch.float32, device=dev)
+            idx = torch.nonzero(sigma > sigma_min).reshape(-1)  # the one host sync: the survivors size everything below
+            if int(idx.shape[0]):
+                fill(data, idx, idx)
+            return RadianceVolume(data.view(*res, -1), b, sh_degree, attrs)
+        # sparse: the [N, C] tensor is never made.  The pruned sigma alone is a 1-channel volume whose occupancy is the
+        # baked volume's (a survivor has sigma > 0, so every brick that holds one is present)
+        keep = sigma > sigma_min
+        idx = torch.nonzero(keep).reshape(-1)
         M = int(idx.shape[0])
+        pruned = torch.where(keep, sigma, 0.0).contiguous()
+        occ = torch.empty(_brick_counts(res), dtype=torch.uint8, device=dev)
+        _lib.call("pn_volume_occupancy", *res, 1, pruned.data_ptr(), occ.data_ptr(), _lib.stream(dev))
+        table, B = _brick_table(occ)
+        del pruned, keep, occ
+        rows = torch.zeros(M, C, dtype=torch.float32, device=dev)
         if M:
-            data[idx, 0] = sigma[idx]
-            pts = grid_points(b, res, 0.0, dev)[0][idx]
-            dirs_t = torch.from_numpy(dirs32).to(dev)
-            P_t = torch.from_numpy(P).to(dev)
-            coef = torch.zeros(M, K, 3, dtype=torch.float64, device=dev)
-            for i in range(dirs32.shape[0]):
-                rgb = query_field(model, pts, variance, viewdirs=dirs_t[i], outputs=("rgb",), chunk_rows=chunk_rows)["rgb"]
-                coef += P_t[:, i].view(1, K, 1) * rgb.to(torch.float64).view(M, 1, 3)
-            data[idx, 1:1 + 3 * K] = coef.to(torch.float32).view(M, 3 * K)
-            if attributes:
-                q = query_field(model, pts, variance, outputs=attributes, chunk_rows=chunk_rows)
-                for j, name in enumerate(attributes):
-                    data[idx, 1 + 3 * K + 3 * j:4 + 3 * K + 3 * j] = q[name]
-    return RadianceVolume(data.view(*res, -1), b, sh_degree, tuple((a, 3) for a in attributes))
+            fill(rows, slice(None), idx)
+        if dtype == torch.float16:
+            over = torch.isfinite(rows) & ~torch.isfinite(rows.to(torch.float16))
+            chans = torch.nonzero(over.any(0)).view(-1).tolist()
+            if chans:
+                names = ", ".join(_channel_name(c, sh_degree, attrs) for c in chans)
+                raise ValueError(f"fp16 storage overflows in {names}: a baked value has magnitude >= 65520")
+        vertex_row = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        vertex_row[idx] = torch.arange(M, dtype=torch.int32, device=dev)
+        pool = _pack(res, C, table, B, dtype, dev, rows=rows, vertex_row=vertex_row)
+    return SparseRadianceVolume(table, pool, b, res, sh_degree, attrs)
 
 
 # ------------------------------------------------------------------------------------------------------------ march
@@ -311,8 +601,9 @@ def _rows(t, R, width, what, dev):
 
 
 def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=True, outputs=("rgb", "depth", "acc")):
-    """March rows of rays through `vol` in one launch of pn_volume_march: dict of rgb [R, 3], depth [R, 1], acc [R, 1] and
-    one [R, w] per requested attribute name, fp32 on the volume's device.
+    """March rows of rays through `vol` in one launch of pn_volume_march (a RadianceVolume) or pn_volume_march_sparse (a
+    SparseRadianceVolume, read in place): dict of rgb [R, 3], depth [R, 1], acc [R, 1] and one [R, w] per requested
+    attribute name, fp32 on the volume's device.
 
     origins, directions: [R, 3] device tensors (directions need not be unit: t runs along them as given, as in Rays); near,
     far: floats or [R] / [R, 1] tensors.  step: the world distance between samples, None = half the smallest grid step (a
@@ -321,8 +612,8 @@ def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=
     (clamp(wt / acc, near, far), 0 / 0 -> 0), so it feeds warp_view, fusion and relight unchanged; there is no background
     term: callers have acc.  A diagnostic besides: "taps" [R, 2] int32, the samples whose sigma was interpolated and, of
     those, the ones that read the colour too (what tools/profile_volume.py counts the gathered bytes with)."""
-    if not isinstance(vol, RadianceVolume):
-        raise ValueError(f"vol must be a RadianceVolume; got {type(vol).__name__}")
+    if not isinstance(vol, (RadianceVolume, SparseRadianceVolume)):
+        raise ValueError(f"vol must be a RadianceVolume or a SparseRadianceVolume; got {type(vol).__name__}")
     outputs = tuple(outputs)
     bad = [o for o in outputs if o not in _CORE + vol.attribute_names + (_TAPS,)]
     if bad or not outputs:
@@ -348,8 +639,14 @@ def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=
         acc = new(1) if "acc" in outputs else None
         attrs = new(E) if want_attr else None
         taps = torch.empty(R, 2, dtype=torch.int32, device=dev) if _TAPS in outputs else None
-        occ = vol.occupancy if skip else None
-        _lib.call("pn_volume_march", R, *vol.resolution, vol.sh_degree, E, vol.data.data_ptr(), _lib.ptr(occ), *vol.lo,
+        if isinstance(vol, SparseRadianceVolume):  # marched in place: the table is the occupancy
+            entry = "pn_volume_march_sparse"
+            store = (vol.table.data_ptr(), vol.pool.data_ptr() if vol.bricks else None, int(vol.dtype == torch.float16),
+                     int(bool(skip)))
+        else:
+            entry = "pn_volume_march"
+            store = (vol.data.data_ptr(), _lib.ptr(vol.occupancy if skip else None))
+        _lib.call(entry, R, *vol.resolution, vol.sh_degree, E, *store, *vol.lo,
                   *vol.step, o.data_ptr(), d.data_ptr(), tn.data_ptr(), tf.data_ptr(), step, t_min,
                   *[_lib.ptr(x) if R else None for x in (rgb, depth, acc, attrs, taps)], _lib.stream(dev))
     got = dict(rgb=rgb, depth=depth, acc=acc, taps=taps)
