@@ -7,6 +7,7 @@ FLAGS="$PN_EXTRA --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -W
 OBJS=""
 for f in pn_gemm pn_render pn_mlp pn_chain pn_wgrad pn_metrics pn_geometry pn_lighting pn_ibl pn_views pn_cameras pn_inpaint pn_data pn_objects pn_bvh pn_textures pn_atlas pn_relight pn_emitters pn_fusion pn_meshops pn_meshdist pn_winding pn_volume; do
   deps="$f.hip pn_common.h pn_tri.h pn_rays.h ../../include/panonerf_hip.h"
+  case $f in pn_lighting|pn_ibl|pn_objects|pn_emitters|pn_volume) deps="$deps pn_probes.h";; esac  # the probe view, SH basis and tile walk
   case $f in pn_emitters|pn_meshops) deps="$deps pn_unionfind.h";; esac  # one union-find loop for pixels and mesh vertices
   case $f in pn_meshdist|pn_winding) deps="$deps pn_mesh64.h";; esac  # fp64 vectors and the face loader of the mesh queries
   case $f in pn_chain|pn_wgrad) deps="$deps pn_chain.h";; esac  # the two kernel families of the fused MLP share it

@@ -26,7 +26,7 @@ struct Rot {
     float m[9];
 };
 
-constexpr float kPi = 3.14159265358979323846f;
+constexpr float kPi = PiOf<float>::value;
 
 // ---------------------------------------------------------------------------------------------------- ray generation
 // the pool of one panorama camera, row-major pixels
@@ -90,76 +90,6 @@ __device__ __forceinline__ bool dst_dir(int kind, int H, int W, const CamParams&
     return fisheye_dir(H, W, p.v[0], px, py, d) <= p.v[1];
 }
 
-// source direction -> continuous source pixel position; false where the source camera does not see it
-__device__ __forceinline__ bool src_pos(int kind, int H, int W, const CamParams& p, const float d[3], float& px, float& py,
-                                        int& face) {
-    face = 0;
-    if (kind == PN_CAM_PANO) {
-        const float phi = atan2f(hypotf(d[0], d[2]), d[1]), theta = atan2f(d[0], d[2]);
-        float t = -theta / (2.f * kPi);
-        t = t - floorf(t);
-        px = t * (float)W;
-        py = phi / kPi * (float)H;
-        return true;
-    }
-    if (kind == PN_CAM_PINHOLE) {
-        float q[3];
-        rotate3(p.v + 9, 3, d, q);
-        if (!(q[2] > 0.f)) return false;
-        px = q[0] / q[2];
-        py = q[1] / q[2];
-        return px >= 0.f && px <= (float)W && py >= 0.f && py <= (float)H;
-    }
-    if (kind == PN_CAM_FISHEYE) {
-        const float rho = hypotf(d[0], d[1]);
-        const float theta = atan2f(rho, -d[2]);
-        if (!(theta <= p.v[1])) return false;
-        const float r = p.v[0] * theta;
-        px = 0.5f * (float)W, py = 0.5f * (float)H;
-        if (rho > 0.f) {
-            px = px + r * d[0] / rho;
-            py = py - r * d[1] / rho;
-        }
-        return px >= 0.f && px <= (float)W && py >= 0.f && py <= (float)H;
-    }
-    return cube_pos(W, d, px, py, face);  // py within the face
-}
-
-struct Taps {
-    int o[4];  // pixel index (row * Ws + column) of the four taps: (y0, x0) (y0, x1) (y1, x0) (y1, x1)
-    float w[4];
-};
-
-// bilinear taps of the continuous position (px, py) (pixel centres at k + 1/2): columns wrap for a panorama and clamp
-// otherwise, rows clamp; a cube's taps clamp within its face
-__device__ __forceinline__ Taps make_taps(int kind, int H, int W, float px, float py, int face) {
-    const float gx = px - 0.5f, gy = py - 0.5f;
-    const float fx = floorf(gx), fy = floorf(gy);
-    const float wx = gx - fx, wy = gy - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const int rows = kind == PN_CAM_CUBE ? W : H;
-    if (kind == PN_CAM_PANO) {
-        x0 = ((x0 % W) + W) % W;
-        x1 = ((x1 % W) + W) % W;
-    } else {
-        x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0);
-        x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
-    }
-    y0 = y0 < 0 ? 0 : (y0 > rows - 1 ? rows - 1 : y0);
-    y1 = y1 < 0 ? 0 : (y1 > rows - 1 ? rows - 1 : y1);
-    const int top = kind == PN_CAM_CUBE ? face * W : 0;
-    Taps t;
-    t.o[0] = (top + y0) * W + x0;
-    t.o[1] = (top + y0) * W + x1;
-    t.o[2] = (top + y1) * W + x0;
-    t.o[3] = (top + y1) * W + x1;
-    t.w[0] = (1.f - wy) * (1.f - wx);
-    t.w[1] = (1.f - wy) * wx;
-    t.w[2] = wy * (1.f - wx);
-    t.w[3] = wy * wx;
-    return t;
-}
-
 __global__ __launch_bounds__(kThreads) void k_reproject(int N, int C, int sk, int Hs, int Ws, CamParams sp, int dk, int Hd,
                                                         int Wd, CamParams dp, Rot rot, int samples, float fill,
                                                         const float* image, int64_t ns, int64_t cs, int64_t ps, float* out,
@@ -184,8 +114,8 @@ __global__ __launch_bounds__(kThreads) void k_reproject(int N, int C, int sk, in
                     int face;
                     if (!dst_dir(dk, Hd, Wd, dp, px, py, d)) continue;
                     rotate3(rot.m, 3, d, e);
-                    if (!src_pos(sk, Hs, Ws, sp, e, qx, qy, face)) continue;
-                    const Taps t = make_taps(sk, Hs, Ws, qx, qy, face);
+                    if (!image_pos(sk, Hs, Ws, sp.v, e, qx, qy, face)) continue;
+                    const Taps<float, int> t = bilinear_taps<float, int>(sk, Hs, Ws, qx, qy, face);
                     ++valid;
 #pragma unroll
                     for (int c = 0; c < kChan; ++c) {
@@ -281,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void k_warp_splat(int64_t n_src, int sk, 
         if (!(rho > 0.f && rho < INFINITY)) continue;
         float qx, qy;
         int face;
-        if (!src_pos(dk, Hd, Wd, dp, e, qx, qy, face)) continue;
+        if (!image_pos(dk, Hd, Wd, dp.v, e, qx, qy, face)) continue;
         const int top = dk == PN_CAM_CUBE ? face * Wd : 0;
         // the landing pixel, kept inside the image (a position on the last border lands in the last pixel)
         int lx = (int)floorf(qx), ly = (int)floorf(qy);

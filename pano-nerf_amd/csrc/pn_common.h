@@ -7,6 +7,15 @@
 
 #define PN_WAVE 64
 
+// the sum of v over the 64 lanes of a wave, in every lane: the xor butterfly 32, 16, .. 1.  Every fp64 reduction of the
+// library ends a wave with it; who adds the per-wave partials, and in which order, is each kernel's own.
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, PN_WAVE);
+    return v;
+}
+
+constexpr double kPiD = 3.14159265358979323846;
+
 #define PN_CHECK_LAUNCH()                                  \
     do {                                                   \
         if (hipGetLastError() != hipSuccess) return PN_ERR_HIP; \

@@ -7,8 +7,9 @@
 // elements in index order, the lanes meet in a fixed butterfly) and every output is rounded once; the only atomics are
 // 32-bit integer atomicMin on the parent array of the union-find, whose RESULT (the smallest pixel index of a component)
 // does not depend on the order in which they land.  Two calls on the same inputs give the same bits.  Radiance is read in
-// place through (probe, channel, pixel) strides, as pn_lighting.hip and pn_shade read it.
+// place through the (probe, channel, pixel) strides of pn_probes.h's Probes.
 #include "pn_common.h"
+#include "pn_probes.h"
 #include "pn_unionfind.h"
 
 namespace {
@@ -17,22 +18,11 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PN_WAVE;
 constexpr int kThrThreads = 1024;  // the threshold's single workgroup per probe: as wide as a workgroup gets
 constexpr int kThrWaves = kThrThreads / PN_WAVE;
-constexpr double kPiD = 3.14159265358979323846;
-
-struct Probes {
-    const float* x;
-    int64_t probe_stride, cs, ps;  // element (p, c, pix) at x[p * probe_stride + c * cs + pix * ps]
-};
 
 // Y = ((double)R + G + B) / 3.0 of pixel pix of the probe at xp
 __device__ __forceinline__ double luminance(const float* xp, const Probes& pr, int64_t pix) {
     const double r = xp[pix * pr.ps], g = xp[pr.cs + pix * pr.ps], b = xp[2 * pr.cs + pix * pr.ps];
     return ((r + g) + b) / 3.0;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- 1. the default threshold: ratio exp(sum omega ln max(Y, 1e-6) / sum omega) over the pixels with finite Y ------------

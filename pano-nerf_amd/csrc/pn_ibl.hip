@@ -14,6 +14,7 @@
 // NaN, as in pn_probe_irradiance: a NaN radiance value makes that channel NaN for EVERY direction of its probe, those
 // facing away from the pixel included (weight 0 times NaN), and a NaN dot product stays NaN.
 #include "pn_common.h"
+#include "pn_probes.h"
 #include "pn_rays.h"
 #include <math.h>
 
@@ -25,11 +26,6 @@ constexpr int kSegTiles = 4;   // tiles one pixel segment covers at least
 constexpr int kMaxSegs = 64;   // pixel segments per probe at most
 constexpr int kMaxLut = 4096;  // largest table size and node count per axis
 
-struct Probes {
-    const float* x;
-    int64_t probe_stride, cs, ps;  // element (p, c, pix) at x[p * probe_stride + c * cs + pix * ps]
-};
-
 // pixel segments of a probe: `segs` runs of `tiles` LDS tiles each (the last one shorter), from the pixel count alone
 struct Split {
     int segs, tiles;
@@ -40,11 +36,6 @@ inline Split split_of(int64_t hw) {
     if (want > kMaxSegs) want = kMaxSegs;
     const int64_t per = (nt + want - 1) / want;
     return Split{(int)((nt + per - 1) / per), (int)per};
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // workgroup g = (p * nkb + b) * nseg + s: directions b * 256 .. b * 256 + 255 of probe p over the pixels of segment s.
@@ -144,43 +135,21 @@ __global__ __launch_bounds__(kThreads) void k_brdf_lut(int S, int n, float* out)
     }
 }
 
-// continuous coordinate u clamped to [0, top], top >= 1 (NaN passes through): cell index in [0, top - 1] and weight
-__device__ __forceinline__ void cell(double u, int top, int& i, double& t) {
-    if (u < 0.0) u = 0.0;
-    if (u > (double)top) u = (double)top;
-    if (isnan(u)) {
-        i = 0, t = u;
-        return;
-    }
-    i = (int)floor(u);
-    if (i > top - 1) i = top - 1;
-    t = u - (double)i;
-}
-
-// bilinear fetch of a cube strip [3, 6 S, S] at direction d: pn_reproject's lookup (cube_pos, the taps clamped within
-// the face, its order of the four products) in fp64; NaN for a zero or NaN direction
+// bilinear fetch of a cube strip [3, 6 S, S] at direction d: image_pos and bilinear_taps (pn_rays.h) in fp64, the taps
+// clamped within the face; NaN for a zero or NaN direction
 __device__ __forceinline__ void cube_fetch(const float* strip, int S, const double d[3], double out[3]) {
     double px, py;
     int face;
-    if (!cube_pos(S, d, px, py, face)) {
+    if (!image_pos<double>(PN_CAM_CUBE, 6 * S, S, nullptr, d, px, py, face)) {
         out[0] = out[1] = out[2] = (double)NAN;
         return;
     }
-    const double gx = px - 0.5, gy = py - 0.5;
-    const double fx = floor(gx), fy = floor(gy);
-    const double wx = gx - fx, wy = gy - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 > S - 1 ? S - 1 : x0);
-    x1 = x1 < 0 ? 0 : (x1 > S - 1 ? S - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 > S - 1 ? S - 1 : y0);
-    y1 = y1 < 0 ? 0 : (y1 > S - 1 ? S - 1 : y1);
-    const int64_t top = (int64_t)face * S;
-    const int64_t o00 = (top + y0) * S + x0, o01 = (top + y0) * S + x1, o10 = (top + y1) * S + x0, o11 = (top + y1) * S + x1;
-    const double w00 = (1.0 - wy) * (1.0 - wx), w01 = (1.0 - wy) * wx, w10 = wy * (1.0 - wx), w11 = wy * wx;
+    const Taps<double, int64_t> t = bilinear_taps<double, int64_t>(PN_CAM_CUBE, 6 * S, S, px, py, face);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float* ch = strip + (int64_t)c * 6 * S * S;
-        out[c] = ((w00 * (double)ch[o00] + w01 * (double)ch[o01]) + w10 * (double)ch[o10]) + w11 * (double)ch[o11];
+        out[c] = ((t.w[0] * (double)ch[t.o[0]] + t.w[1] * (double)ch[t.o[1]]) + t.w[2] * (double)ch[t.o[2]]) +
+                 t.w[3] * (double)ch[t.o[3]];
     }
 }
 
@@ -213,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void k_ibl_shade(int64_t R, IblMaps m, co
     // specular light: the two levels around lambda
     int l0;
     double f;
-    cell(rough * (double)(m.levels - 1), m.levels - 1, l0, f);
+    clamped_cell(rough * (double)(m.levels - 1), m.levels - 1, l0, f);
     const float* lv = m.spec;
     for (int l = 0; l < l0; ++l) lv += (int64_t)18 * (m.size >> l) * (m.size >> l);
     double a[3], b[3], E[3];
@@ -224,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void k_ibl_shade(int64_t R, IblMaps m, co
     int xi, yi;
     double tx, ty;
     const int S = m.lut_size;
-    cell(NoV * (double)S - 0.5, S - 1, xi, tx);
-    cell(rough * (double)S - 0.5, S - 1, yi, ty);
+    clamped_cell(NoV * (double)S - 0.5, S - 1, xi, tx);
+    clamped_cell(rough * (double)S - 0.5, S - 1, yi, ty);
     const float* t00 = m.lut + ((int64_t)yi * S + xi) * 2;
     const float* t10 = t00 + (int64_t)S * 2;
     const double w00 = (1.0 - ty) * (1.0 - tx), w01 = (1.0 - ty) * tx, w10 = ty * (1.0 - tx), w11 = ty * tx;

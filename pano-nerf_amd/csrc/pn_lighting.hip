@@ -9,6 +9,7 @@
 // Radiance is read in place through (probe, channel, pixel) strides, so [P, 3, H, W] views of [P, H, W, 3] buffers
 // need no copy.
 #include "pn_common.h"
+#include "pn_probes.h"
 #include <math.h>
 
 namespace {
@@ -25,34 +26,6 @@ inline int sh_blocks(int64_t hw) {
     return (int)(b < kMaxShBlocks ? b : kMaxShBlocks);
 }
 
-struct Probes {
-    const float* x;
-    int64_t probe_stride, cs, ps;  // element (p, c, pix) at x[p * probe_stride + c * cs + pix * ps]
-};
-
-// real SH basis up to l = 2 at direction (x, y, z), order (0,0) (1,-1) (1,0) (1,1) (2,-2) (2,-1) (2,0) (2,1) (2,2)
-__device__ __forceinline__ void sh_basis(double x, double y, double z, double (&Y)[9]) {
-    const double c0 = 0.28209479177387814;  // 1 / (2 sqrt(pi))
-    const double c1 = 0.48860251190291992;  // sqrt(3 / (4 pi))
-    const double c2 = 1.0925484305920792;   // sqrt(15 / pi) / 2
-    const double c3 = 0.31539156525252005;  // sqrt(5 / pi) / 4
-    const double c4 = 0.54627421529603959;  // sqrt(15 / pi) / 4
-    Y[0] = c0;
-    Y[1] = c1 * y;
-    Y[2] = c1 * z;
-    Y[3] = c1 * x;
-    Y[4] = c2 * (x * y);
-    Y[5] = c2 * (y * z);
-    Y[6] = c3 * (3.0 * (z * z) - 1.0);
-    Y[7] = c2 * (x * z);
-    Y[8] = c4 * (x * x - y * y);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // workgroup g = p * nb + b: partial SH sums of probe p over the pixels b, b + nb, ... (in blocks of kThreads):
 // part[g * 27 + k * 3 + c] = sum L_c(pix) Y_k(dir_pix) omega_pix
 __global__ __launch_bounds__(kThreads) void k_probe_sh(int64_t HW, int nb, Probes pr, const float* dirs,
@@ -65,7 +38,7 @@ __global__ __launch_bounds__(kThreads) void k_probe_sh(int64_t HW, int nb, Probe
     for (int q = 0; q < kShQ; ++q) acc[q] = 0.0;
     for (int64_t pix = (int64_t)b * kThreads + threadIdx.x; pix < HW; pix += (int64_t)nb * kThreads) {
         double Y[9];
-        sh_basis(dirs[pix * 3], dirs[pix * 3 + 1], dirs[pix * 3 + 2], Y);
+        sh_basis<2>(dirs[pix * 3], dirs[pix * 3 + 1], dirs[pix * 3 + 2], Y);
         const double w = omega[pix];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -154,16 +127,7 @@ struct Volume {
 // continuous grid coordinate of x on axis a, clamped to [0, n - 1] (NaN passes through): cell index and weight
 __device__ __forceinline__ void axis_cell(const Volume& v, int a, double x, int& i, double& t) {
     double u = v.d[a] != 0.f ? (x - (double)v.o[a]) / (double)v.d[a] : 0.0;
-    const double top = (double)(v.n[a] - 1);
-    if (u < 0.0) u = 0.0;
-    if (u > top) u = top;
-    if (isnan(u)) {
-        i = 0, t = u;
-        return;
-    }
-    i = (int)floor(u);
-    if (i > v.n[a] - 2) i = v.n[a] - 2;
-    t = u - (double)i;
+    clamped_cell(u, v.n[a] - 1, i, t);  // top >= 1: pn_sh_volume_irradiance refuses an axis of fewer than 2 vertices
 }
 
 // E(n) = sum_lm A_l L_lm Y_lm(n), L_lm interpolated trilinearly from the 8 vertices around the clamped point
@@ -188,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_sh_volume_irradiance(int64_t M, Vo
         for (int q = 0; q < kShQ; ++q) L[q] += w * (double)s[q];
     }
     double Y[9];
-    sh_basis(normals[m * 3], normals[m * 3 + 1], normals[m * 3 + 2], Y);
+    sh_basis<2>(normals[m * 3], normals[m * 3 + 1], normals[m * 3 + 2], Y);
     const double A[9] = {M_PI, 2.0 * M_PI / 3.0, 2.0 * M_PI / 3.0, 2.0 * M_PI / 3.0, M_PI / 4.0, M_PI / 4.0,
                          M_PI / 4.0, M_PI / 4.0, M_PI / 4.0};
 #pragma unroll

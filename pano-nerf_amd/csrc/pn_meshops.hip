@@ -18,11 +18,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PN_WAVE;
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the three corners of face f, or false where one is outside [0, V)
 __device__ __forceinline__ bool corners(const int32_t* faces, int64_t f, int64_t V, int32_t& a, int32_t& b, int32_t& c) {
     a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];

@@ -40,11 +40,6 @@ __device__ __forceinline__ double pixel_weight(int i, int H, int W) {
     return sin((i + 0.5) * M_PI / H) * sin(M_PI / (2.0 * H)) / W;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // sum v[] over the workgroup (fixed butterfly, then the four waves in order) and store it at dst[0..NQ)
 template <int NQ>
 __device__ __forceinline__ void block_store(double (&v)[NQ], double* dst) {

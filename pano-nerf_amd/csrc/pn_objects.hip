@@ -9,6 +9,7 @@
 // with -ffp-contract=off), the same function for primary and shadow rays.  Every sum is fp64 in pixel order, without
 // atomics: two calls on the same inputs give the same bits, whatever the number of rows per launch.
 #include "pn_common.h"
+#include "pn_probes.h"
 #include "pn_tri.h"
 #include <math.h>
 
@@ -17,11 +18,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTile = 256;  // probe pixels staged per LDS tile
 constexpr int kMaxProbes = PN_OBJ_MAX_PROBES;
-
-struct Probes {
-    const float* x;
-    int64_t probe_stride, cs, ps;  // element (k, c, pix) at x[k * probe_stride + c * cs + pix * ps]
-};
 
 // row f of tris [F, 12]: v0, 0, e1 = v1 - v0, 0, e2 = v2 - v0, 0.  A face with an index outside [0, V) becomes the
 // all-zero triangle, which no ray hits (det == 0).

@@ -1,7 +1,9 @@
 // pn_rays.h — one ray of any camera: what every ray generator of the library (pn_cameras.hip: the panorama pool
 // generator and the batch samplers of all camera kinds) is built from, so that all of them give the same bits.
 // A pool row (camera * H W + pixel) is decoded once (decode_row), the camera builds the pixel's RayRow, store_ray writes
-// the eight Rays fields.  Every expression keeps its parenthesisation: the library builds with -ffp-contract=off.
+// the eight Rays fields.  Further down, the way back: image_pos (direction -> image position of any central camera) and
+// bilinear_taps, templated over fp32 / fp64 for pn_cameras.hip and pn_ibl.hip; pn_fusion.hip and pn_relight.hip restate them.
+// Every expression keeps its parenthesisation: the library builds with -ffp-contract=off.
 #pragma once
 #include "pn_common.h"
 
@@ -112,11 +114,29 @@ __device__ __forceinline__ void cube_dir(int S, float px, float py, float d[3]) 
     }
 }
 
+// math functions and pi by the type of the operands: what lets one template serve fp32 and fp64
+__device__ __forceinline__ float atan2_t(float y, float x) { return atan2f(y, x); }
+__device__ __forceinline__ double atan2_t(double y, double x) { return atan2(y, x); }
+__device__ __forceinline__ float hypot_t(float x, float y) { return hypotf(x, y); }
+__device__ __forceinline__ double hypot_t(double x, double y) { return hypot(x, y); }
+__device__ __forceinline__ float floor_t(float x) { return floorf(x); }
+__device__ __forceinline__ double floor_t(double x) { return floor(x); }
+__device__ __forceinline__ float abs_t(float x) { return fabsf(x); }
+__device__ __forceinline__ double abs_t(double x) { return fabs(x); }
+template <class T>
+struct PiOf;  // pi as T: the fp32 constant is its own literal, not a rounded kPiD
+template <>
+struct PiOf<float> {
+    static constexpr float value = 3.14159265358979323846f;
+};
+template <>
+struct PiOf<double> {
+    static constexpr double value = kPiD;
+};
+
 // the inverse: direction d -> the strip's face and the continuous position (px, py) within that face of a cube of size
 // S.  The major axis picks the face, ties to the earlier face of +x -x +y -y +z -z; false for a zero or NaN direction.
 // pn_reproject looks up in fp32, the IBL evaluation (pn_ibl.hip) in fp64: one definition, the same faces.
-__device__ __forceinline__ float abs_t(float x) { return fabsf(x); }
-__device__ __forceinline__ double abs_t(double x) { return fabs(x); }
 template <class T>
 __device__ __forceinline__ bool cube_pos(int S, const T d[3], T& px, T& py, int& face) {
     const T ax = abs_t(d[0]), ay = abs_t(d[1]), az = abs_t(d[2]);
@@ -161,6 +181,90 @@ __device__ __forceinline__ void normalize3(float d[3]) {
     const float n = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) d[k] = d[k] / n;
+}
+
+// ------------------------------------------------------------------------------------------------- direction -> pixel
+// The inverse projections and the bilinear tap rule of include/panonerf_hip.h, once, over T = float (pn_reproject, the
+// warps) and T = double (the cube maps of pn_ibl; TSDF fusion and pn_relight keep a written-out copy): the same trees
+// in either precision, the math functions picked by overload.
+// camera-space direction d -> the continuous image position (px, py) of a camera of `kind` (centres at k + 1/2) and, for
+// a cube, the face, with py counted within it; false where the camera does not see d.  Of the camera's params PINHOLE
+// reads cam2pix at [9, 18), FISHEYE f and theta_max at [0] and [1], the others nothing (params may be null).
+// A caller whose kind is a compile-time constant keeps that kind's projection only.
+template <class T>
+__device__ __forceinline__ bool image_pos(int kind, int H, int W, const float* params, const T d[3], T& px, T& py, int& face) {
+    constexpr T pi = PiOf<T>::value;
+    face = 0;
+    if (kind == PN_CAM_PANO) {
+        const T phi = atan2_t(hypot_t(d[0], d[2]), d[1]), theta = atan2_t(d[0], d[2]);
+        T t = -theta / ((T)2 * pi);
+        t = t - floor_t(t);
+        px = t * (T)W;
+        py = phi / pi * (T)H;
+        return true;
+    }
+    if (kind == PN_CAM_PINHOLE) {
+        T q[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            q[k] = ((T)params[9 + 3 * k] * d[0] + (T)params[10 + 3 * k] * d[1]) + (T)params[11 + 3 * k] * d[2];
+        if (!(q[2] > (T)0)) return false;
+        px = q[0] / q[2];
+        py = q[1] / q[2];
+        return px >= (T)0 && px <= (T)W && py >= (T)0 && py <= (T)H;
+    }
+    if (kind == PN_CAM_FISHEYE) {
+        const T rho = hypot_t(d[0], d[1]);
+        const T theta = atan2_t(rho, -d[2]);
+        if (!(theta <= (T)params[1])) return false;
+        const T r = (T)params[0] * theta;
+        px = (T)0.5 * (T)W, py = (T)0.5 * (T)H;
+        if (rho > (T)0) {  // the axis itself lands on the centre
+            px = px + r * d[0] / rho;
+            py = py - r * d[1] / rho;
+        }
+        return px >= (T)0 && px <= (T)W && py >= (T)0 && py <= (T)H;
+    }
+    return cube_pos<T>(W, d, px, py, face);
+}
+
+// the four bilinear taps of a continuous position: pixel index (row * W + column, of index type I) and weight of
+// (y0, x0) (y0, x1) (y1, x0) (y1, x1); every caller adds the products as ((w0 c0 + w1 c1) + w2 c2) + w3 c3
+template <class T, class I>
+struct Taps {
+    I o[4];
+    T w[4];
+};
+
+// taps of image_pos' (px, py, face): columns wrap for a panorama and clamp otherwise, rows clamp; a cube's taps clamp
+// within its face.  The indices are computed in I throughout.
+template <class T, class I>
+__device__ __forceinline__ Taps<T, I> bilinear_taps(int kind, int H, int W, T px, T py, int face) {
+    const T gx = px - (T)0.5, gy = py - (T)0.5;
+    const T fx = floor_t(gx), fy = floor_t(gy);
+    const T wx = gx - fx, wy = gy - fy;
+    I x0 = (I)fx, y0 = (I)fy, x1 = x0 + 1, y1 = y0 + 1;
+    const int rows = kind == PN_CAM_CUBE ? W : H;
+    if (kind == PN_CAM_PANO) {
+        x0 = ((x0 % W) + W) % W;
+        x1 = ((x1 % W) + W) % W;
+    } else {
+        x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0);
+        x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
+    }
+    y0 = y0 < 0 ? 0 : (y0 > rows - 1 ? rows - 1 : y0);
+    y1 = y1 < 0 ? 0 : (y1 > rows - 1 ? rows - 1 : y1);
+    const I top = kind == PN_CAM_CUBE ? (I)face * W : 0;
+    Taps<T, I> t;
+    t.o[0] = (top + y0) * W + x0;
+    t.o[1] = (top + y0) * W + x1;
+    t.o[2] = (top + y1) * W + x0;
+    t.o[3] = (top + y1) * W + x1;
+    t.w[0] = ((T)1 - wy) * ((T)1 - wx);
+    t.w[1] = ((T)1 - wy) * wx;
+    t.w[2] = wy * ((T)1 - wx);
+    t.w[3] = wy * wx;
+    return t;
 }
 
 // ------------------------------------------------------------------------------------------------------------ cameras

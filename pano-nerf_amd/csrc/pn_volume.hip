@@ -21,6 +21,7 @@
 // questions, "is this cell's brick present" and "corner q, channel ch, as fp64", and carries nothing across samples.
 // k_volume_pack / k_volume_unpack move a volume between the two layouts.
 #include "pn_common.h"
+#include "pn_probes.h"  // sh_basis
 
 namespace {
 
@@ -225,22 +226,7 @@ __global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs<Store> a) {
         const int n = (int)nd;
         const double stepw = dt * len;
         double Y[K];
-        {
-            const double x = d[0] / len, y = d[1] / len, z = d[2] / len;
-            Y[0] = PN_SH_C0;
-            if (kDeg >= 1) {
-                Y[1] = PN_SH_C1 * y;
-                Y[2] = PN_SH_C1 * z;
-                Y[3] = PN_SH_C1 * x;
-            }
-            if (kDeg >= 2) {
-                Y[4] = PN_SH_C2 * (x * y);
-                Y[5] = PN_SH_C2 * (y * z);
-                Y[6] = PN_SH_C3 * (3.0 * (z * z) - 1.0);
-                Y[7] = PN_SH_C2 * (x * z);
-                Y[8] = PN_SH_C4 * (x * x - y * y);
-            }
-        }
+        sh_basis<kDeg>(d[0] / len, d[1] / len, d[2] / len, Y);
         // the grid coordinate of axis x at lattice point kk: THE sampling formula, also what every jump is checked with
         auto coord = [&](int x, int kk) -> double {
             const double t = tn + ((double)kk + 0.5) * dt;
