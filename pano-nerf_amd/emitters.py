@@ -28,11 +28,10 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .cameras import pano_camera
 from .geometry import _model_device
 from .lighting import _cuda, _probe_view, _table
-from .rays import CameraRig
 from .relight import PointLight
 
 _FIELDS = ("pixels", "omega", "flux", "lum_flux", "direction", "peak", "peak_index", "spread", "angular_radius", "distance")
@@ -67,29 +66,19 @@ def probe_rgbd(model, positions, height=64, width=128, near=0.0, far=10.0, chunk
     """(probes [P, 3, H, W], distance [P, H, W]) fp32 from ONE pass of the model: bit for bit lighting.light_probes and
     relight.shadow_maps(kind="pano") of the same arguments - they run the same rig and keep the fine level's radiance and
     its distance respectively.  probes is a view of a contiguous [P, H, W, 3] buffer, as light_probes returns it."""
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must be a [P, 3] tensor; got {getattr(positions, 'shape', type(positions))}")
+    P = views._probe_positions(positions)
     camera = pano_camera(height, width)
     H, W = camera.h, camera.w
     dev = _cuda(positions)
     if _model_device(model) != dev:
         raise RuntimeError(f"positions are on {dev}, the model on {_model_device(model)}")
-    chunk = int(chunk_rays)
-    if chunk <= 0:
-        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
-    P, HW = int(positions.shape[0]), H * W
-    rgb = torch.empty(P * HW, 3, dtype=torch.float32, device=dev)
-    dist = torch.empty(P * HW, dtype=torch.float32, device=dev)
+    chunk = views._chunk_rays(chunk_rays)
+    rgb = torch.empty(P * H * W, 3, dtype=torch.float32, device=dev)
+    dist = torch.empty(P * H * W, 1, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
-        c2ws[:, :3, 3] = positions.detach().to(torch.float32)
-        rig = CameraRig(camera, c2ws, dev)
-        for first in range(0, P * HW, chunk):
-            n = min(chunk, P * HW - first)
-            idx = torch.arange(first, first + n, dtype=torch.int64, device=dev)
-            outs, _ = model._run(rig.sample(idx, near, far)[0], None, False, False, False, False, False)
-            rgb[first:first + n].copy_(outs[2])
-            dist[first:first + n].copy_(outs[3].reshape(n))
+        rig = views._probe_rig(positions, camera, dev)
+        views._render_rows(model, rig, 0, P * H * W, None, False, False, near, far, chunk,
+                           {"fine_rgb": rgb, "fine_dep": dist}, streams=1)
     return rgb.view(P, H, W, 3).permute(0, 3, 1, 2), dist.view(P, H, W)
 
 
@@ -267,7 +256,6 @@ def residual_probes(probes, labels, distance=None, grow=0):
     hole filler, with the emitter pixels as the holes.  grow dilates the removed set by that many pixels first
     (8-neighbourhood, columns wrapped; plain torch on the device), to take a lamp's halo with it.  Pixels that stay keep
     their bits.  A residual probe goes through ibl.bake_ibl / ibl.save_ibl unchanged."""
-    from . import views
     x, _, _, _, P, H, W = _probe_view(probes)
     lab = _labels(labels, None, P, H, W, x.device)
     g = int(grow)

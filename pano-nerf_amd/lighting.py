@@ -25,10 +25,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .geometry import _model_device, _placement, _resolution, grid_points
 from .cameras import PanoCamera
-from .rays import CameraRig, Rays
 from .render import _Field, _light_gather, _planes_of
 
 IrradianceVolume = collections.namedtuple("IrradianceVolume", ["sh", "lo", "step"])
@@ -96,13 +95,7 @@ def _probe_view(probes):
         raise ValueError("probes holds no probe")
     _size(H, W)
     _cuda(probes)
-    x = probes.detach()
-    if x.dtype != torch.float32:
-        x = x.to(torch.float32)
-    sp, sc, sh, sw = x.stride()
-    if sh != W * sw:  # rows of a probe are not evenly spaced pixels: read a copy
-        x = x.contiguous()
-        sp, sc, sh, sw = x.stride()
+    x, (sp, sc, _, sw) = views._image_view(probes)
     return x, sp, sc, sw, P, H, W
 
 
@@ -124,26 +117,16 @@ def light_probes(model, positions, height=32, width=64, near=0.0, far=10.0, chun
     identity-rotation equirectangular camera at the position (the rays generate_pano_rays gives, bit for bit).  Only
     the two levels run: no density-gradient sweep, no light gather.  The result is a view of a contiguous
     [P, H, W, 3] buffer."""
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must be a [P, 3] tensor; got {getattr(positions, 'shape', type(positions))}")
+    P = views._probe_positions(positions)
     H, W = _size(height, width)
     dev = _cuda(positions)
     if _model_device(model) != dev:
         raise RuntimeError(f"positions are on {dev}, the model on {_model_device(model)}")
-    chunk = int(chunk_rays)
-    if chunk <= 0:
-        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
-    P, HW = int(positions.shape[0]), H * W
-    out = torch.empty(P * HW, 3, dtype=torch.float32, device=dev)
+    chunk = views._chunk_rays(chunk_rays)
+    out = torch.empty(P * H * W, 3, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
-        c2ws[:, :3, 3] = positions.detach().to(torch.float32)
-        rig = CameraRig(PanoCamera(H, W), c2ws, dev)
-        for first in range(0, P * HW, chunk):
-            n = min(chunk, P * HW - first)
-            idx = torch.arange(first, first + n, dtype=torch.int64, device=dev)
-            outs, _ = model._run(rig.sample(idx, near, far)[0], None, False, False, False, False, False)
-            out[first:first + n].copy_(outs[2])
+        rig = views._probe_rig(positions, PanoCamera(H, W), dev)
+        views._render_rows(model, rig, 0, P * H * W, None, False, False, near, far, chunk, {"fine_rgb": out}, streams=1)
     return out.view(P, H, W, 3).permute(0, 3, 1, 2)
 
 
@@ -241,8 +224,6 @@ def field_irradiance(model, points, normals, env_rays, chunk_points=None):
     return out
 
 
-
-
 def irradiance_volume(model, bounds, resolution, height=16, width=32, near=0.0, far=10.0, chunk_rays=32768):
     """IrradianceVolume(sh [nx, ny, nz, 9, 3], lo, step): light_probes at the vertices of a grid placed as
     geometry.density_grid places it (bounds = inclusive corner vertices, resolution = int or 3 ints, each >= 2), each
@@ -288,7 +269,6 @@ def probes_to_cubemaps(probes, size, samples=4):
     """[P, 3, 6 size, size] fp32: each [3, H, W] probe as a cube map (a vertical strip of the faces +x, -x, +y, -y, +z,
     -z in the lookup convention engines use; views.cubemap_camera), every texel the mean of samples x samples bilinear
     fetches: views.reproject(probes, pano_camera(H, W), cubemap_camera(size), samples=samples)[0]."""
-    from . import views
     _probe_view(probes)
     H, W = int(probes.shape[2]), int(probes.shape[3])
     return views.reproject(probes, views.pano_camera(H, W), views.cubemap_camera(size), samples=samples)[0]

@@ -53,7 +53,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .geometry import Mesh, _model_device
 from .lighting import _probe_view, _table, light_probes
 
@@ -667,13 +667,11 @@ def hit_attributes(obj, origins, directions, t, face, bary, scene_dep=None, prob
 
 def _frame_rays(camera, c2w, near, far, dev):
     """(origins, directions [H W, 3], cone radii [H W, 1]) of the rays render_view renders for this camera and pose."""
-    from . import views
     rays = views.generate_camera_rays(camera, c2w, near, far, dev)
     return rays.origins, rays.directions, rays.radii
 
 
 def _insert(model, camera, c2w, obj, pos, probes, shadow_probe, shadow_bias, near, far, chunk_rays, accel=None):
-    from . import views
     dev = _model_device(model)
     H, W = camera.h, camera.w
     R = H * W
@@ -743,7 +741,6 @@ def insert_object(model, camera, c2w, obj, probe_positions=None, probe_size=(32,
     normalised inverse distances to their positions.  It is exactly light_probes -> trace_mesh -> hit_attributes ->
     shade / shadow_ratio(hit_attributes' scene_points, scene_nor) -> the composite, all public.  accel (None, "bvh" or a
     MeshBVH of the object) goes to trace_mesh and shadow_ratio; "bvh" is obj.bvh(), built once and kept on the object."""
-    from . import views
     _check_accel(accel)
     camera, dev, _ = views._setup(model, camera, chunk_rays)
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
@@ -758,7 +755,6 @@ def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32,
     rgb, "mask" = the mask as 0 / 255, "depth" = to_frame of depth.  The probes are rendered once, not per frame: the
     object does not move, and neither is its BVH (accel as in insert_object: one build for all frames).  With out_dir the
     frames go to out_dir/<kind>/<i:05d>.png and the returned dict is empty."""
-    from . import io_exr, views
     _check_accel(accel)
     camera, dev, _ = views._setup(model, camera, chunk_rays)
     kinds = tuple(kinds)
@@ -766,26 +762,17 @@ def insert_path(model, camera, poses, obj, probe_positions=None, probe_size=(32,
     if bad or not kinds:
         raise ValueError(f"kinds must be a non-empty subset of ['depth', 'ldr', 'mask']; got {kinds!r}")
     c2ws = views._c2w_stack(poses)
-    n, H, W = c2ws.shape[0], camera.h, camera.w
+    H, W = camera.h, camera.w
     pos, probes, sprobe = _lights(model, obj, probe_positions, probe_size, shadows, shadow_probe, near, far, chunk_rays)
     accel = obj.bvh() if accel == "bvh" else accel  # one MeshBVH for every frame
-    frames = {}
-    if out_dir is None:
-        frames = {k: torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev) for k in kinds}
-    else:
-        for k in kinds:
-            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
-    for i in range(n):
+    sink = views._FrameSink(kinds, c2ws.shape[0], H, W, dev, out_dir)
+    for i in range(sink.n):
         out = _insert(model, camera, c2ws[i], obj, pos, probes, sprobe, shadow_bias, near, far, chunk_rays, accel)
         for k in kinds:
             if k == "ldr":
-                frame = views.to_frame(out["rgb"], "ldr", exposure=exposure)
+                sink.put(k, i, views.to_frame(out["rgb"], "ldr", exposure=exposure))
             elif k == "depth":
-                frame = views.to_frame(out["depth"], "depth", near, far)
+                sink.put(k, i, views.to_frame(out["depth"], "depth", near, far))
             else:
-                frame = (out["mask"][0, 0] * 255.0).to(torch.uint8)[..., None].expand(H, W, 3)
-            if out_dir is None:
-                frames[k][i].copy_(frame)
-            else:
-                io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.contiguous().cpu().numpy())
-    return frames
+                sink.put(k, i, (out["mask"][0, 0] * 255.0).to(torch.uint8)[..., None].expand(H, W, 3))
+    return sink.frames

@@ -20,12 +20,11 @@ scene's radiance units times length^2 - a light of intensity I at distance r fac
 and the surface shows albedo / pi of it.  ``ambient`` scales the whole captured image.  The bias defaults are
 conventions chosen on an analytic room (tests/_relight_ref.py), not measurements of a trained scene."""
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, views
 from .cameras import _c2w_stack, _camera, cubemap_camera, pano_camera
 from .geometry import _model_device
 from .rays import CameraRig
@@ -215,9 +214,7 @@ def shadow_maps(model, lights_or_positions, height=64, width=128, kind="pano", n
         raise ValueError(f"kind must be one of {sorted(_MAP_KINDS)}; got {kind!r}")
     camera = cubemap_camera(width) if kind == "cube" else pano_camera(height, width)
     H, W = camera.h, camera.w
-    chunk = int(chunk_rays)
-    if chunk <= 0:
-        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
+    chunk = views._chunk_rays(chunk_rays)
     dev = _model_device(model)
     if dev.type != "cuda":
         raise RuntimeError("pano_nerf_amd.relight runs on a HIP device only (the model is on %s); there is no CPU "
@@ -236,19 +233,13 @@ def shadow_maps(model, lights_or_positions, height=64, width=128, kind="pano", n
         if positions.device != dev:
             raise RuntimeError(f"positions are on {positions.device}, the model on {dev}")
         positions = positions.detach().to(torch.float32)
-    P, HW = int(positions.shape[0]), H * W
-    out = torch.empty(P * HW, dtype=torch.float32, device=dev)
+    P = int(positions.shape[0])
+    out = torch.empty(P * H * W, 1, dtype=torch.float32, device=dev)
     if P == 0:
         return out.view(0, H, W)
     with torch.no_grad(), torch.cuda.device(dev):
-        c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
-        c2ws[:, :3, 3] = positions
-        rig = CameraRig(camera, c2ws, dev)
-        for first in range(0, P * HW, chunk):
-            n = min(chunk, P * HW - first)
-            idx = torch.arange(first, first + n, dtype=torch.int64, device=dev)
-            outs, _ = model._run(rig.sample(idx, near, far)[0], None, False, False, False, False, False)
-            out[first:first + n].copy_(outs[3].reshape(n))
+        rig = views._probe_rig(positions, camera, dev)
+        views._render_rows(model, rig, 0, P * H * W, None, False, False, near, far, chunk, {"fine_dep": out}, streams=1)
     return out.view(P, H, W)
 
 
@@ -373,7 +364,6 @@ def relight_view(model, camera, c2w, lights, env_rays=None, base="fine_rgb", map
     dict plus "relit_rgb", "direct" [1, 3, H, W] and "visibility" [1, L, H, W].  base: "fine_rgb" relights the rendered
     radiance, "surface_rgb" the Lambertian re-rendering.  map_size = (height, width) of the maps (a cube takes width);
     **kw goes to relight (ambient, normal_offset, bias_abs, bias_rel, bias_slope, pcf)."""
-    from . import views
     if base not in _BASES:
         raise ValueError(f"base must be one of {_BASES}; got {base!r}")
     _params(map_kind, *(kw.get(n, d) for n, d in (("ambient", 1.0), ("normal_offset", 0.02), ("bias_abs", 0.01),
@@ -395,7 +385,6 @@ def relight_path(model, camera, poses, lights, env_rays=None, base="fine_rgb", m
     render_path makes them: "ldr" uint8 [n, H, W, 3] = to_frame(relit_rgb, "ldr", exposure=exposure), "hdr" fp32
     [n, H, W, 3] = relit_rgb itself, "direct" uint8 = to_frame(direct, "ldr", exposure=exposure).  With out_dir, frames go
     to out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr) as they complete and the returned dict is empty."""
-    from . import io_exr, views
     kinds = tuple(kinds)
     bad = [k for k in kinds if k not in _PATH_KINDS]
     if bad or not kinds:
@@ -406,27 +395,15 @@ def relight_path(model, camera, poses, lights, env_rays=None, base="fine_rgb", m
     lights = _lights(lights)
     L = len(lights)
     dev = _model_device(model)
-    n, H, W = c2ws.shape[0], camera.h, camera.w
-    frames = {}
     if maps is None and L:
         maps = shadow_maps(model, lights, h, w, map_kind, near, far, chunk_rays)
-    if out_dir is None:
-        frames = {k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev) for k in kinds}
-    else:
-        for k in kinds:
-            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    sink = views._FrameSink(kinds, c2ws.shape[0], camera.h, camera.w, dev, out_dir)
     lt = _light_tensor(lights, dev)  # uploaded once for every frame
-    for i in range(n):
+    for i in range(sink.n):
         v = relight_view(model, camera, c2ws[i], lt, env_rays, base, maps, (h, w), map_kind, near, far, chunk_rays, **kw)
         for k in kinds:
             if k == "hdr":
-                frame = v["relit_rgb"][0].permute(1, 2, 0)
+                sink.put(k, i, v["relit_rgb"][0].permute(1, 2, 0))
             else:
-                frame = views.to_frame(v["relit_rgb" if k == "ldr" else "direct"], "ldr", exposure=exposure)
-            if out_dir is None:
-                frames[k][i].copy_(frame)
-            elif k == "hdr":
-                io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.contiguous().cpu().numpy())
-            else:
-                io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
-    return frames
+                sink.put(k, i, views.to_frame(v["relit_rgb" if k == "ldr" else "direct"], "ldr", exposure=exposure))
+    return sink.frames

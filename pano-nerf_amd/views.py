@@ -38,7 +38,11 @@ tensors raise, there is no host fallback.  Cameras (``cameras.py``, re-exported 
                                                 prefers the background
 
 Conventions (pixel directions, radii, frame bytes, the cube-map table, the inverse projections) are stated in
-include/panonerf_hip.h.
+include/panonerf_hip.h.  The host-side conventions of every path and probe renderer of the package live here too
+(DESIGN.md 6r): _FrameSink (frames in memory or as files), _put_groups (whole frames per group of rays), _render_rows (the
+one loop from a rig's rows to the field), _probe_rig (identity-rotation cameras at positions), _in_circle (the fisheye
+mask) and _image_view (an image argument read through its strides); lighting, relight, emitters, objects and volume
+import them.
 """
 import math
 import os
@@ -46,7 +50,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, io_exr
 from .geometry import _model_device
 from .cameras import (PinholeCamera, PanoCamera, CubeCamera, FisheyeCamera, StereoPanoCamera, perspective_camera,  # noqa
                       pano_camera, cubemap_camera, fisheye_camera, stereo_pano_camera, camera_mask, cube_faces,
@@ -67,7 +71,7 @@ _SURF = ("albedo", "surface", "shading")
 _PATH_KINDS = {"ldr": ("rgb", "fine_rgb", "ldr"), "ldr_surf": ("surface", "surface_rgb", "ldr"),
                "depth": ("depth", "fine_dep", "depth"), "normal": ("normal", "fine_nor", "normal"),
                "albedo": ("albedo", "albedo", "albedo"), "hdr": ("rgb", "fine_rgb", None)}
-_PATH_GROUP_RAYS = 1 << 22  # rays rendered per group of frames in render_path (~220 MB of outputs at most)
+_PATH_GROUP_RAYS = 1 << 22  # rays per group of frames in _put_groups (~220 MB of render_path outputs at most)
 
 
 def generate_camera_rays(camera, c2w, near=0.0, far=10.0, device="cuda"):
@@ -235,6 +239,18 @@ def _lut(dev):
     return _LUTS[key]
 
 
+def _image_view(image):
+    """(x, strides): image ([.., H, W], any dtype) as fp32, read in place where its rows are evenly spaced pixels
+    (stride(-2) = W stride(-1): contiguous buffers and the permuted views of [.., H, W, C] buffers alike) and as a
+    contiguous copy otherwise.  The kernels take the strides that are left; torch has no negative strides to refuse."""
+    x = image.detach()
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    if x.stride(-2) != x.shape[-1] * x.stride(-1):
+        x = x.contiguous()
+    return x, x.stride()
+
+
 def to_frame(image, kind, near=None, far=None, exposure=0.0):
     """uint8 [H, W, 3] device tensor: the bytes the reference's validation writes for one [1, C, H, W] render_image
     output (systems/panonerf_system.py:77-131 through save_results, utils/vis.py:25-41), read in place through its strides.
@@ -266,13 +282,7 @@ def to_frame(image, kind, near=None, far=None, exposure=0.0):
             raise ValueError("a depth frame needs near and far")
         near_f, range_f = float(near), float(far - near)  # far - near in double, rounded once (as Python does upstream)
     dev = image.device
-    x = image.detach()[0]
-    if x.dtype != torch.float32:
-        x = x.to(torch.float32)
-    cs, sh, sw = x.stride()
-    if sh != W * sw:  # rows are not evenly spaced pixels: read a copy
-        x = x.contiguous()
-        cs, sh, sw = x.stride()
+    x, (cs, _, sw) = _image_view(image[0])
     out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
         work = torch.empty(2, dtype=torch.float32, device=dev) if kind == "depth" else None
@@ -297,10 +307,19 @@ def _flags(model, outputs, env_rays):
     return surf, surf or "normal" in outputs
 
 
+def _in_circle(camera, rays, rows):
+    """rows (name -> [n, C]) with 0 in every channel outside a fisheye's image circle; any other camera's as they are"""
+    if not isinstance(camera, FisheyeCamera):
+        return rows
+    seen = rays.lossmult > 0
+    return {k: torch.where(seen, v, 0.0) for k, v in rows.items()}
+
+
 def _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, chunk, bufs, streams=2):
-    """Render rays [first, first + count) of the (frame, pixel) index space into bufs[name][0:count].  The chunks are
-    dealt to `streams` HIP streams with the weight packs built once and frozen, as render_image deals them (the same
-    kernels on the same rays: the same bits)."""
+    """Render rays [first, first + count) of the (frame, pixel) index space into bufs[name][0:count]: the one loop that
+    feeds a rig's rows to the field for inference.  The chunks are dealt to `streams` HIP streams with the weight packs
+    built once and frozen, as render_image deals them (the same kernels on the same rays: the same bits); with
+    streams=1 everything runs on the current stream and nothing is packed ahead or frozen (the probes)."""
     dev = rig.device
     starts = list(range(0, count, chunk))
     # (with surface outputs the cached fp32 env rays are made on this stream, before the other lanes fork from it)
@@ -314,13 +333,16 @@ def _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, c
                 comp0, dist0, comp1, dist1, _, normal, albedo, surface, _, shading = outs
                 got = dict(coarse_rgb=comp0, fine_rgb=comp1, coarse_dep=dist0, fine_dep=dist1, fine_nor=normal,
                            albedo=albedo, surface_rgb=surface, shading=shading)
-                if isinstance(rig.camera, FisheyeCamera):  # 0 in every channel outside the image circle
-                    seen = rays.lossmult > 0
-                    for name, buf in bufs.items():
-                        buf[s:s + n].copy_(torch.where(seen, got[name].reshape(n, -1), 0.0))
-                    continue
+                rows = _in_circle(rig.camera, rays, {name: got[name].reshape(n, -1) for name in bufs})
                 for name, buf in bufs.items():
-                    buf[s:s + n].copy_(got[name].reshape(n, -1))
+                    buf[s:s + n].copy_(rows[name])
+
+
+def _chunk_rays(chunk_rays):
+    chunk = int(chunk_rays)
+    if chunk <= 0:
+        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
+    return chunk
 
 
 def _setup(model, camera, chunk_rays):
@@ -329,13 +351,68 @@ def _setup(model, camera, chunk_rays):
     if dev.type != "cuda":
         raise RuntimeError("pano_nerf_amd.views renders on a HIP device only (the model is on %s); there is no CPU "
                            "fallback" % dev)
-    chunk = int(chunk_rays)
-    if chunk <= 0:
-        raise ValueError(f"chunk_rays must be positive; got {chunk_rays!r}")
-    return camera, dev, chunk
+    return camera, dev, _chunk_rays(chunk_rays)
+
+
+def _probe_positions(positions):
+    """P of a [P, 3] positions tensor"""
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
+        raise ValueError(f"positions must be a [P, 3] tensor; got {getattr(positions, 'shape', type(positions))}")
+    return int(positions.shape[0])
+
+
+def _probe_rig(positions, camera, dev):
+    """The CameraRig of P identity-rotation cameras at positions ([P, 3] tensor on dev): what every probe, shadow map and
+    volume probe is seen from, so that their pixel (p, i, j) looks along the same ray."""
+    P = int(positions.shape[0])
+    c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
+    c2ws[:, :3, 3] = positions.detach().to(torch.float32)
+    return CameraRig(camera, c2ws, dev)
 
 
 _WIDTH = dict(coarse_rgb=3, fine_rgb=3, coarse_dep=1, fine_dep=1, fine_nor=3, albedo=3, surface_rgb=3, shading=3)
+
+
+class _FrameSink:
+    """Where a path renderer's frames go: `frames`, kind -> [n, H, W, 3] tensors on `dev` (uint8; fp32 for "hdr"), or with
+    out_dir the files out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr), written as the frames arrive, and `frames` stays {}."""
+
+    def __init__(self, kinds, n, h, w, dev, out_dir=None):
+        self.kinds, self.n, self.h, self.w, self.out_dir, self.frames = tuple(kinds), n, h, w, out_dir, {}
+        for k in self.kinds:
+            if out_dir is None:
+                self.frames[k] = torch.empty(n, h, w, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev)
+            else:
+                os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+
+    def put(self, kind, i, frame):
+        """frame [H, W, 3] (any strides) is frame i of `kind`"""
+        if self.out_dir is None:
+            self.frames[kind][i].copy_(frame)
+            return
+        pixels = frame.contiguous().cpu().numpy()
+        if kind == "hdr":
+            io_exr.write_exr(os.path.join(self.out_dir, kind, f"{i:05d}.exr"), pixels)
+        else:
+            io_exr.write_png(os.path.join(self.out_dir, kind, f"{i:05d}.png"), pixels)
+
+
+def _put_groups(sink, rows, table, near, far, exposure):
+    """Fill `sink` from rows over the (frame, pixel) index space, a group of whole frames (at most _PATH_GROUP_RAYS rays)
+    at a time: rows(first_ray, count) -> name -> [count, C] fp32; table: kind -> (row name, to_frame kind, or None for
+    the rows themselves).  exposure applies to "ldr" frames only."""
+    HW = sink.h * sink.w
+    group = max(1, min(sink.n, _PATH_GROUP_RAYS // HW))
+    for g0 in range(0, sink.n, group):
+        nf = min(group, sink.n - g0)
+        got = rows(g0 * HW, nf * HW)
+        for f in range(nf):
+            for k in sink.kinds:
+                name, kind = table[k]
+                frame = got[name][f * HW:(f + 1) * HW].view(sink.h, sink.w, -1)
+                if kind is not None:
+                    frame = to_frame(frame[None].permute(0, 3, 1, 2), kind, near, far, exposure if kind == "ldr" else 0.0)
+                sink.put(k, g0 + f, frame)
 
 
 def render_view(model, camera, c2w, env_rays=None, outputs=("rgb", "depth", "normal"), near=0.0, far=10.0,
@@ -366,7 +443,6 @@ def render_path(model, camera, poses, env_rays=None, kinds=("ldr", "depth", "nor
     "hdr" is fine_rgb itself as fp32 [n, H, W, 3].  Rays are indexed over (frame, pixel), so small frames share full
     chunks.  With out_dir, frames go to out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr) as they complete and the returned
     dict is empty."""
-    from . import io_exr
     camera, dev, chunk = _setup(model, camera, chunk_rays)
     kinds = tuple(kinds)
     bad = [k for k in kinds if k not in _PATH_KINDS]
@@ -375,38 +451,18 @@ def render_path(model, camera, poses, env_rays=None, kinds=("ldr", "depth", "nor
     outputs = tuple(dict.fromkeys(_PATH_KINDS[k][0] for k in kinds))
     surf, normals = _flags(model, outputs, env_rays)
     c2ws = _c2w_stack(poses)
-    n, H, W = c2ws.shape[0], camera.h, camera.w
-    HW = H * W
     names = tuple(dict.fromkeys(_PATH_KINDS[k][1] for k in kinds))
-    group = max(1, min(n, _PATH_GROUP_RAYS // HW))
-    frames = {}
-    if out_dir is None:
-        frames = {k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev) for k in kinds}
-    else:
-        for k in kinds:
-            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    sink = _FrameSink(kinds, c2ws.shape[0], camera.h, camera.w, dev, out_dir)
+
+    def rows(first, count):
+        bufs = {k: torch.empty(count, _WIDTH[k], dtype=torch.float32, device=dev) for k in names}
+        _render_rows(model, rig, first, count, env_rays, surf, normals, near, far, chunk, bufs)
+        return bufs
+
     with torch.no_grad(), torch.cuda.device(dev):
         rig = CameraRig(camera, c2ws, dev)
-        for g0 in range(0, n, group):
-            nf = min(group, n - g0)
-            bufs = {k: torch.empty(nf * HW, _WIDTH[k], dtype=torch.float32, device=dev) for k in names}
-            _render_rows(model, rig, g0 * HW, nf * HW, env_rays, surf, normals, near, far, chunk, bufs)
-            for f in range(nf):
-                i = g0 + f
-                for k in kinds:
-                    src = bufs[_PATH_KINDS[k][1]][f * HW:(f + 1) * HW].view(H, W, -1)
-                    if k == "hdr":
-                        frame = src
-                    else:
-                        frame = to_frame(src[None].permute(0, 3, 1, 2), _PATH_KINDS[k][2], near, far,
-                                         exposure if _PATH_KINDS[k][2] == "ldr" else 0.0)
-                    if out_dir is None:
-                        frames[k][i].copy_(frame)
-                    elif k == "hdr":
-                        io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
-                    else:
-                        io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
-    return frames
+        _put_groups(sink, rows, {k: _PATH_KINDS[k][1:] for k in kinds}, near, far, exposure)
+    return sink.frames
 
 
 def render_stereo_pano(model, height, width, ipd, c2w, env_rays=None, outputs=("rgb", "depth", "normal"), near=0.0,
@@ -454,12 +510,7 @@ def reproject(image, src_camera, dst_camera, rotation=None, samples=1, fill=0.0)
     if x.device.type != "cuda":
         raise RuntimeError("pano_nerf_amd.views runs on a HIP device only (the image is on %s); there is no CPU fallback"
                            % x.device)
-    if x.dtype != torch.float32:
-        x = x.to(torch.float32)
-    sn, sc, sh, sw = x.stride()
-    if sh != Ws * sw or min(sn, sc, sw) < 0:  # rows are not evenly spaced pixels: read a copy
-        x = x.contiguous()
-        sn, sc, sh, sw = x.stride()
+    x, (sn, sc, _, sw) = _image_view(x)
     dev = x.device
     (sk, sp), (dk, dp) = _kind_params(src), _kind_params(dst)
     r32 = np.ascontiguousarray(rot.astype(np.float32).reshape(9))
@@ -553,12 +604,7 @@ def warp_view(image, depth, src_camera, src_c2w, dst_camera, dst_c2w, max_splat=
     z = z.to(torch.float32).contiguous()
     C, sn, sc, sw = 0, 0, 0, 0
     if x is not None:
-        if x.dtype != torch.float32:
-            x = x.to(torch.float32)
-        sn, sc, sh, sw = x.stride()
-        if sh != Ws * sw or min(sn, sc, sw) < 0:  # rows are not evenly spaced pixels: read a copy
-            x = x.contiguous()
-            sn, sc, sh, sw = x.stride()
+        x, (sn, sc, _, sw) = _image_view(x)
         C = int(x.shape[1])
     (sk, sp), (dk, dp) = _kind_params(src), _kind_params(dst)
     Hd, Wd = dst.h, dst.w
@@ -754,7 +800,6 @@ def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("l
     the warped (or blended) frames go through fill_holes with the camera before to_frame, so their depth frames are
     complete; "coverage" still reports what the warp covered, i.e. which pixels were invented.  depth_ratio and levels
     are blend_warps' and fill_holes'.  Rendered poses are never touched; with both off these are the calls described above."""
-    from . import io_exr
     camera, dev, _ = _setup(model, camera, chunk_rays)
     kinds = tuple(kinds)
     bad = [k for k in kinds if k not in _WARPED_KINDS]
@@ -766,29 +811,18 @@ def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("l
     c2ws = _c2w_stack(poses)
     n, H, W = c2ws.shape[0], camera.h, camera.w
     keys = sorted(set(range(0, n, step)) | {n - 1})
-    frames = {"coverage": torch.empty(n, H, W, dtype=torch.float32, device=dev)}
-    if out_dir is None:
-        frames.update({k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev)
-                       for k in kinds})
-    else:
-        for k in kinds:
-            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    coverage = torch.empty(n, H, W, dtype=torch.float32, device=dev)
+    sink = _FrameSink(kinds, n, H, W, dev, out_dir)
 
     def emit(i, rgb, dep, cov):
-        frames["coverage"][i].copy_(cov)
+        coverage[i].copy_(cov)
         for k in kinds:
             if k == "hdr":
-                frame = rgb[0].permute(1, 2, 0)
+                sink.put(k, i, rgb[0].permute(1, 2, 0))
             elif k == "ldr":
-                frame = to_frame(rgb, "ldr", near, far, exposure)
+                sink.put(k, i, to_frame(rgb, "ldr", near, far, exposure))
             else:
-                frame = to_frame(dep, "depth", near, far)
-            if out_dir is None:
-                frames[k][i].copy_(frame)
-            elif k == "hdr":
-                io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
-            else:
-                io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
+                sink.put(k, i, to_frame(dep, "depth", near, far))
 
     def render(i):
         v = render_view(model, camera, c2ws[i], env_rays, ("rgb", "depth"), near, far, chunk_rays)
@@ -815,4 +849,4 @@ def render_path_warped(model, camera, poses, key_every, env_rays=None, kinds=("l
                 emit(i, w["image"][f:f + 1], w["depth"][f:f + 1], w["coverage"][f])
         emit(b, *cur, one)
         prev = cur
-    return frames
+    return {"coverage": coverage, **sink.frames}

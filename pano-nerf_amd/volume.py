@@ -44,8 +44,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from .cameras import FisheyeCamera, PanoCamera, _c2w_stack, _camera
+from . import _lib, views
+from .cameras import PanoCamera, _c2w_stack, _camera
 from .geometry import _model_device, _placement, _resolution, _variance, density_grid, grid_points, query_field
 from .rays import CameraRig
 
@@ -60,7 +60,6 @@ _CORE = ("rgb", "depth", "acc")
 _TAPS = "taps"  # march_rays' diagnostic output
 _PATH_KINDS = {"ldr": ("rgb", "ldr"), "hdr": ("rgb", None), "depth": ("depth", "depth"), "albedo": ("albedo", "albedo"),
                "normal": ("normal", "normal")}
-_PATH_GROUP_RAYS = 1 << 22  # rays marched per group of frames in render_volume_path
 
 
 def fibonacci_directions(count):
@@ -664,10 +663,7 @@ def _march_rig(vol, rig, first, count, near, far, step, t_min, skip, outputs):
     idx = torch.arange(first, first + count, dtype=torch.int64, device=vol.device)
     rays, _ = rig.sample(idx, near, far)
     got = march_rays(vol, rays.origins, rays.directions, rays.near, rays.far, step, t_min, skip, outputs)
-    if isinstance(rig.camera, FisheyeCamera):
-        seen = rays.lossmult > 0
-        got = {k: torch.where(seen, v, 0.0) for k, v in got.items()}
-    return got
+    return views._in_circle(rig.camera, rays, got)
 
 
 def render_volume(vol, camera, c2w, outputs=("rgb", "depth"), near=0.0, far=10.0, step=None, t_min=1e-3, skip=True):
@@ -689,8 +685,6 @@ def render_volume_path(vol, camera, poses, kinds=("ldr", "depth"), near=0.0, far
     with near / far, albedo and normal <- the volume's attributes of those names); "hdr" is rgb itself as fp32
     [n, H, W, 3].  Rays are indexed over (frame, pixel), one march_rays call per group of frames.  With out_dir, frames go
     to out_dir/<kind>/<i:05d>.png (hdr/<i:05d>.exr) and the returned dict is empty."""
-    from . import io_exr
-    from .views import to_frame
     camera = _camera(camera)
     kinds = tuple(kinds)
     bad = [k for k in kinds if k not in _PATH_KINDS or _PATH_KINDS[k][0] not in _CORE + vol.attribute_names]
@@ -699,45 +693,20 @@ def render_volume_path(vol, camera, poses, kinds=("ldr", "depth"), near=0.0, far
         raise ValueError(f"kinds must be a non-empty subset of {have} for this volume; got {kinds!r}")
     outputs = tuple(dict.fromkeys(_PATH_KINDS[k][0] for k in kinds))
     c2ws = _c2w_stack(poses)
-    n, H, W = c2ws.shape[0], camera.h, camera.w
-    HW = H * W
-    group = max(1, min(n, _PATH_GROUP_RAYS // HW))
     dev = vol.device
-    frames = {}
-    if out_dir is None:
-        frames = {k: torch.empty(n, H, W, 3, dtype=torch.float32 if k == "hdr" else torch.uint8, device=dev) for k in kinds}
-    else:
-        for k in kinds:
-            os.makedirs(os.path.join(out_dir, k), exist_ok=True)
+    sink = views._FrameSink(kinds, c2ws.shape[0], camera.h, camera.w, dev, out_dir)
     with torch.no_grad(), torch.cuda.device(dev):
         rig = CameraRig(camera, c2ws, dev)
-        for g0 in range(0, n, group):
-            nf = min(group, n - g0)
-            got = _march_rig(vol, rig, g0 * HW, nf * HW, near, far, step, t_min, skip, outputs)
-            for f in range(nf):
-                i = g0 + f
-                for k in kinds:
-                    name, kind = _PATH_KINDS[k]
-                    src = got[name][f * HW:(f + 1) * HW].view(H, W, -1)
-                    if kind is None:
-                        frame = src
-                    else:
-                        frame = to_frame(src[None].permute(0, 3, 1, 2), kind, near, far, exposure if kind == "ldr" else 0.0)
-                    if out_dir is None:
-                        frames[k][i].copy_(frame)
-                    elif k == "hdr":
-                        io_exr.write_exr(os.path.join(out_dir, k, f"{i:05d}.exr"), frame.cpu().numpy())
-                    else:
-                        io_exr.write_png(os.path.join(out_dir, k, f"{i:05d}.png"), frame.cpu().numpy())
-    return frames
+        views._put_groups(sink, lambda first, count: _march_rig(vol, rig, first, count, near, far, step, t_min, skip, outputs),
+                          _PATH_KINDS, near, far, exposure)
+    return sink.frames
 
 
 def volume_probes(vol, positions, height=32, width=64, near=0.0, far=10.0, step=None, t_min=1e-3, skip=True):
     """HDR radiance [P, 3, H, W] seen from each of positions [P, 3]: the volume marched along the pixel directions of
     lighting.light_probes (an identity-rotation panorama camera at the position), all probes in one march_rays call.
     lighting.sh_project, irradiance, ibl.bake_ibl and emitters take the result as they take light_probes'."""
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must be a [P, 3] tensor; got {getattr(positions, 'shape', type(positions))}")
+    P = views._probe_positions(positions)
     if positions.device.type != "cuda":
         raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the positions are on %s); there is no CPU "
                            "fallback" % positions.device)
@@ -745,12 +714,9 @@ def volume_probes(vol, positions, height=32, width=64, near=0.0, far=10.0, step=
     if H < 2 or W < 2:
         raise ValueError(f"a probe needs height and width >= 2; got {height} x {width}")
     dev = vol.device
-    P = int(positions.shape[0])
     with torch.no_grad(), torch.cuda.device(dev):
-        c2ws = torch.eye(4, dtype=torch.float32, device=dev).repeat(P, 1, 1)
-        c2ws[:, :3, 3] = positions.detach().to(torch.float32)
+        rig = views._probe_rig(positions, PanoCamera(H, W), dev)
         if P == 0:
             return torch.empty(0, 3, H, W, dtype=torch.float32, device=dev)
-        rig = CameraRig(PanoCamera(H, W), c2ws, dev)
         rgb = _march_rig(vol, rig, 0, P * H * W, near, far, step, t_min, skip, ("rgb",))["rgb"]
     return rgb.view(P, H, W, 3).permute(0, 3, 1, 2)

@@ -134,3 +134,42 @@ def test_cpu_tensors_raise():
         views.to_frame(torch.zeros(1, 1, 4, 4), "depth", 0.0, 1.0)
     with pytest.raises(RuntimeError):
         views.generate_perspective_rays(views.perspective_camera(8, 8, focal=5.0), np.eye(4), device="cpu")
+
+
+def test_frame_sink_on_host_tensors(tmp_path):
+    """The frame sink of the path renderers with a CPU device (no library call is involved): in memory it holds what was
+    put, with out_dir the files decode to the same frames bit for bit and a permuted view writes its contiguous copy's
+    bytes."""
+    import os
+    from pano_nerf_amd import io_exr, views
+    n, H, W = 3, 2, 4
+    kinds = ("ldr", "depth", "hdr")
+    rng = np.random.default_rng(11)
+    want = {k: (torch.from_numpy(rng.standard_normal((n, H, W, 3)).astype(np.float32)) if k == "hdr" else
+                torch.from_numpy(rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8))) for k in kinds}
+    cpu = torch.device("cpu")
+    sink = views._FrameSink(kinds, n, H, W, cpu)
+    files = views._FrameSink(kinds, n, H, W, cpu, str(tmp_path / "a"))
+    views_only = views._FrameSink(kinds, n, H, W, cpu, str(tmp_path / "b"))
+    for i in range(n):
+        for k in kinds:
+            sink.put(k, i, want[k][i])
+            files.put(k, i, want[k][i])
+            chw = want[k][i].permute(2, 0, 1).contiguous()  # the same frame behind a [3, H, W] buffer
+            assert not chw.permute(1, 2, 0).is_contiguous()
+            views_only.put(k, i, chw.permute(1, 2, 0))
+    assert sorted(sink.frames) == sorted(kinds)
+    for k in kinds:
+        assert sink.frames[k].dtype == (torch.float32 if k == "hdr" else torch.uint8)
+        assert sink.frames[k].shape == (n, H, W, 3) and sink.frames[k].device == cpu
+        assert torch.equal(sink.frames[k].view(torch.uint8), want[k].view(torch.uint8)), k
+    assert files.frames == {} and views_only.frames == {}
+    for k in kinds:
+        ext = "exr" if k == "hdr" else "png"
+        names = [f"{i:05d}.{ext}" for i in range(n)]
+        assert sorted(os.listdir(tmp_path / "a" / k)) == names and sorted(os.listdir(tmp_path / "b" / k)) == names
+        for i, name in enumerate(names):
+            back = (io_exr.read_exr if k == "hdr" else io_exr.read_png)(str(tmp_path / "a" / k / name))
+            assert back.dtype == want[k].numpy().dtype and back.tobytes() == want[k][i].numpy().tobytes(), (k, i)
+            with open(tmp_path / "a" / k / name, "rb") as fa, open(tmp_path / "b" / k / name, "rb") as fb:
+                assert fa.read() == fb.read(), (k, i)
