@@ -782,7 +782,7 @@ int pn_object_composite(int64_t R, const uint8_t* mask, const float* object_rgb,
                         const float* scene_rgb, const float* scene_dep, const float* shadow, float* rgb, float* depth,
                         void* stream);
 
-/* ---- mesh tracing through a device-built BVH (built by pn_bvh.hip, walked by pn_tri.h's BvhFinder): opt-in ------------
+/* ---- mesh tracing through a device-built BVH (built by pn_bvh.hip, walked by pn_bvh_walk.h for pn_tri.h's BvhFinder): opt-in
  * The ray / triangle test is the one above (the same function, on the same tris rows).  A BVH skips triangles whose box
  * the ray misses, and the fp32 test above is not exact (it owns a band of PN_OBJ_EDGE_EPS outside each triangle and its t
  * is badly conditioned for grazing rays), so a BVH cannot promise the brute-force result for every input.  It promises a

@@ -10,6 +10,7 @@ for f in pn_gemm pn_render pn_mlp pn_chain pn_wgrad pn_metrics pn_geometry pn_li
   case $f in pn_lighting|pn_ibl|pn_objects|pn_emitters|pn_volume) deps="$deps pn_probes.h";; esac  # the probe view, SH basis and tile walk
   case $f in pn_emitters|pn_meshops) deps="$deps pn_unionfind.h";; esac  # one union-find loop for pixels and mesh vertices
   case $f in pn_meshdist|pn_winding) deps="$deps pn_mesh64.h";; esac  # fp64 vectors and the face loader of the mesh queries
+  case $f in pn_objects|pn_bvh|pn_meshdist|pn_winding) deps="$deps pn_bvh_walk.h";; esac  # the node row, the LDS stack and the ordered walk
   case $f in pn_chain|pn_wgrad) deps="$deps pn_chain.h";; esac  # the two kernel families of the fused MLP share it
   stale=0
   for d in $deps; do

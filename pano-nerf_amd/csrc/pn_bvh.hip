@@ -1,18 +1,17 @@
 // pn_bvh.hip — a linear BVH over a mesh's triangles, built on the device (gfx950): the opt-in fast path of virtual object
 // insertion.  The contract (padded triangle boxes, the node layout and the depth bound) is stated in
-// include/panonerf_hip.h; the walk is pn_tri.h's BvhFinder, under pn_objects.hip's tracer and shadow kernels.
+// include/panonerf_hip.h; pn_bvh_walk.h reads and walks the rows, under pn_objects.hip, pn_meshdist.hip and pn_winding.hip.
 //
 // Build: padded boxes -> 63-bit Morton keys -> (the caller's stable sort) -> Karras' radix tree, one thread per internal
 // node -> bottom-up refit, one thread per leaf.  One triangle per leaf; a node row carries both children's boxes, so one
 // 64-byte fetch tests both.
+#include "pn_bvh_walk.h"
 #include "pn_common.h"
-#include "pn_tri.h"
 #include <math.h>
 
 namespace {
 
 constexpr int kThreads = 256;
-using pn_tri::kDepth;
 
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -130,15 +129,6 @@ __global__ __launch_bounds__(kThreads) void k_bvh_tree(int64_t F, const int64_t*
     row[15] = 0;
 }
 
-// Words of a node row that another workgroup wrote in this launch are read and written with agent-scope accesses, which
-// go past the caches that are private to a compute unit or a die.
-__device__ __forceinline__ void put(float* p, float v) {
-    __hip_atomic_store((int*)p, __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float get(const float* p) {
-    return __int_as_float(__hip_atomic_load((const int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 // One thread per leaf (sorted position j) climbs towards the root carrying the box of what lies under it.  At a node it
 // writes its own side's box, fences and counts its arrival; the first to arrive stops, the second reads the other side,
 // takes the union (exact min / max) and goes on.  Each node's box words are written once, by the thread that came up that
@@ -151,18 +141,18 @@ __global__ __launch_bounds__(kThreads) void k_bvh_refit(int64_t F, const int64_t
     if (face < 0 || face >= F) return;  // not a permutation: nothing of this library's making
     float4 lo = tbox[face * 2], hi = tbox[face * 2 + 1];
     int32_t me = ~(int32_t)face, cur = leaf_parent[j];
-    for (int level = 0; level < kDepth && cur >= 0 && cur < F - 1; ++level) {
+    for (int level = 0; level < pn_bvh::kDepth && cur >= 0 && cur < F - 1; ++level) {
         float* row = nodes + (int64_t)cur * 16;
         const bool left = ((const int32_t*)row)[3] == me;  // written by k_bvh_tree, an earlier launch
         float* mine = row + (left ? 0 : 8);
         const float* other = row + (left ? 8 : 0);
-        put(mine, lo.x), put(mine + 1, lo.y), put(mine + 2, lo.z);
-        put(mine + 4, hi.x), put(mine + 5, hi.y), put(mine + 6, hi.z);
+        agent_put(mine, lo.x), agent_put(mine + 1, lo.y), agent_put(mine + 2, lo.z);
+        agent_put(mine + 4, hi.x), agent_put(mine + 5, hi.y), agent_put(mine + 6, hi.z);
         __threadfence();
         if (atomicAdd(counters + cur, 1) == 0) return;
         __threadfence();
-        lo.x = fminf(lo.x, get(other)), lo.y = fminf(lo.y, get(other + 1)), lo.z = fminf(lo.z, get(other + 2));
-        hi.x = fmaxf(hi.x, get(other + 4)), hi.y = fmaxf(hi.y, get(other + 5)), hi.z = fmaxf(hi.z, get(other + 6));
+        lo.x = fminf(lo.x, agent_get(other)), lo.y = fminf(lo.y, agent_get(other + 1)), lo.z = fminf(lo.z, agent_get(other + 2));
+        hi.x = fmaxf(hi.x, agent_get(other + 4)), hi.y = fmaxf(hi.y, agent_get(other + 5)), hi.z = fmaxf(hi.z, agent_get(other + 6));
         me = cur;
         cur = ((const int32_t*)row)[11];
     }
@@ -178,14 +168,12 @@ __global__ void k_bvh_single(const float4* tbox, float4* nodes) {
     nodes[3] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
 }
 
-bool faces_ok(int64_t F) { return F > 0 && F < ((int64_t)1 << 31); }
-
 }  // namespace
 
 extern "C" {
 
 int pn_bvh_boxes(int64_t F, int64_t V, const float* vertices, const int32_t* faces, float* tbox, void* stream) {
-    if (!faces_ok(F) || V < 0) return PN_ERR_BAD_SHAPE;
+    if (F <= 0 || !count_ok(F) || V < 0) return PN_ERR_BAD_SHAPE;
     if (!faces || !tbox || (V > 0 && !vertices)) return PN_ERR_NULL;
     hipLaunchKernelGGL(k_bvh_boxes, dim3(nblk(F, kThreads)), dim3(kThreads), 0, ST(stream), F, V, vertices, faces,
                        (float4*)tbox);
@@ -194,7 +182,7 @@ int pn_bvh_boxes(int64_t F, int64_t V, const float* vertices, const int32_t* fac
 }
 
 int pn_bvh_keys(int64_t F, const float* tbox, const float* scene_box, int64_t* keys, void* stream) {
-    if (!faces_ok(F)) return PN_ERR_BAD_SHAPE;
+    if (F <= 0 || !count_ok(F)) return PN_ERR_BAD_SHAPE;
     if (!tbox || !scene_box || !keys) return PN_ERR_NULL;
     hipLaunchKernelGGL(k_bvh_keys, dim3(nblk(F, kThreads)), dim3(kThreads), 0, ST(stream), F, (const float4*)tbox,
                        scene_box, keys);
@@ -204,7 +192,7 @@ int pn_bvh_keys(int64_t F, const float* tbox, const float* scene_box, int64_t* k
 
 int pn_bvh_tree(int64_t F, const int64_t* sorted_keys, const int64_t* order, const float* tbox, float* nodes,
                 int32_t* leaf_parent, int32_t* counters, void* stream) {
-    if (!faces_ok(F)) return PN_ERR_BAD_SHAPE;
+    if (F <= 0 || !count_ok(F)) return PN_ERR_BAD_SHAPE;
     if (!tbox || !nodes) return PN_ERR_NULL;
     if (F == 1) {
         hipLaunchKernelGGL(k_bvh_single, dim3(1), dim3(1), 0, ST(stream), (const float4*)tbox, (float4*)nodes);

@@ -14,6 +14,14 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// words that another workgroup wrote in this launch: agent-scope accesses go past the caches private to a compute unit or die
+template <class T>  // float (pn_bvh.hip's refit) and double (pn_winding.hip's moments)
+__device__ __forceinline__ void agent_put(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T>
+__device__ __forceinline__ T agent_get(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+static inline bool count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }  // what an int32 index reaches
+
 constexpr double kPiD = 3.14159265358979323846;
 
 #define PN_CHECK_LAUNCH()                                  \

@@ -9,14 +9,13 @@
 // flow (the brute-force finder holds barriers).  h.best comes in as max_distance^2 (or +inf) and h.face as -1.  A search
 // keeps (best, face) only; the kernel evaluates the winner once more for the closest point and its barycentrics, which
 // gives the same fp64 values as the evaluation that won.
+#include "pn_bvh_walk.h"
 #include "pn_common.h"
 #include "pn_mesh64.h"
-#include "pn_tri.h"
 #include <math.h>
 
 namespace {
 
-using pn_tri::kDepth;
 using pn_mesh64::P3;
 using pn_mesh64::sub3;
 using pn_mesh64::dot3;
@@ -114,14 +113,12 @@ __device__ __forceinline__ void offer(double d, int32_t f, Near& h) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- brute force
-// Every face in ascending index, staged through LDS in tiles of kTile corners (3 float4 each, .w of the first = valid:
-// 12 KB).  Ascending order makes the replacement rule a strict < (plus the first face that meets best exactly).
+// Every face in ascending index through pn_mesh64.h's tile.  Ascending order makes the replacement rule a strict < (plus
+// the first face that meets best exactly).
+static_assert(PN_MESHDIST_TILE == pn_mesh64::kTile, "BruteNear stages pn_mesh64.h's tile");
 struct BruteNear {
     static constexpr int kThreads = 256;
-    static constexpr int kTile = PN_MESHDIST_TILE;
-    struct Shared {
-        float4 tri[kTile * 3];
-    };
+    typedef float4 Shared[PN_MESHDIST_TILE * 3];
     int64_t F, V;
     const float* vertices;
     const int32_t* faces;
@@ -129,28 +126,18 @@ struct BruteNear {
 
     __device__ __forceinline__ BruteNear(int64_t F, int64_t V, const float* vertices, const int32_t* faces, const float4*,
                                          Shared& s)
-        : F(F), V(V), vertices(vertices), faces(faces), s_tri(s.tri) {}
+        : F(F), V(V), vertices(vertices), faces(faces), s_tri(s) {}
 
     __device__ __forceinline__ void find(bool ask, const P3 p, Near& h) {
-        for (int64_t base = 0; base < F; base += kTile) {
-            const int cnt = (int)((F - base) < kTile ? (F - base) : kTile);
-            __syncthreads();  // every reader of the previous tile is done
-            for (int i = threadIdx.x; i < cnt; i += kThreads) {
-                P3 a{0, 0, 0}, b{0, 0, 0}, c{0, 0, 0};
-                const bool ok = load_tri(base + i, V, vertices, faces, a, b, c);
-                s_tri[i * 3] = make_float4((float)a.x, (float)a.y, (float)a.z, ok ? 1.f : 0.f);
-                s_tri[i * 3 + 1] = make_float4((float)b.x, (float)b.y, (float)b.z, 0.f);
-                s_tri[i * 3 + 2] = make_float4((float)c.x, (float)c.y, (float)c.z, 0.f);
-            }
-            __syncthreads();
+        for (int64_t base = 0; base < F; base += PN_MESHDIST_TILE) {
+            const int cnt = (int)((F - base) < PN_MESHDIST_TILE ? (F - base) : PN_MESHDIST_TILE);
+            pn_mesh64::stage_tile<kThreads>(base, cnt, V, vertices, faces, s_tri);
             if (!ask) continue;
             for (int j = 0; j < cnt; ++j) {
-                const float4 a = s_tri[j * 3], b = s_tri[j * 3 + 1], c = s_tri[j * 3 + 2];
-                if (a.w == 0.f) continue;
-                P3 q;
+                P3 a, b, c, q;
                 double u, v;
-                const double d = point_tri(p, P3{a.x, a.y, a.z}, P3{b.x, b.y, b.z}, P3{c.x, c.y, c.z}, q, u, v);
-                offer(d, (int32_t)(base + j), h);
+                if (!pn_mesh64::tile_tri(s_tri, j, a, b, c)) continue;
+                offer(point_tri(p, a, b, c, q, u, v), (int32_t)(base + j), h);
             }
         }
     }
@@ -169,72 +156,46 @@ __device__ __forceinline__ double box_lb(const P3 p, float lx, float ly, float l
 }
 
 struct BvhNear {
-    static constexpr int kThreads = 64;  // one wave per workgroup: the [depth][thread] stack of pn_tri.h's BvhFinder
-    struct Shared {
-        int stack[kDepth * kThreads];
-    };
+    static constexpr int kThreads = 64;  // one wave per workgroup (the LDS stack is per thread)
+    using Shared = pn_bvh::Stack<kThreads>::Shared;
     int64_t F, V;
     const float* vertices;
     const int32_t* faces;
     const float4* nodes;
-    int* stack;
+    Shared& shared;
 
     __device__ __forceinline__ BvhNear(int64_t F, int64_t V, const float* vertices, const int32_t* faces,
                                        const float4* nodes, Shared& s)
-        : F(F), V(V), vertices(vertices), faces(faces), nodes(nodes), stack(s.stack + threadIdx.x) {}
+        : F(F), V(V), vertices(vertices), faces(faces), nodes(nodes), shared(s) {}
 
-    // leaf of face f whose padded box lies lb from p: the candidate rule, then the replacement rule
-    __device__ __forceinline__ void leaf(const P3 p, int32_t f, double lb, Near& h) const {
-        if (f < 0 || f >= F) return;  // PN_BVH_NONE, or a row this library did not write
-        P3 a, b, c, q;
-        if (!load_tri(f, V, vertices, faces, a, b, c)) return;
-        double u, v;
-        const double d = point_tri(p, a, b, c, q, u, v);
-        if (!(lb <= d)) return;
-        offer(d, f, h);
-    }
-
-    // From row 0.  A child is skipped only when its box is empty or lb > best (strict); the child with the smaller bound
-    // is entered first (the left one on a tie) and the other pushed.  Every internal node is entered at most once, so F
-    // iterations always suffice: the bound also ends the walk over a buffer that is not a tree.
-    __device__ __forceinline__ void walk(const P3 p, Near& h) const {
-        const int64_t rows = F > 1 ? F - 1 : 1;
-        int32_t cur = 0;
-        int sp = 0;
-        for (int64_t it = 0; it < F; ++it) {
-            const float4 a = nodes[(int64_t)cur * 4], b = nodes[(int64_t)cur * 4 + 1], c = nodes[(int64_t)cur * 4 + 2],
-                         e = nodes[(int64_t)cur * 4 + 3];
-            const int32_t lref = __float_as_int(a.w), rref = __float_as_int(b.w);
-            const double ll = box_lb(p, a.x, a.y, a.z, b.x, b.y, b.z), lr = box_lb(p, c.x, c.y, c.z, e.x, e.y, e.z);
-            bool hl = a.x <= b.x && !(ll > h.best);
-            bool hr = c.x <= e.x && !(lr > h.best);
-            if (hl && lref < 0) {
-                leaf(p, ~lref, ll, h);
-                hl = false;
-            }
-            if (hr && rref < 0) {
-                if (!(lr > h.best)) leaf(p, ~rref, lr, h);
-                hr = false;
-            }
-            hl = hl && lref < rows && !(ll > h.best);
-            hr = hr && rref < rows && !(lr > h.best);
-            if (hl && hr) {
-                const bool left_first = ll <= lr;
-                if (sp < kDepth) stack[sp++ * kThreads] = left_first ? rref : lref;  // sp < kDepth always: the depth bound
-                cur = left_first ? lref : rref;
-            } else if (hl) {
-                cur = lref;
-            } else if (hr) {
-                cur = rref;
-            } else {
-                if (sp == 0) return;
-                cur = stack[--sp * kThreads];
-            }
+    struct Query {  // pn_bvh::walk_ordered's, of one point
+        using Bound = double;  // lb
+        const BvhNear& m;
+        const P3 p;
+        Near& h;
+        __device__ __forceinline__ bool bound(float lx, float ly, float lz, float hx, float hy, float hz, double& lb) const {
+            lb = box_lb(p, lx, ly, lz, hx, hy, hz);
+            return lx <= hx;
         }
-    }
+        __device__ __forceinline__ bool beyond(double lb) const { return lb > h.best; }
+        __device__ __forceinline__ bool done() const { return false; }
+
+        // leaf of face f whose padded box lies lb from p: the candidate rule, then the replacement rule
+        __device__ __forceinline__ void leaf(int32_t f, double lb) {
+            if (f < 0 || f >= m.F) return;  // PN_BVH_NONE, or a row this library did not write
+            P3 a, b, c, q;
+            if (!load_tri(f, m.V, m.vertices, m.faces, a, b, c)) return;
+            double u, v;
+            const double d = point_tri(p, a, b, c, q, u, v);
+            if (lb <= d) offer(d, f, h);
+        }
+    };
 
     __device__ __forceinline__ void find(bool ask, const P3 p, Near& h) const {
-        if (ask) walk(p, h);
+        if (!ask) return;
+        pn_bvh::Stack<kThreads> stack(shared);
+        Query q{*this, p, h};
+        pn_bvh::walk_ordered(nodes, F, stack, q);
     }
 };
 
@@ -245,18 +206,12 @@ __global__ __launch_bounds__(Finder::kThreads) void k_closest(int64_t P, const f
                                                              int32_t* face_out, float* closest_out, float* bary_out) {
     __shared__ typename Finder::Shared s_find;
     const int64_t r = (int64_t)blockIdx.x * Finder::kThreads + threadIdx.x;
-    const bool live = r < P;
-    P3 p{0.0, 0.0, 0.0};
-    bool ask = false;
-    if (live) {
-        const float x = points[r * 3], y = points[r * 3 + 1], z = points[r * 3 + 2];
-        p = P3{(double)x, (double)y, (double)z};
-        ask = isfinite(x) && isfinite(y) && isfinite(z);
-    }
+    P3 p;
+    const bool ask = pn_mesh64::load_point(r, P, points, p);
     Near h{(double)max_distance * (double)max_distance, -1};
     Finder finder(F, V, vertices, faces, nodes, s_find);
     finder.find(ask, p, h);
-    if (!live) return;
+    if (r >= P) return;
     float d = INFINITY, qx = 0.f, qy = 0.f, qz = 0.f, bu = 0.f, bv = 0.f;
     if (h.face >= 0) {
         P3 a, b, c, q;
@@ -327,8 +282,6 @@ __global__ __launch_bounds__(kThreads) void k_sample(int64_t count, int64_t W, i
     face_out[i] = f;
     bary[i * 2] = bu, bary[i * 2 + 1] = bv;
 }
-
-bool count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }
 
 template <class Finder>
 int closest_point(int64_t P, const float* points, int64_t V, const float* vertices, int64_t F, const int32_t* faces,

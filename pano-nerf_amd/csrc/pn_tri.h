@@ -9,6 +9,7 @@
 // any: the first hit found ends the ray's search, and of h only face means anything.  kThreads is the workgroup size a
 // finder is written for.
 #pragma once
+#include "pn_bvh_walk.h"
 #include "pn_common.h"
 #include <math.h>
 
@@ -102,12 +103,8 @@ struct BruteFinder {
 };
 
 // ------------------------------------------------------------------------------------------------------------ BVH walk
-// The contract (the box test, the candidate rule, why the tree cannot matter, the node layout and the depth bound) is
-// stated in include/panonerf_hip.h.  One ray per thread, near child first, the far child pushed on a stack in LDS laid out
-// [depth][thread] - lane l always touches bank l % 32, whatever its depth, so a wave's accesses never conflict - sized by
-// the depth bound: 94 x 64 threads x 4 B = 24 064 B per workgroup, one wave.  No scratch.  Neighbouring threads ask about
-// neighbouring rays (or the same direction from neighbouring points), so a wave's walks stay close.
-constexpr int kDepth = PN_BVH_MAX_DEPTH;                // stack entries per thread
+// include/panonerf_hip.h states the contract; the walk and its stack are pn_bvh_walk.h's.  One ray per thread: neighbours
+// ask about neighbouring rays (or the same direction from neighbouring points), so a wave's walks stay close.
 constexpr float kShrink = 1.f - 4.76837158203125e-07f;  // 1 - 2^-21
 constexpr float kGrow = 1.f + 4.76837158203125e-07f;    // 1 + 2^-21
 
@@ -162,76 +159,48 @@ __device__ __forceinline__ bool box_pass(const Ray& r, float lx, float ly, float
 struct BvhFinder {
     static constexpr int kThreads = 64;  // one wave per workgroup (the LDS stack is per thread)
     static constexpr bool kNodes = true;
-    struct Shared {
-        int stack[kDepth * kThreads];
-    };
+    using Shared = pn_bvh::Stack<kThreads>::Shared;
     int64_t F;
     const float4 *tris, *nodes;
-    int* stack;  // this thread's column, stride kThreads
+    Shared& shared;
 
     __device__ __forceinline__ BvhFinder(int64_t F, const float4* tris, const float4* nodes, Shared& s)
-        : F(F), tris(tris), nodes(nodes), stack(s.stack + threadIdx.x) {}
+        : F(F), tris(tris), nodes(nodes), shared(s) {}
 
-    // leaf of face f, whose padded box the ray passes from tn on: the candidate rule, then the replacement rule
-    __device__ __forceinline__ void leaf(const Ray& r, int32_t f, float tn, Hit& h) const {
-        if (f < 0 || f >= F) return;  // PN_BVH_NONE, or a row this library did not write
-        float t, u, v;
-        if (!mt_hit(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, tris[(int64_t)f * 3], tris[(int64_t)f * 3 + 1],
-                    tris[(int64_t)f * 3 + 2], t, u, v))
-            return;
-        if (!(tn <= t)) return;
-        if (t < h.best || (t == h.best && h.face >= 0 && f < h.face)) h.best = t, h.face = f, h.u = u, h.v = v;
-    }
-
-    // Walks the tree from row 0.  A node is skipped only when the ray does not pass its box or tn > best; the near child
-    // is entered first and the far one pushed.  Every internal node is entered at most once, so F iterations always
-    // suffice: the bound also ends the walk over a buffer that is not a tree.
     template <bool kAny>
-    __device__ __forceinline__ void walk(const Ray& r, Hit& h) const {
-        const int64_t rows = F > 1 ? F - 1 : 1;
-        int32_t cur = 0;
-        int sp = 0;
-        for (int64_t it = 0; it < F; ++it) {
-            const float4 a = nodes[(int64_t)cur * 4], b = nodes[(int64_t)cur * 4 + 1], c = nodes[(int64_t)cur * 4 + 2],
-                         e = nodes[(int64_t)cur * 4 + 3];
-            const int32_t lref = __float_as_int(a.w), rref = __float_as_int(b.w);
-            float tl = 0.f, tr = 0.f;
-            bool hl = box_pass(r, a.x, a.y, a.z, b.x, b.y, b.z, tl) && !(tl > h.best);
-            bool hr = box_pass(r, c.x, c.y, c.z, e.x, e.y, e.z, tr) && !(tr > h.best);
-            if (hl && lref < 0) {
-                leaf(r, ~lref, tl, h);
-                hl = false;
-            }
-            if (hr && rref < 0) {
-                leaf(r, ~rref, tr, h);
-                hr = false;
-            }
-            if (kAny && h.face >= 0) return;
-            hl = hl && lref < rows && !(tl > h.best);
-            hr = hr && rref < rows && !(tr > h.best);
-            if (hl && hr) {
-                const bool left_first = tl <= tr;
-                if (sp < kDepth) stack[sp++ * kThreads] = left_first ? rref : lref;  // sp < kDepth always: the depth bound
-                cur = left_first ? lref : rref;
-            } else if (hl) {
-                cur = lref;
-            } else if (hr) {
-                cur = rref;
-            } else {
-                if (sp == 0) return;
-                cur = stack[--sp * kThreads];
-            }
+    struct Query {  // pn_bvh::walk_ordered's, of one ray
+        using Bound = float;  // tn
+        const BvhFinder& m;
+        const Ray& r;
+        Hit& h;
+        __device__ __forceinline__ bool bound(float lx, float ly, float lz, float hx, float hy, float hz, float& tn) const {
+            return box_pass(r, lx, ly, lz, hx, hy, hz, tn);
         }
-    }
+        __device__ __forceinline__ bool beyond(float tn) const { return tn > h.best; }
+        __device__ __forceinline__ bool done() const { return kAny && h.face >= 0; }
+
+        // leaf of face f, whose padded box the ray passes from tn on: the candidate rule, then the replacement rule
+        __device__ __forceinline__ void leaf(int32_t f, float tn) {
+            if (f < 0 || f >= m.F) return;  // PN_BVH_NONE, or a row this library did not write
+            const float4* tri = m.tris + (int64_t)f * 3;
+            float t, u, v;
+            if (!mt_hit(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, tri[0], tri[1], tri[2], t, u, v) || !(tn <= t)) return;
+            if (t < h.best || (t == h.best && h.face >= 0 && f < h.face)) h.best = t, h.face = f, h.u = u, h.v = v;
+        }
+    };
 
     __device__ __forceinline__ void find(bool ask, float ox, float oy, float oz, float dx, float dy, float dz, bool any,
                                          Hit& h) const {
         if (!ask) return;
+        pn_bvh::Stack<kThreads> stack(shared);
         const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
-        if (any)
-            walk<true>(r, h);
-        else
-            walk<false>(r, h);
+        if (any) {
+            Query<true> q{*this, r, h};
+            pn_bvh::walk_ordered(nodes, F, stack, q);
+        } else {
+            Query<false> q{*this, r, h};
+            pn_bvh::walk_ordered(nodes, F, stack, q);
+        }
     }
 };
 

@@ -3,14 +3,13 @@
 // and a pre-order walk of that tree that replaces far nodes by their dipole (Barnes-Hut).  The contract (the solid angle
 // operation for operation, the moments, the opening rule, the order of the sum) is stated in include/panonerf_hip.h,
 // section "winding number"; tests/_winding_ref.py restates it in numpy.
+#include "pn_bvh_walk.h"
 #include "pn_common.h"
 #include "pn_mesh64.h"
-#include "pn_tri.h"
 #include <math.h>
 
 namespace {
 
-using pn_tri::kDepth;
 using pn_mesh64::P3;
 using pn_mesh64::sub3;
 using pn_mesh64::dot3;
@@ -30,45 +29,28 @@ __device__ __forceinline__ double solid_angle(const P3 p, const P3 a, const P3 b
     return 2.0 * atan2(num, den);
 }
 
-// the point of thread r, and whether it is asked (every coordinate finite)
-__device__ __forceinline__ bool load_point(int64_t r, int64_t P, const float* points, P3& p) {
-    p = P3{0.0, 0.0, 0.0};
-    if (r >= P) return false;
-    const float x = points[r * 3], y = points[r * 3 + 1], z = points[r * 3 + 2];
-    p = P3{(double)x, (double)y, (double)z};
-    return isfinite(x) && isfinite(y) && isfinite(z);
-}
-
 __device__ __forceinline__ float finish(bool ask, double S) { return ask ? (float)(S / PN_WINDING_FOUR_PI) : NAN; }
 
 // ---------------------------------------------------------------------------------------------------------- brute force
-// Every face in ascending index, staged through LDS in tiles of kTile corners (3 float4 each, .w of the first = valid:
-// 12 KB), as pn_meshdist.hip's BruteNear; S takes the terms in that order.
+// Every face in ascending index through pn_mesh64.h's tile; S takes the terms in that order.
+static_assert(PN_WINDING_TILE == pn_mesh64::kTile, "k_winding stages pn_mesh64.h's tile");
 constexpr int kBruteThreads = 256;
-constexpr int kTile = PN_WINDING_TILE;
+using pn_mesh64::kTile;
 
 __global__ __launch_bounds__(kBruteThreads) void k_winding(int64_t P, const float* points, int64_t V, const float* vertices,
                                                           int64_t F, const int32_t* faces, float* winding) {
     __shared__ float4 s_tri[kTile * 3];
     const int64_t r = (int64_t)blockIdx.x * kBruteThreads + threadIdx.x;
     P3 p;
-    const bool ask = load_point(r, P, points, p);
+    const bool ask = pn_mesh64::load_point(r, P, points, p);
     double S = 0.0;
     for (int64_t base = 0; base < F; base += kTile) {
         const int cnt = (int)((F - base) < kTile ? (F - base) : kTile);
-        __syncthreads();  // every reader of the previous tile is done
-        for (int i = threadIdx.x; i < cnt; i += kBruteThreads) {
-            P3 a{0, 0, 0}, b{0, 0, 0}, c{0, 0, 0};
-            const bool ok = load_tri(base + i, V, vertices, faces, a, b, c);
-            s_tri[i * 3] = make_float4((float)a.x, (float)a.y, (float)a.z, ok ? 1.f : 0.f);
-            s_tri[i * 3 + 1] = make_float4((float)b.x, (float)b.y, (float)b.z, 0.f);
-            s_tri[i * 3 + 2] = make_float4((float)c.x, (float)c.y, (float)c.z, 0.f);
-        }
-        __syncthreads();
+        pn_mesh64::stage_tile<kBruteThreads>(base, cnt, V, vertices, faces, s_tri);
         if (!ask) continue;
         for (int j = 0; j < cnt; ++j) {
-            const float4 a = s_tri[j * 3], b = s_tri[j * 3 + 1], c = s_tri[j * 3 + 2];
-            if (a.w == 0.f) continue;
+            const float4 a = s_tri[j * 3], b = s_tri[j * 3 + 1], c = s_tri[j * 3 + 2];  // pn_mesh64::tile_tri, restated:
+            if (a.w == 0.f) continue;                                                   // through it the sum is 2.5 % slower
             S += solid_angle(p, P3{a.x, a.y, a.z}, P3{b.x, b.y, b.z}, P3{c.x, c.y, c.z});
         }
     }
@@ -76,15 +58,6 @@ __global__ __launch_bounds__(kBruteThreads) void k_winding(int64_t P, const floa
 }
 
 // -------------------------------------------------------------------------------------------------------------- moments
-// Words of a moments row that another workgroup wrote in this launch are read and written with agent-scope accesses, as
-// the box words of pn_bvh.hip's refit are.
-__device__ __forceinline__ void put(double* p, double v) {
-    __hip_atomic_store((long long*)p, __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double get(const double* p) {
-    return __longlong_as_double(__hip_atomic_load((const long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 struct Part {  // what a child hands to its parent: zero for a face that is not valid and for an empty node
     P3 g, N;
     double A;
@@ -105,9 +78,9 @@ __device__ __forceinline__ Part child_part(int32_t ref, int64_t F, int64_t V, co
         }
     } else if (ref < F - 1) {
         const double* m = moments + (int64_t)ref * 8;
-        q.g = P3{get(m), get(m + 1), get(m + 2)};
-        q.N = P3{get(m + 4), get(m + 5), get(m + 6)};
-        q.A = get(m + 7);
+        q.g = P3{agent_get(m), agent_get(m + 1), agent_get(m + 2)};
+        q.N = P3{agent_get(m + 4), agent_get(m + 5), agent_get(m + 6)};
+        q.A = agent_get(m + 7);
     }
     return q;
 }
@@ -122,7 +95,7 @@ __device__ __forceinline__ void node_row(int64_t i, int64_t F, int64_t V, const 
     const float hx = fmaxf(b.x, e.x), hy = fmaxf(b.y, e.y), hz = fmaxf(b.z, e.z);
     double* m = moments + i * 8;
     if (!(lx <= hx)) {  // the empty box: nothing valid below
-        for (int k = 0; k < 8; ++k) put(m + k, 0.0);
+        for (int k = 0; k < 8; ++k) agent_put(m + k, 0.0);
         return;
     }
     const P3 N = add3(l.N, r.N);
@@ -134,8 +107,8 @@ __device__ __forceinline__ void node_row(int64_t i, int64_t F, int64_t V, const 
         g = P3{((double)lx + (double)hx) * 0.5, ((double)ly + (double)hy) * 0.5, ((double)lz + (double)hz) * 0.5};
     const double ex = fmax(g.x - (double)lx, (double)hx - g.x), ey = fmax(g.y - (double)ly, (double)hy - g.y),
                  ez = fmax(g.z - (double)lz, (double)hz - g.z);
-    put(m, g.x), put(m + 1, g.y), put(m + 2, g.z), put(m + 3, (ex * ex + ey * ey) + ez * ez);
-    put(m + 4, N.x), put(m + 5, N.y), put(m + 6, N.z), put(m + 7, A);
+    agent_put(m, g.x), agent_put(m + 1, g.y), agent_put(m + 2, g.z), agent_put(m + 3, (ex * ex + ey * ey) + ez * ez);
+    agent_put(m + 4, N.x), agent_put(m + 5, N.y), agent_put(m + 6, N.z), agent_put(m + 7, A);
 }
 
 // One thread per internal node.  A node's row can be written once both children are known: a leaf child is known from
@@ -154,7 +127,7 @@ __global__ __launch_bounds__(256) void k_bvh_moments(int64_t F, int64_t V, const
         if (atomicAdd(counters + cur, 1) == 0) return;
         __threadfence();
     }
-    for (int level = 0; level < kDepth; ++level) {
+    for (int level = 0; level < pn_bvh::kDepth; ++level) {
         node_row(cur, F, V, vertices, faces, nodes, moments);
         const int32_t parent = __float_as_int(nodes[cur * 4 + 2].w);
         if (parent < 0 || parent >= F - 1) return;  // the root, or a row this library did not write
@@ -173,22 +146,21 @@ __global__ void k_zero_row(double* moments) {
 // Pre-order from row 0, the left child first and the right one pushed; S takes the terms in visiting order.  `visits`
 // counts every reference taken up, leaf or node, and ends the walk at 2 F: a tree has 2 F - 1 of them, so the bound only
 // shows over a buffer that is no tree.
-constexpr int kWalkThreads = 64;  // one wave per workgroup: the [depth][thread] stack of pn_tri.h's BvhFinder
+constexpr int kWalkThreads = 64;  // one wave per workgroup (the LDS stack is per thread)
 
 __global__ __launch_bounds__(kWalkThreads) void k_winding_bvh(int64_t P, const float* points, int64_t V,
                                                              const float* vertices, int64_t F, const int32_t* faces,
                                                              const float4* nodes, const double* moments, double beta2,
                                                              float* winding) {
-    __shared__ int s_stack[kDepth * kWalkThreads];
-    int* stack = s_stack + threadIdx.x;
+    __shared__ pn_bvh::Stack<kWalkThreads>::Shared s_stack;
+    pn_bvh::Stack<kWalkThreads> stack(s_stack);
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= P) return;  // no barrier below
     P3 p;
-    const bool ask = load_point(r, P, points, p);
+    const bool ask = pn_mesh64::load_point(r, P, points, p);
     double S = 0.0;
     if (ask) {
         int32_t cur = F > 1 ? 0 : ~0;  // F = 1: the single leaf
-        int sp = 0;
         for (int64_t visits = 0; visits < 2 * F; ++visits) {
             if (cur >= 0 && cur < F - 1) {
                 const double* m = moments + (int64_t)cur * 8;
@@ -197,10 +169,9 @@ __global__ __launch_bounds__(kWalkThreads) void k_winding_bvh(int64_t P, const f
                 if (d2 > 0.0 && d2 >= beta2 * m[3]) {
                     S += dot3(P3{m[4], m[5], m[6]}, x) / (d2 * sqrt(d2));
                 } else {
-                    const int32_t lref = __float_as_int(nodes[(int64_t)cur * 4].w),
-                                  rref = __float_as_int(nodes[(int64_t)cur * 4 + 1].w);
-                    if (sp < kDepth) stack[sp++ * kWalkThreads] = rref;  // sp < kDepth always: the depth bound
-                    cur = lref;
+                    const pn_bvh::Row n = pn_bvh::read_row(nodes, cur);  // only .w of a and b is used: the ISA loads two words
+                    stack.push(n.rref);
+                    cur = n.lref;
                     continue;
                 }
             } else if (cur < 0) {
@@ -208,14 +179,12 @@ __global__ __launch_bounds__(kWalkThreads) void k_winding_bvh(int64_t P, const f
                 P3 a, b, c;
                 if (f < F && load_tri(f, V, vertices, faces, a, b, c)) S += solid_angle(p, a, b, c);
             }
-            if (sp == 0) break;
-            cur = stack[--sp * kWalkThreads];
+            if (stack.empty()) break;
+            cur = stack.pop();
         }
     }
     winding[r] = finish(ask, S);
 }
-
-bool count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }
 
 }  // namespace
 

@@ -63,16 +63,24 @@ def _points(points, dev=None):
     return points.detach().contiguous()
 
 
+def _number(value, name, lo, hi, message, fp32=True):
+    """value, a Python or numpy number (no bool, no tensor), as the fp32 the kernel sees (fp32=False: as given), in [lo, hi]"""
+    ok = not isinstance(value, (torch.Tensor, bool)) and isinstance(value, (int, float, np.integer, np.floating))
+    x = (float(np.float32(value)) if fp32 else float(value)) if ok else math.nan
+    if not lo <= x <= hi:
+        raise ValueError(f"{name} {message}; got {value!r}")
+    return x
+
+
 def _reach(max_distance):
     """max_distance as the fp32 value the kernel sees; None: +inf"""
-    if max_distance is None:
-        return math.inf
-    if isinstance(max_distance, (torch.Tensor, bool)) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
-        raise ValueError(f"max_distance must be None or a number >= 0; got {max_distance!r}")
-    m = float(np.float32(max_distance))
-    if not m >= 0.0:
-        raise ValueError(f"max_distance must be None or a number >= 0; got {max_distance!r}")
-    return m
+    return math.inf if max_distance is None else _number(max_distance, "max_distance", 0.0, math.inf,
+                                                          "must be None or a number >= 0")
+
+
+def _tree(mesh, dev, accel, wanted=True):
+    """what objects._prepare makes of accel for this mesh; None for brute force, or when nothing is asked (wanted)"""
+    return _prepare(mesh.vertices, mesh.faces, dev, accel) if accel is not None and wanted else None
 
 
 def _count(count, name="count"):
@@ -111,7 +119,7 @@ def closest_point(points, vertices, faces, max_distance=None, accel="bvh"):
     mesh, dev = _as_mesh(vertices, faces)
     p = _points(points, dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        tree = _prepare(mesh.vertices, mesh.faces, dev, accel) if accel is not None and p.shape[0] else None
+        tree = _tree(mesh, dev, accel, p.shape[0])
         return _closest(p, mesh.vertices, mesh.faces, tree, reach, dev)
 
 
@@ -202,8 +210,7 @@ def compare_meshes(a, b, samples=DEFAULT_SAMPLES, thresholds=DEFAULT_THRESHOLDS,
     with torch.no_grad(), torch.cuda.device(dev):
         pa, fa, _ = _sample(a.vertices, a.faces, n, dev)
         pb, fb, _ = _sample(b.vertices, b.faces, n, dev)
-        tree_a = _prepare(a.vertices, a.faces, dev, accel) if accel is not None else None
-        tree_b = _prepare(b.vertices, b.faces, dev, accel) if accel is not None else None
+        tree_a, tree_b = _tree(a, dev, accel), _tree(b, dev, accel)
         dab, nab = _one_way(pa, fa, a, b, tree_b, dev)
         dba, nba = _one_way(pb, fb, b, a, tree_a, dev)
         tau = torch.tensor(taus, dtype=torch.float64, device=dev)
@@ -225,6 +232,19 @@ def compare_meshes(a, b, samples=DEFAULT_SAMPLES, thresholds=DEFAULT_THRESHOLDS,
             "normal_consistency": nc, "samples": n}
 
 
+def _grid_query(mesh, dev, res, lo, step, tree, query):
+    """query(points [m, 3]) -> [m] on geometry's grid, GRID_CHUNK points at a time; mesh and tree are what query closes over"""
+    vol = torch.empty(res, dtype=torch.float32, device=dev)
+    n = vol.numel()
+    pts = torch.empty(min(n, GRID_CHUNK), 3, dtype=torch.float32, device=dev)
+    cov = torch.empty_like(pts)
+    for first in range(0, n, GRID_CHUNK):
+        m = min(GRID_CHUNK, n - first)
+        _lib.call("pn_grid_points", *res, first, m, *lo, *step, 0.0, pts.data_ptr(), cov.data_ptr(), _lib.stream(dev))
+        vol.view(-1)[first:first + m] = query(pts[:m])
+    return vol
+
+
 def distance_grid(mesh, bounds, resolution, max_distance=None):
     """The unsigned distance to the mesh at the vertices of geometry's grid: a contiguous fp32 [nx, ny, nz] tensor in
     density_grid's point order ((i ny + j) nz + k; bounds are the inclusive corner vertices), +inf where no face lies within
@@ -234,16 +254,7 @@ def distance_grid(mesh, bounds, resolution, max_distance=None):
     lo, step = _placement(bounds, res)
     reach = _reach(max_distance)
     mesh, dev = _as_mesh(mesh)
-    vol = torch.empty(res, dtype=torch.float32, device=dev)
-    flat = vol.view(-1)
     with torch.no_grad(), torch.cuda.device(dev):
-        tree = _prepare(mesh.vertices, mesh.faces, dev, "bvh")
-        st = _lib.stream(dev)
-        n = flat.numel()
-        pts = torch.empty(min(n, GRID_CHUNK), 3, dtype=torch.float32, device=dev)
-        cov = torch.empty_like(pts)
-        for first in range(0, n, GRID_CHUNK):
-            m = min(GRID_CHUNK, n - first)
-            _lib.call("pn_grid_points", *res, first, m, *lo, *step, 0.0, pts.data_ptr(), cov.data_ptr(), st)
-            flat[first:first + m] = _closest(pts[:m], mesh.vertices, mesh.faces, tree, reach, dev)[0]
-    return vol
+        tree = _tree(mesh, dev, "bvh")
+        return _grid_query(mesh, dev, res, lo, step, tree,
+                           lambda p: _closest(p, mesh.vertices, mesh.faces, tree, reach, dev)[0])

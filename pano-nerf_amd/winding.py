@@ -33,27 +33,22 @@ point-cloud or oriented-point inputs; gradients; exact booleans; tuning (the wal
 waves, as it does for the tracer and the distance walk).
 """
 import math
+import sys
 
-import numpy as np
 import torch
 
 from . import _lib
 from .geometry import Mesh, _placement, _resolution, marching_tetrahedra
-from .meshdist import GRID_CHUNK, _closest, _points, _points_arg, _reach
+from .meshdist import _closest, _grid_query, _number, _points, _points_arg, _reach, _tree
 from .meshops import _as_mesh
-from .objects import MeshBVH, _check_accel, _prepare
+from .objects import MeshBVH, _check_accel
 
 DEFAULT_BETA = 4.0  # a convention: DESIGN.md 6n has the error it buys
 
 
 def _beta(beta):
     """beta as the fp32 value the kernel sees"""
-    if isinstance(beta, (torch.Tensor, bool)) or not isinstance(beta, (int, float, np.integer, np.floating)):
-        raise ValueError(f"beta must be a number in [1, 1e6]; got {beta!r}")
-    b = float(np.float32(beta))
-    if not 1.0 <= b <= 1e6:
-        raise ValueError(f"beta must be a number in [1, 1e6]; got {beta!r}")
-    return b
+    return _number(beta, "beta", 1.0, 1e6, "must be a number in [1, 1e6]")
 
 
 def _moments(tree, v, f, dev):
@@ -100,7 +95,7 @@ def winding_number(points, vertices, faces, accel="bvh", beta=DEFAULT_BETA):
     times its radius on.  The module docstring has the conventions."""
     p, mesh, dev, beta = _args(points, vertices, faces, accel, beta)
     with torch.no_grad(), torch.cuda.device(dev):
-        tree = _prepare(mesh.vertices, mesh.faces, dev, accel) if accel is not None and p.shape[0] else None
+        tree = _tree(mesh, dev, accel, p.shape[0])
         return _winding(p, mesh.vertices, mesh.faces, tree, beta, dev)
 
 
@@ -122,30 +117,20 @@ def signed_distance(points, vertices, faces, max_distance=None, accel="bvh", bet
     reach = _reach(max_distance)
     p, mesh, dev, beta = _args(points, vertices, faces, accel, beta)
     with torch.no_grad(), torch.cuda.device(dev):
-        tree = _prepare(mesh.vertices, mesh.faces, dev, accel) if accel is not None and p.shape[0] else None
+        tree = _tree(mesh, dev, accel, p.shape[0])
         return _signed(p, mesh.vertices, mesh.faces, tree, reach, beta, dev)
 
 
 def _grid(mesh, bounds, resolution, accel, beta, query):
-    """query(points [m, 3], v, f, tree, beta, dev) -> [m] on geometry's grid, GRID_CHUNK points at a time"""
+    """query(points [m, 3], v, f, tree, beta, dev) -> [m] on geometry's grid, through meshdist._grid_query"""
     _check_accel(accel)
     beta = _beta(beta)
     res = _resolution(resolution)
     lo, step = _placement(bounds, res)
     mesh, dev = _as_mesh(mesh)
-    vol = torch.empty(res, dtype=torch.float32, device=dev)
-    flat = vol.view(-1)
     with torch.no_grad(), torch.cuda.device(dev):
-        tree = _prepare(mesh.vertices, mesh.faces, dev, accel) if accel is not None else None
-        st = _lib.stream(dev)
-        n = flat.numel()
-        pts = torch.empty(min(n, GRID_CHUNK), 3, dtype=torch.float32, device=dev)
-        cov = torch.empty_like(pts)
-        for first in range(0, n, GRID_CHUNK):
-            m = min(GRID_CHUNK, n - first)
-            _lib.call("pn_grid_points", *res, first, m, *lo, *step, 0.0, pts.data_ptr(), cov.data_ptr(), st)
-            flat[first:first + m] = query(pts[:m], mesh.vertices, mesh.faces, tree, beta, dev)
-    return vol
+        tree = _tree(mesh, dev, accel)
+        return _grid_query(mesh, dev, res, lo, step, tree, lambda p: query(p, mesh.vertices, mesh.faces, tree, beta, dev))
 
 
 def winding_grid(mesh, bounds, resolution, accel="bvh", beta=DEFAULT_BETA):
@@ -168,9 +153,7 @@ def remesh(mesh, resolution, bounds=None, level=0.5, accel="bvh", beta=DEFAULT_B
     broken one - a culled TSDF mesh, a clustered mesh, a soup - the 0.5 level of the winding field closes the holes.
     bounds=None: the box of the vertices grown by two grid steps on every side (needs resolution >= 6 per axis).  The
     result has no normals or colours; it feeds filter_components, simplify_mesh, bake_textures and write_ply as any mesh."""
-    if isinstance(level, (torch.Tensor, bool)) or not isinstance(level, (int, float, np.integer, np.floating)) or \
-            not math.isfinite(level):
-        raise ValueError(f"level must be a finite number; got {level!r}")
+    level = _number(level, "level", -sys.float_info.max, sys.float_info.max, "must be a finite number", fp32=False)
     _check_accel(accel)
     _beta(beta)
     res = _resolution(resolution)
@@ -186,5 +169,5 @@ def remesh(mesh, resolution, bounds=None, level=0.5, accel="bvh", beta=DEFAULT_B
         h = [(b - a) / (n - 5) for a, b, n in zip(lo, hi, res)]
         bounds = (tuple(a - 2.0 * s for a, s in zip(lo, h)), tuple(b + 2.0 * s for b, s in zip(hi, h)))
     vol = winding_grid(m, bounds, res, accel, beta)
-    verts, faces = marching_tetrahedra(vol, float(level), bounds)
+    verts, faces = marching_tetrahedra(vol, level, bounds)
     return Mesh(verts, faces, None, None)

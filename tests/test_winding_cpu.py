@@ -259,3 +259,60 @@ def test_argument_checks_that_need_no_device():
             winding.remesh((v, f), 8, level=bad)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         winding.winding_number(p, v, f)
+
+
+def test_one_number_check_behind_max_distance_beta_and_level():
+    """meshdist._number behind _reach, _beta and remesh's level: a bool, a tensor, a NaN and a value out of range raise each
+    user's own message, whole; a numpy scalar passes as the fp32 the kernel sees (level: as given)"""
+    import torch
+    from pano_nerf_amd import meshdist, winding
+    v, f = torch.zeros(4, 3), torch.zeros(1, 3, dtype=torch.int32)
+    users = {
+        "max_distance": (meshdist._reach, "max_distance must be None or a number >= 0", -0.5),
+        "beta": (winding._beta, "beta must be a number in [1, 1e6]", 1.5e6),
+        "level": (lambda x: winding.remesh((v, f), 8, level=x), "level must be a finite number", float("inf")),
+    }
+    for name, (call, message, outside) in users.items():
+        for bad in (True, torch.ones(1), float("nan"), np.float64("nan"), outside, np.float32(outside)):
+            with pytest.raises(ValueError) as e:
+                call(bad)
+            assert str(e.value) == f"{message}; got {bad!r}", name
+    third = np.float64(1.0) / 3.0
+    for good in (np.float32(2.5), np.float64(2.5), np.int64(3), np.float16(1.5), 2, third + 1.0):
+        want = float(np.float32(good))
+        assert meshdist._reach(good) == want and type(meshdist._reach(good)) is float
+        assert winding._beta(good) == want and type(winding._beta(good)) is float
+    assert meshdist._reach(None) == float("inf") and meshdist._reach(np.float32("inf")) == float("inf")
+    assert meshdist._reach(-1e-50) == 0.0 and winding._beta(1.0 - 1e-9) == 1.0  # judged as fp32
+    assert meshdist._number(third, "level", -1.0, 1.0, "", fp32=False) == float(third) != float(np.float32(third))
+    assert meshdist._number(1e300, "level", -1.7976931348623157e308, 1.7976931348623157e308, "", fp32=False) == 1e300
+
+
+def test_the_grid_loop_visits_every_chunk_once(monkeypatch):
+    """meshdist._grid_query: first = 0, GRID_CHUNK, ... with the last chunk short, each chunk's answers in its place"""
+    import torch
+    from pano_nerf_amd import _lib, meshdist
+    monkeypatch.setattr(meshdist, "GRID_CHUNK", 7)
+    placed, asked = [], []
+    grid = (2, 3, 4, 0.0, 0.5, 1.0, 0.25, 0.5, 1.0, 0.0)  # res, lo, step and the radius, as pn_grid_points takes them
+
+    def call(name, *args):
+        assert name == "pn_grid_points" and args[:3] + args[5:12] == grid
+        placed.append((args[3], args[4]))
+
+    def query(points):
+        assert points.shape == (placed[-1][1], 3) and len(asked) == len(placed) - 1
+        asked.append(len(points))
+        return torch.arange(len(points), dtype=torch.float32) + 100.0 * len(asked)
+
+    monkeypatch.setattr(_lib, "call", call)
+    monkeypatch.setattr(_lib, "stream", lambda dev: 0)
+    vol = meshdist._grid_query(None, torch.device("cpu"), (2, 3, 4), (0.0, 0.5, 1.0), (0.25, 0.5, 1.0), None, query)
+    assert placed == [(0, 7), (7, 7), (14, 7), (21, 3)] and asked == [7, 7, 7, 3]
+    assert tuple(vol.shape) == (2, 3, 4) and vol.dtype == torch.float32 and vol.is_contiguous()
+    want = torch.cat([torch.arange(m, dtype=torch.float32) + 100.0 * (k + 1) for k, m in enumerate(asked)])
+    assert torch.equal(vol.view(-1), want)
+    placed.clear(), asked.clear()
+    grid = (1, 1, 7, 0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0.0)
+    assert meshdist._grid_query(None, torch.device("cpu"), (1, 1, 7), (0.0,) * 3, (1.0,) * 3, None, query).shape == (1, 1, 7)
+    assert placed == [(0, 7)]  # a grid of exactly one chunk: one launch

@@ -15,6 +15,7 @@ profiles/geometry_meshdist.txt) and prints the same figures as one JSON line.
 Times are medians of --iters synchronised calls after one warm-up call, host clock around a device synchronise, with the
 spread (max - min) of the repeats.  The resource report of the kernels comes from the compiler, not from a run:
     PN_EXTRA=-Rpass-analysis=kernel-resource-usage bash pano-nerf_amd/csrc/build.sh 2>&1 | grep -A9 "k_closest\\|k_face_\\|k_sample"
+PN_LIB=<another build of the library> in the environment measures that build, as tools/profile_conventions.py.
 """
 import argparse
 import json
@@ -26,7 +27,10 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pano_nerf_amd import geometry, meshdist, meshops, objects  # noqa: E402
+from pano_nerf_amd import _lib, geometry, meshdist, meshops, objects  # noqa: E402
+
+if os.environ.get("PN_LIB"):  # another build of the library, as tools/profile_conventions.py
+    _lib.LIB_PATH = os.path.abspath(os.environ["PN_LIB"])
 
 RADIUS, CENTRE = 0.35, (0.5, -0.1, 0.8)
 BOUNDS = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))

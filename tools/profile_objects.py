@@ -14,6 +14,7 @@ differ.  Level 8 is 1 310 720 faces.
     python tools/profile_objects.py --accel both --levels 3,6,8
     python tools/profile_objects.py --kernels              # the kernels alone, for a trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/profile_objects.py --kernels --iters 2 --levels 6 --frames pano
+    PN_LIB=<another build of the library> python tools/profile_objects.py --kernels --accel bvh     # as tools/profile_conventions.py
 """
 import argparse
 import json
@@ -28,6 +29,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pano_nerf_amd as pn  # noqa: E402
 from oracle import pano_oracle as orc  # noqa: E402
 from pano_nerf_amd import _lib, lighting, objects, views  # noqa: E402
+
+if os.environ.get("PN_LIB"):  # another build of the library, as tools/profile_conventions.py
+    _lib.LIB_PATH = os.path.abspath(os.environ["PN_LIB"])
 
 
 def setup():

@@ -15,6 +15,7 @@ profiles/geometry_winding.txt) and prints the same figures as one JSON line.
 Times are medians of --iters synchronised calls after one warm-up call, host clock around a device synchronise, with the
 spread (max - min) of the repeats.  The resource report of the kernels comes from the compiler, not from a run:
     PN_EXTRA=-Rpass-analysis=kernel-resource-usage bash pano-nerf_amd/csrc/build.sh 2>&1 | grep -A9 "k_winding\\|k_bvh_moments"
+PN_LIB=<another build of the library> in the environment measures that build, as tools/profile_conventions.py.
 """
 import argparse
 import json
@@ -28,7 +29,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from pano_nerf_amd import geometry, meshdist, meshops, objects, winding  # noqa: E402
+from pano_nerf_amd import _lib, geometry, meshdist, meshops, objects, winding  # noqa: E402
+
+if os.environ.get("PN_LIB"):  # another build of the library, as tools/profile_conventions.py
+    _lib.LIB_PATH = os.path.abspath(os.environ["PN_LIB"])
 from tools.profile_meshdist import BOUNDS, CENTRE, RADIUS, icosphere, query_sets, timed  # noqa: E402
 
 BETAS = (2.0, 4.0, 8.0)
