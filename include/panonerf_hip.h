@@ -1394,6 +1394,40 @@ int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, con
                     const float* directions, const float* near, const float* far, float step, float t_min, float* rgb,
                     float* depth, float* acc, float* attrs, int32_t* taps, void* stream);
 
+/* ---- radiance volume: gradients: the reverse of the compositing sweep, for the dense store (pn_volume.hip) -----------
+ * pn_volume_march_bwd takes pn_volume_march's arguments up to t_min (the optional occupancy table included), the upstream
+ * gradients g_rgb [R, 3] and g_acc [R] (fp32; a null pointer counts as zeros) of a scalar L, and adds dL/d(data) for the
+ * sigma and coefficient channels into sums [N, 1 + 3 K] (N = nx ny nz, vertex v, channel ch at v (1 + 3 K) + ch) as
+ * 64-bit integers in units of `quantum`.  All arithmetic is fp64 on the fp32 inputs, separate operations in the written
+ * order.  Per valid row (the forward's rule) the kernel runs pn_volume_march's own loop twice: the same lattice, gates,
+ * jumps and early stop, term for term, from the same device function.  A sample "composites" if its sigma > 0; col_c is
+ * its clamped colour, s_c the unclamped sum, w, alpha, T (before the sample) and wgt = T alpha the forward's values,
+ * stepw = dt len.
+ *   Pass 1.  u = ((g_r col_r + g_g col_g) + g_b col_b) + g_a per compositing sample; U = U + wgt u, ascending from 0.
+ *   Pass 2.  Per compositing sample: P = P + wgt u (from 0), Tn = T (1 - alpha), ds = stepw (Tn u - (U - P)), which is
+ *     dL/d(sigma of the sample): Tn u is what the sample adds itself, U - P what the samples behind it lose.  Its
+ *     contributions, for corner q (weight w[q], vertex v):  sigma: x = w[q] ds into (v, 0);  coefficient (k, c):
+ *     x = w[q] (Y_k (wgt g_c)) into (v, 1 + 3 k + c), only where s_c > 0 (the clamp's gate).
+ * Attribute channels, depth, origins and directions get no gradient; a row the forward does not march adds nothing.
+ * Accumulation.  quantum is a power of two in [2^-60, 1].  A contribution x becomes m = llrint(x / quantum) (round half
+ *   to even) and, if m != 0, ONE relaxed agent-scope 64-bit integer fetch_add into sums (a vector atomic).  Integer
+ *   addition is associative: sums depends neither on the order of the rows, nor on the schedule, nor on the table, and
+ *   calls accumulate.  A contribution that is not finite or has |x / quantum| >= 2^52 adds nothing and ORs 1 into *flag
+ *   (an integer atomic) instead.  Range: |sum| < 2^63 quantum, i.e. 2^23 at the customary quantum 2^-40; a sum beyond it
+ *   wraps, silently: the caller's scale to avoid.  Each contribution is off by at most quantum / 2.
+ * pn_volume_grad_finish: grad [N, C] fp32, grad[v, ch] = (float)((double)sums[v, ch] quantum) for ch < Cg (= 1 + 3 K),
+ *   0 for Cg <= ch < C (the attribute channels), and NaN in EVERY entry if *flag != 0 (a poisoned backward, as torch
+ *   has it; no host synchronisation is needed to look at the flag).  clear != 0 zeroes sums as it reads them and resets
+ *   the flag with a one-thread launch behind the first.
+ * Errors: as pn_volume_march, and PN_ERR_BAD_SHAPE for a quantum that is not a power of two in [2^-60, 1], Cg < 1,
+ *   C < Cg or C > 36; PN_ERR_NULL for sums, flag or grad.  R = 0 launches nothing. */
+int pn_volume_march_bwd(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float* data, const uint8_t* occupancy,
+                        float x0, float y0, float z0, float dx, float dy, float dz, const float* origins,
+                        const float* directions, const float* near, const float* far, float step, float t_min,
+                        const float* g_rgb, const float* g_acc, double quantum, int64_t* sums, int32_t* flag, void* stream);
+int pn_volume_grad_finish(int64_t N, int C, int Cg, int64_t* sums, double quantum, int32_t* flag, float* grad, int clear,
+                          void* stream);
+
 /* ---- sparse radiance volume: a brick table and a pool of the present bricks, fp32 or fp16 (pn_volume.hip) -------------
  * The same volume as above with the unoccupied bricks left out.  Bricks and their linear index are pn_volume_occupancy's:
  * nb_a = ceil((n_a - 1) / PN_VOLUME_BRICK), brick (bi nby + bj) nbz + bk.  A brick is PRESENT iff pn_volume_occupancy

@@ -132,6 +132,8 @@ SIGNATURES = {
     "pn_volume_bricks": ("l", "iii"),
     "pn_volume_occupancy": ("i", "iiii" + "pp" + "p"),
     "pn_volume_march": ("i", "liiiii" + "pp" + "ffffff" + "pppp" + "ff" + "ppppp" + "p"),
+    "pn_volume_march_bwd": ("i", "liiiii" + "pp" + "ffffff" + "pppp" + "ff" + "pp" + "d" + "pp" + "p"),
+    "pn_volume_grad_finish": ("i", "liip" + "d" + "ppi" + "p"),
     "pn_volume_pack": ("i", "iiii" + "pl" + "pplp" + "ip" + "p"),
     "pn_volume_unpack": ("i", "iiii" + "pl" + "pi" + "p" + "p"),
     "pn_volume_march_sparse": ("i", "liiiii" + "pp" + "ii" + "ffffff" + "pppp" + "ff" + "ppppp" + "p"),

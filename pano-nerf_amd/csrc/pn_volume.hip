@@ -20,6 +20,10 @@
 // brick pool (fp32 or fp16) behind its table, section "sparse radiance volume" of the header.  A policy answers two
 // questions, "is this cell's brick present" and "corner q, channel ch, as fp64", and carries nothing across samples.
 // k_volume_pack / k_volume_unpack move a volume between the two layouts.
+//
+// k_volume_march_bwd is the reverse of the compositing sweep for the dense store (header, "radiance volume: gradients"): it
+// scatters dL/d(sigma, coefficients) as 64-bit integers, so that the sums are the same bits whatever the order;
+// k_volume_grad_finish turns them into the fp32 gradient.
 #include "pn_common.h"
 #include "pn_probes.h"  // sh_basis
 
@@ -383,6 +387,289 @@ __global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs<Store> a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------- gradients
+// what the marching loop reads: the volume, the rays and the two march parameters
+template <class Store>
+struct MarchRows {
+    int64_t R;
+    int n[3];  // vertices per axis
+    int E;     // attribute channels
+    Store store;
+    double lo[3], st[3];
+    const float *origins, *directions, *near, *far;
+    double step, t_min;
+};
+
+// the reverse sweep's extra arguments (header, "radiance volume: gradients")
+struct GradArgs {
+    const float *g_rgb, *g_acc;  // [R, 3], [R]; null counts as zeros
+    double inv_quantum;          // 1 / quantum: a power of two, so x * inv_quantum is x / quantum exactly
+    long long* sums;             // [N, 1 + 3 K]
+    int32_t* flag;
+};
+
+// one row's lattice (header, "Lattice"); valid false: the row marches nothing
+struct Row {
+    double o[3], d[3], tn, tf, len, dt;
+    int n;
+    bool valid;
+};
+
+template <class Store>
+__device__ __forceinline__ Row load_row(const MarchRows<Store>& a, int64_t r) {
+    Row row;
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        row.o[x] = (double)a.origins[3 * r + x];
+        row.d[x] = (double)a.directions[3 * r + x];
+    }
+    row.tn = (double)a.near[r], row.tf = (double)a.far[r];
+    bool valid = finite_d(row.tn) && finite_d(row.tf);
+#pragma unroll
+    for (int x = 0; x < 3; ++x) valid = valid && finite_d(row.o[x]) && finite_d(row.d[x]);
+    row.len = sqrt((row.d[0] * row.d[0] + row.d[1] * row.d[1]) + row.d[2] * row.d[2]);
+    valid = valid && row.len > 0.0 && row.tf > row.tn;
+    double nd = 0.0;
+    row.dt = 0.0;
+    if (valid) {
+        row.dt = a.step / row.len;
+        nd = ceil((row.tf - row.tn) / row.dt);
+        valid = nd < 2147483648.0;  // an infinite or NaN count fails too
+    }
+    row.n = valid ? (int)nd : 0;
+    row.valid = valid;
+    return row;
+}
+
+// k_volume_march's loop over a valid row, statement for statement (lattice, gates, jumps, early stop) without the tap
+// counters: hoisting the forward's own body into this template moved its register counts (DenseStore, degree 0, with
+// attributes: 167 -> 169 VGPRs, one wave per SIMD fewer), so the forward keeps its loop and the two passes of the reverse
+// sweep share this copy.  Every sample that composites (sigma > 0) is handed to on_sample(c, w, s, alpha, wgt, T): the
+// cell, the corner weights, the unclamped colour sums s_c, and T before the sample.
+template <int kDeg, class Store, class F>
+__device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& row,
+                                          const double (&Y)[(kDeg + 1) * (kDeg + 1)], F&& on_sample) {
+    constexpr int K = (kDeg + 1) * (kDeg + 1);
+    const int C = 1 + 3 * K + a.E;
+    const double(&o)[3] = row.o;
+    const double(&d)[3] = row.d;
+    const double tn = row.tn, dt = row.dt;
+    {
+        const int n = row.n;
+        const double stepw = dt * row.len;
+        // the grid coordinate of axis x at lattice point kk: THE sampling formula, also what every jump is checked with
+        auto coord = [&](int x, int kk) -> double {
+            const double t = tn + ((double)kk + 0.5) * dt;
+            return ((o[x] + t * d[x]) - a.lo[x]) / a.st[x];
+        };
+        // the lattice position of the plane g_x = p: (t_plane - near) / dt - 0.5 (callers have d[x] != 0)
+        auto plane = [&](int x, double p) -> double {
+            return ((((a.lo[x] + p * a.st[x]) - o[x]) / d[x]) - tn) / dt - 0.5;
+        };
+        double T = 1.0;
+        int k = 0;
+        while (k < n) {
+            const double t = tn + ((double)k + 0.5) * dt;
+            double g[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) g[x] = ((o[x] + t * d[x]) - a.lo[x]) / a.st[x];
+            // ---- outside the box: nothing to add; jump to the face ahead, or stop if the ray only moves away
+            bool outside = false, gone = false;
+            int kl = k;
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                const double top = (double)(a.n[x] - 1);
+                const bool low = !(g[x] >= 0.0), high = g[x] > top;
+                if (low || high) {
+                    outside = true;
+                    if (low ? !(d[x] > 0.0) : !(d[x] < 0.0)) {
+                        gone = true;  // monotone coordinates: no later point comes back
+                    } else {
+                        int c = propose(plane(x, low ? 0.0 : top), k, n);
+#pragma unroll 1
+                        for (int tries = 0; tries < 2 && c > k; ++tries) {
+                            const double gc = coord(x, c);
+                            if (low ? !(gc >= 0.0) : gc > top) break;
+                            c = tries == 0 ? c - 1 : k;
+                        }
+                        kl = c > kl ? c : kl;
+                    }
+                }
+            }
+            if (gone) break;
+            if (outside) {
+                k = kl + 1;
+                continue;
+            }
+            // ---- the cell: g in [0, n - 1] on every axis, so 0 <= c <= n - 2 and every corner c, c + 1 is a vertex
+            int c[3];
+            double f[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                const double fl = floor(g[x]);
+                c[x] = imin((int)fl, a.n[x] - 2);
+                f[x] = g[x] - (double)c[x];
+            }
+            typename Store::Tap tap;
+            if (!a.store.present(c, a.n, tap)) {
+                if (Store::kBricks && !a.store.jumps()) {  // an absent brick without jumps: a sigma of 0
+                    ++k;
+                    continue;
+                }
+                // every cell of this brick has corners <= 0 or NaN only: skip to the last lattice point still in it
+                const int b[3] = {c[0] >> kShift, c[1] >> kShift, c[2] >> kShift};
+                double s = (double)(n - 1);
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    if (d[x] != 0.0) {  // an axis the ray does not move along never leaves the brick: no division
+                        const int up = imin((b[x] + 1) * kBrick, a.n[x] - 1);
+                        const double sx = plane(x, d[x] > 0.0 ? (double)up : (double)(b[x] * kBrick));
+                        s = sx < s ? sx : s;
+                    }
+                }
+                int cand = propose(s, k, n);
+#pragma unroll 1
+                for (int tries = 0; tries < 2 && cand > k; ++tries) {
+                    bool same = true;
+#pragma unroll
+                    for (int x = 0; x < 3; ++x) {
+                        const double gc = coord(x, cand);
+                        const bool in = gc >= 0.0 && gc <= (double)(a.n[x] - 1);
+                        const int cc = in ? imin((int)floor(gc), a.n[x] - 2) : -kBrick;
+                        same = same && (cc >> kShift) == b[x];
+                    }
+                    if (same) break;
+                    cand = tries == 0 ? cand - 1 : k;
+                }
+                k = cand + 1;
+                continue;
+            }
+            // ---- the trilinear tap: weights (wx wy) wz, corners in the order i, j, k, low corner first
+            double w[8];
+            a.store.locate(c, a.n, C, tap);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int qi = q >> 2, qj = (q >> 1) & 1, qk = q & 1;
+                w[q] = ((qi ? f[0] : 1.0 - f[0]) * (qj ? f[1] : 1.0 - f[1])) * (qk ? f[2] : 1.0 - f[2]);
+            }
+            double sigma = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) sigma = sigma + w[q] * a.store.value(tap, q, 0);
+            if (!(sigma > 0.0)) {
+                ++k;
+                continue;
+            }
+            double col[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int kk = 0; kk < K; ++kk) {
+                double tri[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) tri[ch] = tri[ch] + w[q] * a.store.value(tap, q, 1 + 3 * kk + ch);
+                }
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) col[ch] = col[ch] + Y[kk] * tri[ch];
+            }
+            const double alpha = 1.0 - exp(-sigma * stepw);
+            const double wgt = T * alpha;
+            on_sample(c, w, col, alpha, wgt, T);
+            T = T * (1.0 - alpha);
+            if (T < a.t_min) break;
+            ++k;
+        }
+    }
+}
+
+// The reverse of the compositing sweep (header, "radiance volume: gradients"): one ray per thread as in the forward, two
+// runs of march_row.  Pass 1 sums U = sum wgt u over the row; pass 2 carries the prefix P, so that U - P is what the
+// samples behind this one still add, and scatters 8 (1 + 3 K) contributions per sample as 64-bit integers of `quantum`:
+// integer addition is associative, so sums depends on no order.  One vector atomic per non-zero contribution, relaxed, at
+// agent scope; a thread's contributions of one sample go to 8 runs of 1 + 3 K consecutive sums, all distinct, so there is
+// nothing to pre-sum within a sample, and summing across samples would need the cell's 8 (1 + 3 K) integers in registers.
+__device__ __forceinline__ void scatter(const GradArgs& g, int64_t at, double x, bool& bad) {
+    const double xq = x * g.inv_quantum;
+    if (!(fabs(xq) < 4503599627370496.0)) {  // 2^52; a NaN or an infinity fails too
+        bad = true;
+        return;
+    }
+    const long long m = llrint(xq);  // round to nearest, ties to even
+    if (m != 0) __hip_atomic_fetch_add(g.sums + at, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int kDeg>
+__global__ __launch_bounds__(kThreads) void k_volume_march_bwd(MarchRows<DenseStore> a, GradArgs g) {
+    constexpr int K = (kDeg + 1) * (kDeg + 1);
+    constexpr int Cg = 1 + 3 * K;
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= a.R) return;
+    const Row row = load_row(a, r);
+    if (!row.valid) return;
+    double gc[3] = {0.0, 0.0, 0.0}, ga = 0.0;
+    if (g.g_rgb) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) gc[ch] = (double)g.g_rgb[3 * r + ch];
+    }
+    if (g.g_acc) ga = (double)g.g_acc[r];
+    double Y[K];
+    sh_basis<kDeg>(row.d[0] / row.len, row.d[1] / row.len, row.d[2] / row.len, Y);
+    const double stepw = row.dt * row.len;
+    auto upstream = [&](const double(&s)[3]) -> double {
+        const double c0 = s[0] > 0.0 ? s[0] : 0.0, c1 = s[1] > 0.0 ? s[1] : 0.0, c2 = s[2] > 0.0 ? s[2] : 0.0;
+        return ((gc[0] * c0 + gc[1] * c1) + gc[2] * c2) + ga;
+    };
+    double U = 0.0;
+    march_row<kDeg>(a, row, Y, [&](const int(&)[3], const double(&)[8], const double(&s)[3], double, double wgt, double) {
+        U = U + wgt * upstream(s);
+    });
+    double P = 0.0;
+    bool bad = false;
+    march_row<kDeg>(a, row, Y,
+                    [&](const int(&c)[3], const double(&w)[8], const double(&s)[3], double alpha, double wgt, double T) {
+                        const double u = upstream(s);
+                        P = P + wgt * u;
+                        const double Tn = T * (1.0 - alpha);
+                        const double ds = stepw * (Tn * u - (U - P));
+                        double gw[3];
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch) gw[ch] = wgt * gc[ch];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) {
+                            // corner q of cell c: a vertex of the grid, c <= n - 2 on every axis
+                            const int64_t v = ((int64_t)(c[0] + (q >> 2)) * a.n[1] + (c[1] + ((q >> 1) & 1))) * a.n[2] +
+                                              (c[2] + (q & 1));
+                            const int64_t at = v * Cg;
+                            scatter(g, at, w[q] * ds, bad);
+#pragma unroll
+                            for (int kk = 0; kk < K; ++kk) {
+#pragma unroll
+                                for (int ch = 0; ch < 3; ++ch)
+                                    if (s[ch] > 0.0) scatter(g, at + 1 + 3 * kk + ch, w[q] * (Y[kk] * gw[ch]), bad);
+                            }
+                        }
+                    });
+    if (bad) __hip_atomic_fetch_or(g.flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// one thread per entry of grad [N, C]; the flag is read by every thread and reset, if asked, by a launch of its own after
+__global__ __launch_bounds__(kCopyThreads) void k_volume_grad_finish(int64_t total, int C, int Cg, long long* __restrict__ sums,
+                                                                     double quantum, const int32_t* __restrict__ flag,
+                                                                     float* __restrict__ grad, int clear) {
+    const int64_t i = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x;
+    if (i >= total) return;
+    const int64_t v = i / C;
+    const int ch = (int)(i - v * C);
+    float out = 0.f;
+    if (ch < Cg) {
+        const int64_t at = v * Cg + ch;
+        out = (float)((double)sums[at] * quantum);
+        if (clear) sums[at] = 0;
+    }
+    grad[i] = *flag != 0 ? __builtin_nanf("") : out;
+}
+
+__global__ void k_volume_flag_reset(int32_t* flag) { *flag = 0; }
+
 bool grid_ok(int nx, int ny, int nz) {
     return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
 }
@@ -396,15 +683,27 @@ void launch_march(const MarchArgs<Store>& a, bool attrs, hipStream_t s) {
         hipLaunchKernelGGL((k_volume_march<Store, kDeg, 0>), grid, block, 0, s, a);
 }
 
+// the argument checks of every marcher, forward and reverse
+bool rows_ok(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float (&lo)[3], const float (&st)[3], float step,
+             float t_min) {
+    bool ok = R >= 0 && R < ((int64_t)1 << 31) * kThreads && grid_ok(nx, ny, nz) && sh_degree >= 0 && sh_degree <= 2 &&
+              E >= 0 && E <= PN_VOLUME_MAX_ATTR && step > 0.f && step < INFINITY && t_min >= 0.f && t_min < INFINITY;
+    for (int x = 0; x < 3; ++x) ok = ok && lo[x] - lo[x] == 0.f && st[x] > 0.f && st[x] < INFINITY;
+    return ok;
+}
+
+// a power of two in [2^-60, 1]
+bool quantum_ok(double quantum) {
+    int e = 0;
+    return quantum >= 0x1p-60 && quantum <= 1.0 && frexp(quantum, &e) == 0.5;
+}
+
 // what pn_volume_march and pn_volume_march_sparse share: the argument checks and the dispatch over the SH degree
 template <class Store>
 int march(const Store& store, bool have_store, int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float (&lo)[3],
           const float (&st)[3], const float* origins, const float* directions, const float* near, const float* far,
           float step, float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
-    bool ok = R >= 0 && R < ((int64_t)1 << 31) * kThreads && grid_ok(nx, ny, nz) && sh_degree >= 0 && sh_degree <= 2 &&
-              E >= 0 && E <= PN_VOLUME_MAX_ATTR && step > 0.f && step < INFINITY && t_min >= 0.f && t_min < INFINITY;
-    for (int x = 0; x < 3; ++x) ok = ok && lo[x] - lo[x] == 0.f && st[x] > 0.f && st[x] < INFINITY;
-    if (!ok) return PN_ERR_BAD_SHAPE;
+    if (!rows_ok(R, nx, ny, nz, sh_degree, E, lo, st, step, t_min)) return PN_ERR_BAD_SHAPE;
     if (R == 0) return PN_OK;
     if (!have_store || !origins || !directions || !near || !far) return PN_ERR_NULL;
     MarchArgs<Store> a{R, {nx, ny, nz}, E, store, {}, {}, origins, directions, near, far, (double)step, (double)t_min,
@@ -456,6 +755,45 @@ int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, con
     const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
     return march(DenseStore{data, occupancy}, data != nullptr, R, nx, ny, nz, sh_degree, E, lo, st, origins, directions, near,
                  far, step, t_min, rgb, depth, acc, attrs, taps, stream);
+}
+
+int pn_volume_march_bwd(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float* data, const uint8_t* occupancy,
+                        float x0, float y0, float z0, float dx, float dy, float dz, const float* origins,
+                        const float* directions, const float* near, const float* far, float step, float t_min,
+                        const float* g_rgb, const float* g_acc, double quantum, int64_t* sums, int32_t* flag, void* stream) {
+    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
+    if (!rows_ok(R, nx, ny, nz, sh_degree, E, lo, st, step, t_min) || !quantum_ok(quantum)) return PN_ERR_BAD_SHAPE;
+    if (R == 0) return PN_OK;
+    if (!data || !origins || !directions || !near || !far || !sums || !flag) return PN_ERR_NULL;
+    MarchRows<DenseStore> a{R, {nx, ny, nz}, E, DenseStore{data, occupancy}, {}, {}, origins, directions, near, far,
+                            (double)step, (double)t_min};
+    for (int x = 0; x < 3; ++x) a.lo[x] = (double)lo[x], a.st[x] = (double)st[x];
+    const GradArgs g{g_rgb, g_acc, 1.0 / quantum, (long long*)sums, flag};
+    const dim3 grid(nblk(R, kThreads)), block(kThreads);
+    switch (sh_degree) {
+        case 0: hipLaunchKernelGGL(k_volume_march_bwd<0>, grid, block, 0, ST(stream), a, g); break;
+        case 1: hipLaunchKernelGGL(k_volume_march_bwd<1>, grid, block, 0, ST(stream), a, g); break;
+        default: hipLaunchKernelGGL(k_volume_march_bwd<2>, grid, block, 0, ST(stream), a, g); break;
+    }
+    PN_CHECK_LAUNCH();
+    return PN_OK;
+}
+
+int pn_volume_grad_finish(int64_t N, int C, int Cg, int64_t* sums, double quantum, int32_t* flag, float* grad, int clear,
+                          void* stream) {
+    if (N < 0 || N >= ((int64_t)1 << 31) || Cg < 1 || C < Cg || C > 1 + 27 + PN_VOLUME_MAX_ATTR || !quantum_ok(quantum))
+        return PN_ERR_BAD_SHAPE;
+    if (N == 0) return PN_OK;
+    if (!sums || !flag || !grad) return PN_ERR_NULL;
+    const int64_t total = N * C;
+    hipLaunchKernelGGL(k_volume_grad_finish, dim3(nblk(total, kCopyThreads)), dim3(kCopyThreads), 0, ST(stream), total, C, Cg,
+                       (long long*)sums, quantum, flag, grad, clear);
+    PN_CHECK_LAUNCH();
+    if (clear) {
+        hipLaunchKernelGGL(k_volume_flag_reset, dim3(1), dim3(1), 0, ST(stream), flag);
+        PN_CHECK_LAUNCH();
+    }
+    return PN_OK;
 }
 
 int pn_volume_pack(int nx, int ny, int nz, int channels, const int32_t* table, int64_t B, const float* data,

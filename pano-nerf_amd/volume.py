@@ -3,8 +3,8 @@
 Every other view of a trained model goes through the MLP.  This module exports the field as the asset NeRF toolchains use
 for previews, viewers and fast probes (PlenOctrees / "baked" NeRF style): one dense voxel volume of density, view-dependent
 radiance as real spherical harmonics, and optional attributes (albedo, normal), marched directly by ``pn_volume.hip`` with
-empty-space skipping over 8^3-cell bricks.  Everything runs on the HIP device under ``torch.no_grad()`` on the current
-stream; CPU tensors raise, there is no host fallback.
+empty-space skipping over 8^3-cell bricks.  Everything runs on the HIP device on the current stream (under
+``torch.no_grad()`` except march_rays_ad); CPU tensors raise, there is no host fallback.
 
     RadianceVolume(data, bounds, sh_degree, attributes)   data [nx, ny, nz, C] on geometry's vertex grid
       .sigma / .coeff / .attributes             views: [nx, ny, nz], [nx, ny, nz, K, 3], name -> [nx, ny, nz, w]
@@ -24,6 +24,10 @@ stream; CPU tensors raise, there is no host fallback.
     render_volume(vol, camera, c2w, ...)        dict of [1, C, H, W] images for any camera of cameras.py
     render_volume_path(vol, camera, poses, ...) dict kind -> frames (or PNG / EXR files), as views.render_path
     volume_probes(vol, positions, ...)          [P, 3, H, W] HDR probes with lighting.light_probes' pixel directions
+    march_rays_grad(vol, rays.., grad_rgb, grad_acc, ...)   the reverse sweep: int64 sums [N, 1 + 3 K] of `quantum`, and a flag
+    finish_grad(vol, sums, flag, quantum, clear)   the fp32 gradient [nx, ny, nz, C] of vol.data (NaN if the flag is set)
+    march_rays_ad(vol, rays.., outputs)         march_rays as an autograd function: vol.data.requires_grad_() just works
+    fit_volume(vol, images, camera, poses, steps, ...)   Adam on sigma and the coefficients against images, in place
 
 The contract of the marcher is stated in include/panonerf_hip.h, section "radiance volume", and argued in DESIGN.md 6o.
 Conventions, not measurements: D = 4 K baking directions, a marching step of half the smallest grid step, t_min = 1e-3 and
@@ -33,9 +37,14 @@ ray through the box.
 The sparse form is stated in the header's section "sparse radiance volume" and argued in DESIGN.md 6p: marching it gives
 the bits of marching its dense expansion, because the marcher's arithmetic is fp64 on the stored values either way.
 
+The gradient of the marcher is stated in the header's section "radiance volume: gradients" and argued in DESIGN.md 6t: the
+reverse sweep scatters 64-bit integers of a power-of-two quantum, so a gradient is the same bits whatever the order of
+the rays.  fit_volume's two learning rates are conventions (profiles/volume_fit.txt has the sweep).
+
 Out of scope: a split sigma / colour pool, quantised or block-compressed storage, hashed tables, bricks other than 8,
-editing a sparse volume in place, an fp32-arithmetic marcher, gradients or fine-tuning of the volume, cone-aware (mip)
-filtering, baking the surface / shading branch, and stereo baking.
+editing a sparse volume in place, an fp32-arithmetic marcher, cone-aware (mip) filtering, baking the surface / shading
+branch, and stereo baking.  Of the gradients: sparse and fp16 gradients; depth, attribute, ray and camera gradients; TV or
+sparsity regularisers; data-parallel fitting; growing or pruning the grid.
 """
 import json
 import math
@@ -47,7 +56,7 @@ import torch
 from . import _lib, views
 from .cameras import PanoCamera, _c2w_stack, _camera
 from .geometry import _model_device, _placement, _resolution, _variance, density_grid, grid_points, query_field
-from .rays import CameraRig
+from .rays import CameraRig, RayPool
 
 BRICK = 8          # PN_VOLUME_BRICK
 BRICK_VERTICES = (BRICK + 1) ** 3  # a stored brick: its 8^3 cells' vertices, the shared far faces included
@@ -720,3 +729,224 @@ def volume_probes(vol, positions, height=32, width=64, near=0.0, far=10.0, step=
             return torch.empty(0, 3, H, W, dtype=torch.float32, device=dev)
         rgb = _march_rig(vol, rig, 0, P * H * W, near, far, step, t_min, skip, ("rgb",))["rgb"]
     return rgb.view(P, H, W, 3).permute(0, 3, 1, 2)
+
+
+# -------------------------------------------------------------------------------------------------------- gradients
+QUANTUM = 2.0 ** -40  # the unit of the integer gradient sums: |sum| < 2^63 QUANTUM = 2^23, each contribution off by <= 2^-41
+_ADAM = (0.9, 0.999, 1e-8)  # beta1, beta2, eps of fit_volume's update: torch.optim.Adam's defaults
+# fit_volume's default rates, conventions chosen from the sweep of tools/profile_volume_fit.py (profiles/volume_fit.txt):
+# sigma moves by about LR_SIGMA / |box diagonal| per step, a coefficient by about LR_COEFF
+LR_SIGMA, LR_COEFF = 10.0, 0.01
+
+
+def _quantum(quantum):
+    q = float(quantum)
+    if not (2.0 ** -60 <= q <= 1.0) or math.frexp(q)[0] != 0.5:
+        raise ValueError(f"quantum must be a power of two in [2^-60, 1]; got {quantum!r}")
+    return q
+
+
+def _dense(vol, what):
+    if isinstance(vol, SparseRadianceVolume):
+        raise ValueError(f"{what} takes a dense RadianceVolume: a brick pool stores the vertices on shared faces once per "
+                         "present brick, so its copies would each get part of the gradient and drift apart.  Fit the dense "
+                         "volume (to_dense()), then to_sparse()")
+    if not isinstance(vol, RadianceVolume):
+        raise ValueError(f"{what} takes a RadianceVolume; got {type(vol).__name__}")
+    return 1 + 3 * _sh_count(vol.sh_degree)
+
+
+def _march_params(vol, step, t_min):
+    step = default_step(vol) if step is None else float(np.float32(step))
+    t_min = float(np.float32(t_min))
+    if not (step > 0.0 and math.isfinite(step)) or not (t_min >= 0.0 and math.isfinite(t_min)):
+        raise ValueError(f"step must be positive and finite and t_min >= 0; got {step!r}, {t_min!r}")
+    return step, t_min
+
+
+def march_rays_grad(vol, origins, directions, near, far, grad_rgb=None, grad_acc=None, step=None, t_min=1e-3, skip=True,
+                    quantum=QUANTUM, sums=None, flag=None):
+    """The reverse of march_rays for a dense RadianceVolume, one launch of pn_volume_march_bwd: with the upstream gradients
+    grad_rgb [R, 3] and grad_acc [R] / [R, 1] of a scalar L (None counts as zeros), add dL/d(sigma) and dL/d(coefficients)
+    into `sums`, int64 [N, 1 + 3 K] in units of `quantum` (N = nx ny nz vertices), and return (sums, flag).  sums / flag
+    None allocate zeros; given ones are accumulated into.  flag int32 [1] becomes non-zero if a contribution was not
+    finite or reached 2^52 quanta (it then added nothing).  The sums are integers, so they are the same bits for any
+    order of the rows, any split of them over calls, and with or without skip; |sum| must stay below 2^63 quantum
+    (2^23 at the default).  The rays, step, t_min and skip are march_rays'.  finish_grad turns the sums into fp32."""
+    Cg = _dense(vol, "march_rays_grad")
+    quantum = _quantum(quantum)
+    for t, what in ((origins, "origins"), (directions, "directions")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
+    dev = vol.device
+    R = int(origins.shape[0])
+    step, t_min = _march_params(vol, step, t_min)
+    o = _rows(origins, R, 3, "origins", dev)
+    d = _rows(directions, R, 3, "directions", dev)
+    tn, tf = _rows(near, R, 1, "near", dev), _rows(far, R, 1, "far", dev)
+    g_rgb = None if grad_rgb is None else _rows(grad_rgb, R, 3, "grad_rgb", dev)
+    g_acc = None if grad_acc is None else _rows(grad_acc, R, 1, "grad_acc", dev)
+    N = vol.resolution[0] * vol.resolution[1] * vol.resolution[2]
+    E = vol.channels - Cg
+    with torch.no_grad(), torch.cuda.device(dev):
+        if sums is None:
+            sums = torch.zeros(N, Cg, dtype=torch.int64, device=dev)
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        _check_workspace(sums, flag, N, Cg, dev)
+        _lib.call("pn_volume_march_bwd", R, *vol.resolution, vol.sh_degree, E, vol.data.data_ptr(),
+                  _lib.ptr(vol.occupancy if skip else None), *vol.lo, *vol.step, o.data_ptr(), d.data_ptr(), tn.data_ptr(),
+                  tf.data_ptr(), step, t_min, _lib.ptr(g_rgb) if R else None, _lib.ptr(g_acc) if R else None, quantum,
+                  sums.data_ptr(), flag.data_ptr(), _lib.stream(dev))
+    return sums, flag
+
+
+def _check_workspace(sums, flag, N, Cg, dev):
+    if (not isinstance(sums, torch.Tensor) or sums.dtype != torch.int64 or tuple(sums.shape) != (N, Cg)
+            or not sums.is_contiguous() or sums.device != dev):
+        raise ValueError(f"sums must be a contiguous int64 [{N}, {Cg}] tensor on {dev}; got "
+                         f"{getattr(sums, 'dtype', type(sums))} {tuple(getattr(sums, 'shape', ()))}")
+    if not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != dev:
+        raise ValueError(f"flag must be an int32 [1] tensor on {dev}")
+
+
+def finish_grad(vol, sums, flag, quantum=QUANTUM, clear=False):
+    """fp32 [nx, ny, nz, C], the gradient of march_rays_grad's scalar with respect to vol.data (pn_volume_grad_finish):
+    float(sums quantum) in the sigma and coefficient channels, 0 in the attribute channels, and NaN everywhere if the flag
+    is set: a poisoned backward, visible downstream without a host synchronisation here.  clear=True zeroes sums and the
+    flag on the way, ready for the next step."""
+    Cg = _dense(vol, "finish_grad")
+    quantum = _quantum(quantum)
+    dev = vol.device
+    N = vol.resolution[0] * vol.resolution[1] * vol.resolution[2]
+    _check_workspace(sums, flag, N, Cg, dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        grad = torch.empty(*vol.resolution, vol.channels, dtype=torch.float32, device=dev)
+        _lib.call("pn_volume_grad_finish", N, vol.channels, Cg, sums.data_ptr(), quantum, flag.data_ptr(), grad.data_ptr(),
+                  int(bool(clear)), _lib.stream(dev))
+    return grad
+
+
+class _MarchRaysAD(torch.autograd.Function):
+    """march_rays with a gradient for vol.data: forward is march_rays (the same bits), backward march_rays_grad +
+    finish_grad at the default quantum."""
+
+    @staticmethod
+    def forward(ctx, data, vol, origins, directions, near, far, step, t_min, skip, outputs):
+        got = march_rays(vol, origins, directions, near, far, step, t_min, skip, outputs)
+        ctx.save_for_backward(data)  # an in-place edit of the volume before backward() raises there
+        ctx.vol, ctx.rays, ctx.params, ctx.outputs = vol, (origins, directions, near, far), (step, t_min, skip), outputs
+        ctx.occ = vol.occupancy if skip else None  # the table this pass marched with
+        flat = tuple(got[k] for k in outputs)
+        ctx.mark_non_differentiable(*[t for k, t in zip(outputs, flat) if k not in ("rgb", "acc")])
+        return flat
+
+    @staticmethod
+    def backward(ctx, *grads):
+        (data,) = ctx.saved_tensors
+        vol = ctx.vol
+        if data.data_ptr() != vol.data.data_ptr():
+            raise RuntimeError("the volume's data tensor was replaced between march_rays_ad and backward()")
+        g = dict(zip(ctx.outputs, grads))
+        step, t_min, skip = ctx.params
+        occ, vol._occ = vol._occ, ctx.occ if skip else vol._occ
+        try:
+            sums, flag = march_rays_grad(vol, *ctx.rays, g.get("rgb"), g.get("acc"), step, t_min, skip)
+        finally:
+            vol._occ = occ
+        return (finish_grad(vol, sums, flag),) + (None,) * 9
+
+
+def march_rays_ad(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=True, outputs=("rgb", "acc")):
+    """march_rays as a torch.autograd.Function: the same dict of the same bits, with rgb and acc differentiable with respect
+    to vol.data (only: rays and attributes get no gradient), so vol.data.requires_grad_() works with any torch loss and
+    optimiser.  Dense volumes only.  The gradient is the one of march_rays_grad + finish_grad at the default quantum; it
+    is all NaN if the flag was set.  vol.data is saved through save_for_backward, so an in-place edit between the two
+    passes raises in backward(), and the backward marches with the occupancy table the forward used.  With
+    vol.data.requires_grad, asking for depth or an attribute raises: they have no backward here."""
+    _dense(vol, "march_rays_ad")
+    outputs = tuple(outputs)
+    if vol.data.requires_grad:
+        bad = [k for k in outputs if k not in ("rgb", "acc")]
+        if bad:
+            raise ValueError(f"{bad} have no gradient: with vol.data.requires_grad, outputs must be a subset of "
+                             "('rgb', 'acc')")
+    flat = _MarchRaysAD.apply(vol.data, vol, origins, directions, near, far, step, t_min, skip, outputs)
+    return dict(zip(outputs, flat))
+
+
+def fit_volume(vol, images, camera, poses, steps, batch_rays=4096, lr_sigma=None, lr_coeff=None, loss=None, near=0.0,
+               far=10.0, step=None, t_min=1e-3, seed=0, callback=None):
+    """Fit a dense RadianceVolume, in place, to images [V, 3, H, W] (render_view's fine_rgb, render_volume's rgb or captured
+    HDR frames: no model is needed) seen through `camera` at poses [V, 4, 4]: `steps` steps of Adam on batches of
+    batch_rays pixels drawn by a rays.RayPool over CameraRig(camera, poses) with a generator seeded by `seed`.
+
+    loss None is the mean squared error on rgb, whose gradient (pred - target) (2 / (3 B)) is written out; a callable
+    loss(pred_rgb [B, 3], pred_acc [B, 1], target [B, 3]) -> scalar is differentiated by torch.  Each step: march_rays,
+    the upstream gradients, march_rays_grad into one reused workspace, finish_grad(clear=True), then Adam (beta 0.9 /
+    0.999, eps 1e-8, bias-corrected) in tensor ops with the rate lr_sigma / |box diagonal| for sigma (so lr_sigma is
+    scale-free: optical depth per box diagonal) and lr_coeff for the coefficients; the attribute channels are not
+    touched.  None: LR_SIGMA and LR_COEFF, conventions.  Then sigma.clamp_(min=0) and vol.refresh(): the occupancy depends
+    on sigma > 0.  Nothing synchronises with the host per step; every 100 steps and at the end the overflow flags seen
+    so far are read together with the step's loss, and a set flag raises.  callback(step, loss_value) is called at those
+    checks.  Returns the list of the checked (step, loss) pairs.  A fitted volume no longer is bake_volume's bits, and
+    the sigma_min bound on what pruning removed no longer describes it."""
+    Cg = _dense(vol, "fit_volume")
+    camera = _camera(camera)
+    dev = vol.device
+    steps = int(steps)
+    B = int(batch_rays)
+    if steps < 0 or B < 1:
+        raise ValueError(f"steps must be >= 0 and batch_rays >= 1; got {steps!r}, {batch_rays!r}")
+    c2ws = _c2w_stack(poses)
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or tuple(images.shape) != (c2ws.shape[0], 3, camera.h,
+                                                                                          camera.w):
+        raise ValueError(f"images must be a [{c2ws.shape[0]}, 3, {camera.h}, {camera.w}] tensor; got "
+                         f"{tuple(getattr(images, 'shape', ()))}")
+    diag = math.sqrt(sum((h - l) ** 2 for l, h in zip(*vol.bounds)))
+    lr = torch.full((Cg,), LR_COEFF if lr_coeff is None else float(lr_coeff), dtype=torch.float32, device=dev)
+    lr[0] = (LR_SIGMA if lr_sigma is None else float(lr_sigma)) / diag
+    b1, b2, eps = _ADAM
+    checks = []
+    with torch.cuda.device(dev):
+        with torch.no_grad():
+            pool = RayPool(CameraRig(camera, c2ws, dev), images.detach().to(dev, torch.float32).permute(0, 2, 3, 1), near, far)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+            par = vol.data.view(-1, vol.channels)[:, :Cg]  # a view: sigma and the coefficients
+            m, v = torch.zeros_like(par), torch.zeros_like(par)
+            sums = torch.zeros(par.shape[0], Cg, dtype=torch.int64, device=dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            seen = torch.zeros(1, dtype=torch.int32, device=dev)
+        for it in range(1, steps + 1):
+            with torch.no_grad():
+                rays, target = pool.sample(B, gen)
+                rows = (rays.origins, rays.directions, rays.near, rays.far)
+                pred = march_rays(vol, *rows, step, t_min, True, ("rgb", "acc"))
+            if loss is None:
+                with torch.no_grad():
+                    diff = pred["rgb"] - target
+                    value = (diff * diff).mean()
+                    g_rgb, g_acc = diff * (2.0 / (3 * B)), None
+            else:
+                p_rgb, p_acc = pred["rgb"].requires_grad_(), pred["acc"].requires_grad_()
+                value = loss(p_rgb, p_acc, target)
+                g_rgb, g_acc = torch.autograd.grad(value, (p_rgb, p_acc), allow_unused=True)
+                value = value.detach()
+            with torch.no_grad():
+                march_rays_grad(vol, *rows, g_rgb, g_acc, step, t_min, True, QUANTUM, sums, flag)
+                seen |= flag
+                g = finish_grad(vol, sums, flag, QUANTUM, clear=True).view(-1, vol.channels)[:, :Cg]
+                m = b1 * m + (1.0 - b1) * g
+                v = b2 * v + (1.0 - b2) * (g * g)
+                par.sub_(lr * ((m / (1.0 - b1 ** it)) / ((v / (1.0 - b2 ** it)).sqrt() + eps)))
+                vol.sigma.clamp_(min=0)
+                vol.refresh()
+                if it % 100 == 0 or it == steps:
+                    if int(seen):
+                        raise RuntimeError(f"fit_volume: a gradient contribution was not finite or reached 2^52 quanta of "
+                                           f"quantum = 2^-40 by step {it}; the volume now holds NaNs.  Scale the loss down")
+                    checks.append((it, float(value)))
+                    if callback is not None:
+                        callback(it, checks[-1][1])
+    return checks
