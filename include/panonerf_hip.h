@@ -164,6 +164,13 @@ int pn_density_grad(int64_t M, int num_density_channels, float density_bias, con
  * n_deferred (<= 2) and, per deferred evaluation, its M, enc, acts, rsweep (or null), work and whether it ran the
  * tangent sweep (host arrays), and reduces everything.  M_batched = total rows of those GEMMs (own + deferred, tangent
  * rows counted) sizes the slab part of `work` (0 = stand-alone).
+ * The kept head of `work`, which a later call reads through dwork_host and which holds these results after every call
+ * (Mp = pn_pad_rows(M), rows >= M are not written), in this order from its first float:
+ *   delta [9][Mp][256]  d loss / d pre-activation of h0..h7; slot 8: the density-head addend d_raw_density * Wd
+ *   tang  [8][Mp][256]  the tangent sweep hdot_0..hdot_7 (written only with v_gradmean)
+ *   d_bott   [Mp][256]  d loss / d bottleneck
+ *   edot     [Mp][96]   the tangent of the encoding along v_gradmean (written only with v_gradmean)
+ * Everything behind it is scratch whose layout is private to the call.
  * side_stream (nullable): a second hipStream_t; when given, the weight-gradient GEMMs / reductions run there,
  * forked from and joined back to `stream` with events inside the call, so they overlap the data-gradient chain. */
 int64_t pn_mlp_backward_work_floats(int64_t M, int rows_per_ray, int64_t view_rows, int64_t M_batched);
