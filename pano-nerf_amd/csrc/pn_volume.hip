@@ -40,6 +40,12 @@ constexpr int kCopyThreads = 256;                   // pack and unpack
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
+// bricks along an axis of n vertices (n - 1 cells), and the index of the brick of cell c in the [nbx, nby, nbz] tables
+__host__ __device__ __forceinline__ int bricks_along(int n) { return (n + kBrick - 2) >> kShift; }
+__device__ __forceinline__ int64_t brick_of(const int (&c)[3], const int (&n)[3]) {
+    return ((int64_t)(c[0] >> kShift) * bricks_along(n[1]) + (c[1] >> kShift)) * bricks_along(n[2]) + (c[2] >> kShift);
+}
+
 // ---------------------------------------------------------------------------------------------------------- occupancy
 // one wave per brick: the lanes stride over the brick's (up to 9^3) vertices; a brick is occupied iff one has sigma > 0
 __global__ __launch_bounds__(kThreads) void k_volume_occupancy(int nx, int ny, int nz, int C, const float* __restrict__ data,
@@ -135,9 +141,7 @@ struct DenseStore {
     };
     __device__ __forceinline__ bool jumps() const { return occ != nullptr; }
     __device__ __forceinline__ bool present(const int (&c)[3], const int (&n)[3], Tap&) const {
-        if (!occ) return true;
-        const int nb1 = (n[1] + kBrick - 2) >> kShift, nb2 = (n[2] + kBrick - 2) >> kShift;
-        return occ[((int64_t)(c[0] >> kShift) * nb1 + (c[1] >> kShift)) * nb2 + (c[2] >> kShift)] != 0;
+        return !occ || occ[brick_of(c, n)] != 0;
     }
     __device__ __forceinline__ void locate(const int (&c)[3], const int (&n)[3], int C, Tap& tap) const {
         const int64_t base = ((int64_t)c[0] * n[1] + c[1]) * n[2] + c[2];
@@ -160,8 +164,7 @@ struct BrickStore {
     };
     __device__ __forceinline__ bool jumps() const { return skip != 0; }
     __device__ __forceinline__ bool present(const int (&c)[3], const int (&n)[3], Tap& tap) const {
-        const int nb1 = (n[1] + kBrick - 2) >> kShift, nb2 = (n[2] + kBrick - 2) >> kShift;
-        tap.base = table[((int64_t)(c[0] >> kShift) * nb1 + (c[1] >> kShift)) * nb2 + (c[2] >> kShift)];
+        tap.base = table[brick_of(c, n)];
         return tap.base >= 0;
     }
     __device__ __forceinline__ void locate(const int (&c)[3], const int (&)[3], int C, Tap& tap) const {
@@ -175,19 +178,6 @@ struct BrickStore {
     }
 };
 
-template <class Store>
-struct MarchArgs {
-    int64_t R;
-    int n[3];  // vertices per axis
-    int E;     // attribute channels
-    Store store;
-    double lo[3], st[3];
-    const float *origins, *directions, *near, *far;
-    double step, t_min;
-    float *rgb, *depth, *acc, *attrs;
-    int32_t* taps;  // [R, 2]: trilinear taps taken for sigma, and of those the ones that went on to the colour
-};
-
 __device__ __forceinline__ bool finite_d(double x) { return x - x == 0.0; }
 
 // the last point to skip, from the lattice position s of an exit plane: floor(s) held to [k, n - 1]; a NaN proposes k
@@ -197,197 +187,6 @@ __device__ __forceinline__ int propose(double s, int k, int n) {
     return (int)floor(s);
 }
 
-template <class Store, int kDeg, int kEmax>
-__global__ __launch_bounds__(kThreads) void k_volume_march(MarchArgs<Store> a) {
-    constexpr int K = (kDeg + 1) * (kDeg + 1);
-    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (r >= a.R) return;
-    const int C = 1 + 3 * K + a.E;
-    double o[3], d[3];
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-        o[x] = (double)a.origins[3 * r + x];
-        d[x] = (double)a.directions[3 * r + x];
-    }
-    const double tn = (double)a.near[r], tf = (double)a.far[r];
-    bool valid = finite_d(tn) && finite_d(tf);
-#pragma unroll
-    for (int x = 0; x < 3; ++x) valid = valid && finite_d(o[x]) && finite_d(d[x]);
-    const double len = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    valid = valid && len > 0.0 && tf > tn;
-    double dt = 0.0, nd = 0.0;
-    if (valid) {
-        dt = a.step / len;
-        nd = ceil((tf - tn) / dt);
-        valid = nd < 2147483648.0;  // an infinite or NaN count fails too
-    }
-    double rgb[3] = {0.0, 0.0, 0.0}, at[kEmax > 0 ? kEmax : 1], acc = 0.0, wt = 0.0;
-#pragma unroll
-    for (int e = 0; e < kEmax; ++e) at[e] = 0.0;
-    float depth = 0.f;
-    int n_sigma = 0, n_colour = 0;
-    if (valid) {
-        const int n = (int)nd;
-        const double stepw = dt * len;
-        double Y[K];
-        sh_basis<kDeg>(d[0] / len, d[1] / len, d[2] / len, Y);
-        // the grid coordinate of axis x at lattice point kk: THE sampling formula, also what every jump is checked with
-        auto coord = [&](int x, int kk) -> double {
-            const double t = tn + ((double)kk + 0.5) * dt;
-            return ((o[x] + t * d[x]) - a.lo[x]) / a.st[x];
-        };
-        // the lattice position of the plane g_x = p: (t_plane - near) / dt - 0.5 (callers have d[x] != 0)
-        auto plane = [&](int x, double p) -> double {
-            return ((((a.lo[x] + p * a.st[x]) - o[x]) / d[x]) - tn) / dt - 0.5;
-        };
-        double T = 1.0;
-        int k = 0;
-        while (k < n) {
-            const double t = tn + ((double)k + 0.5) * dt;
-            double g[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) g[x] = ((o[x] + t * d[x]) - a.lo[x]) / a.st[x];
-            // ---- outside the box: nothing to add; jump to the face ahead, or stop if the ray only moves away
-            bool outside = false, gone = false;
-            int kl = k;
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                const double top = (double)(a.n[x] - 1);
-                const bool low = !(g[x] >= 0.0), high = g[x] > top;
-                if (low || high) {
-                    outside = true;
-                    if (low ? !(d[x] > 0.0) : !(d[x] < 0.0)) {
-                        gone = true;  // monotone coordinates: no later point comes back
-                    } else {
-                        int c = propose(plane(x, low ? 0.0 : top), k, n);
-#pragma unroll 1
-                        for (int tries = 0; tries < 2 && c > k; ++tries) {
-                            const double gc = coord(x, c);
-                            if (low ? !(gc >= 0.0) : gc > top) break;
-                            c = tries == 0 ? c - 1 : k;
-                        }
-                        kl = c > kl ? c : kl;
-                    }
-                }
-            }
-            if (gone) break;
-            if (outside) {
-                k = kl + 1;
-                continue;
-            }
-            // ---- the cell: g in [0, n - 1] on every axis, so 0 <= c <= n - 2 and every corner c, c + 1 is a vertex
-            int c[3];
-            double f[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                const double fl = floor(g[x]);
-                c[x] = imin((int)fl, a.n[x] - 2);
-                f[x] = g[x] - (double)c[x];
-            }
-            typename Store::Tap tap;
-            if (!a.store.present(c, a.n, tap)) {
-                if (Store::kBricks && !a.store.jumps()) {  // an absent brick without jumps: one sigma tap of value 0
-                    ++n_sigma;
-                    ++k;
-                    continue;
-                }
-                // every cell of this brick has corners <= 0 or NaN only: skip to the last lattice point still in it
-                const int b[3] = {c[0] >> kShift, c[1] >> kShift, c[2] >> kShift};
-                double s = (double)(n - 1);
-#pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    if (d[x] != 0.0) {  // an axis the ray does not move along never leaves the brick: no division
-                        const int up = imin((b[x] + 1) * kBrick, a.n[x] - 1);
-                        const double sx = plane(x, d[x] > 0.0 ? (double)up : (double)(b[x] * kBrick));
-                        s = sx < s ? sx : s;
-                    }
-                }
-                int cand = propose(s, k, n);
-#pragma unroll 1
-                for (int tries = 0; tries < 2 && cand > k; ++tries) {
-                    bool same = true;
-#pragma unroll
-                    for (int x = 0; x < 3; ++x) {
-                        const double gc = coord(x, cand);
-                        const bool in = gc >= 0.0 && gc <= (double)(a.n[x] - 1);
-                        const int cc = in ? imin((int)floor(gc), a.n[x] - 2) : -kBrick;
-                        same = same && (cc >> kShift) == b[x];
-                    }
-                    if (same) break;
-                    cand = tries == 0 ? cand - 1 : k;
-                }
-                k = cand + 1;
-                continue;
-            }
-            // ---- the trilinear tap: weights (wx wy) wz, corners in the order i, j, k, low corner first
-            double w[8];
-            a.store.locate(c, a.n, C, tap);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int qi = q >> 2, qj = (q >> 1) & 1, qk = q & 1;
-                w[q] = ((qi ? f[0] : 1.0 - f[0]) * (qj ? f[1] : 1.0 - f[1])) * (qk ? f[2] : 1.0 - f[2]);
-            }
-            ++n_sigma;
-            double sigma = 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) sigma = sigma + w[q] * a.store.value(tap, q, 0);
-            if (!(sigma > 0.0)) {
-                ++k;
-                continue;
-            }
-            ++n_colour;
-            double col[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < K; ++kk) {
-                double tri[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) tri[ch] = tri[ch] + w[q] * a.store.value(tap, q, 1 + 3 * kk + ch);
-                }
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) col[ch] = col[ch] + Y[kk] * tri[ch];
-            }
-            const double alpha = 1.0 - exp(-sigma * stepw);
-            const double wgt = T * alpha;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + wgt * (col[ch] > 0.0 ? col[ch] : 0.0);
-#pragma unroll
-            for (int e = 0; e < kEmax; ++e) {
-                if (e < a.E) {
-                    double tri = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) tri = tri + w[q] * a.store.value(tap, q, 1 + 3 * K + e);
-                    at[e] = at[e] + wgt * tri;
-                }
-            }
-            acc = acc + wgt;
-            wt = wt + wgt * t;
-            T = T * (1.0 - alpha);
-            if (T < a.t_min) break;
-            ++k;
-        }
-        double q = wt / acc;
-        if (q != q) q = 0.0;
-        q = q > tn ? q : tn;
-        q = q < tf ? q : tf;
-        depth = (float)q;
-    }
-    if (a.rgb) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) a.rgb[3 * r + ch] = (float)rgb[ch];
-    }
-    if (a.depth) a.depth[r] = depth;
-    if (a.acc) a.acc[r] = (float)acc;
-    if (a.taps) a.taps[2 * r] = n_sigma, a.taps[2 * r + 1] = n_colour;
-    if (kEmax > 0 && a.attrs) {
-#pragma unroll
-        for (int e = 0; e < kEmax; ++e)
-            if (e < a.E) a.attrs[(int64_t)a.E * r + e] = (float)at[e];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------- gradients
 // what the marching loop reads: the volume, the rays and the two march parameters
 template <class Store>
 struct MarchRows {
@@ -398,6 +197,12 @@ struct MarchRows {
     double lo[3], st[3];
     const float *origins, *directions, *near, *far;
     double step, t_min;
+};
+
+// what the forward writes; a null output is not asked for
+struct MarchOut {
+    float *rgb, *depth, *acc, *attrs;
+    int32_t* taps;  // [R, 2]: trilinear taps taken for sigma, and of those the ones that went on to the colour
 };
 
 // the reverse sweep's extra arguments (header, "radiance volume: gradients")
@@ -441,14 +246,16 @@ __device__ __forceinline__ Row load_row(const MarchRows<Store>& a, int64_t r) {
     return row;
 }
 
-// k_volume_march's loop over a valid row, statement for statement (lattice, gates, jumps, early stop) without the tap
-// counters: hoisting the forward's own body into this template moved its register counts (DenseStore, degree 0, with
-// attributes: 167 -> 169 VGPRs, one wave per SIMD fewer), so the forward keeps its loop and the two passes of the reverse
-// sweep share this copy.  Every sample that composites (sigma > 0) is handed to on_sample(c, w, s, alpha, wgt, T): the
-// cell, the corner weights, the unclamped colour sums s_c, and T before the sample.
-template <int kDeg, class Store, class F>
+// The lattice loop of every marcher, forward and reverse, over a valid row: gates, jumps, early stop.  on_tap() is called
+// for every sigma tap (an absent brick without jumps, and each interpolated sigma); every sample that composites
+// (sigma > 0) is handed to on_sample(c, w, tap, t, s, alpha, wgt, T): the cell, the corner weights, the located tap, the
+// sample's t, the unclamped colour sums s_c, and T before the sample.
+// Registers: inlined into k_volume_march the loop takes the dense degree-0 instance with attributes from 167 to 169 VGPRs,
+// past the 168 of three waves per SIMD.  The forward's degree-0 instances hold the step by not carrying `far` through the
+// loop: they read it again for the depth clamp.  profiles/volume_refactor.txt has every instance's registers and timings.
+template <int kDeg, class Store, class FT, class FS>
 __device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& row,
-                                          const double (&Y)[(kDeg + 1) * (kDeg + 1)], F&& on_sample) {
+                                          const double (&Y)[(kDeg + 1) * (kDeg + 1)], FT&& on_tap, FS&& on_sample) {
     constexpr int K = (kDeg + 1) * (kDeg + 1);
     const int C = 1 + 3 * K + a.E;
     const double(&o)[3] = row.o;
@@ -512,7 +319,8 @@ __device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& 
             }
             typename Store::Tap tap;
             if (!a.store.present(c, a.n, tap)) {
-                if (Store::kBricks && !a.store.jumps()) {  // an absent brick without jumps: a sigma of 0
+                if (Store::kBricks && !a.store.jumps()) {  // an absent brick without jumps: one sigma tap of value 0
+                    on_tap();
                     ++k;
                     continue;
                 }
@@ -552,6 +360,7 @@ __device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& 
                 const int qi = q >> 2, qj = (q >> 1) & 1, qk = q & 1;
                 w[q] = ((qi ? f[0] : 1.0 - f[0]) * (qj ? f[1] : 1.0 - f[1])) * (qk ? f[2] : 1.0 - f[2]);
             }
+            on_tap();
             double sigma = 0.0;
 #pragma unroll
             for (int q = 0; q < 8; ++q) sigma = sigma + w[q] * a.store.value(tap, q, 0);
@@ -573,7 +382,7 @@ __device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& 
             }
             const double alpha = 1.0 - exp(-sigma * stepw);
             const double wgt = T * alpha;
-            on_sample(c, w, col, alpha, wgt, T);
+            on_sample(c, w, tap, t, col, alpha, wgt, T);
             T = T * (1.0 - alpha);
             if (T < a.t_min) break;
             ++k;
@@ -581,6 +390,65 @@ __device__ __forceinline__ void march_row(const MarchRows<Store>& a, const Row& 
     }
 }
 
+template <class Store, int kDeg, int kEmax>
+__global__ __launch_bounds__(kThreads) void k_volume_march(MarchRows<Store> a, MarchOut out) {
+    constexpr int K = (kDeg + 1) * (kDeg + 1);
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= a.R) return;
+    const Row row = load_row(a, r);
+    double rgb[3] = {0.0, 0.0, 0.0}, at[kEmax > 0 ? kEmax : 1], acc = 0.0, wt = 0.0;
+#pragma unroll
+    for (int e = 0; e < kEmax; ++e) at[e] = 0.0;
+    float depth = 0.f;
+    int n_sigma = 0, n_colour = 0;
+    if (row.valid) {
+        double Y[K];
+        sh_basis<kDeg>(row.d[0] / row.len, row.d[1] / row.len, row.d[2] / row.len, Y);
+        march_row<kDeg>(
+            a, row, Y, [&] { ++n_sigma; },
+            [&](const int(&)[3], const double(&w)[8], const typename Store::Tap& tap, double t, const double(&s)[3], double,
+                double wgt, double) {
+                ++n_colour;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + wgt * (s[ch] > 0.0 ? s[ch] : 0.0);
+#pragma unroll
+                for (int e = 0; e < kEmax; ++e) {
+                    if (e < a.E) {
+                        double tri = 0.0;
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) tri = tri + w[q] * a.store.value(tap, q, 1 + 3 * K + e);
+                        at[e] = at[e] + wgt * tri;
+                    }
+                }
+                acc = acc + wgt;
+                wt = wt + wgt * t;
+            });
+        double q = wt / acc;
+        if (q != q) q = 0.0;
+        q = q > row.tn ? q : row.tn;
+        // Degree 0 reads `far` again (volatile, or the compiler keeps the first load live) so that it is not carried through
+        // the loop: the same value, two VGPRs fewer.  It holds the instances with attributes at 167 / 167 / 155 VGPRs (dense,
+        // fp32, fp16 bricks), three waves per SIMD; without it the dense and the fp32-brick one take 169 and lose a wave.
+        // The allocator decides this, not the language: after a compiler change, check those numbers in the resource report.
+        const double tf = kDeg == 0 ? (double)*(const volatile float*)(a.far + r) : row.tf;
+        q = q < tf ? q : tf;
+        depth = (float)q;
+    }
+    if (out.rgb) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) out.rgb[3 * r + ch] = (float)rgb[ch];
+    }
+    if (out.depth) out.depth[r] = depth;
+    if (out.acc) out.acc[r] = (float)acc;
+    if (out.taps) out.taps[2 * r] = n_sigma, out.taps[2 * r + 1] = n_colour;
+    if (kEmax > 0 && out.attrs) {
+#pragma unroll
+        for (int e = 0; e < kEmax; ++e)
+            if (e < a.E) out.attrs[(int64_t)a.E * r + e] = (float)at[e];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- gradients
 // The reverse of the compositing sweep (header, "radiance volume: gradients"): one ray per thread as in the forward, two
 // runs of march_row.  Pass 1 sums U = sum wgt u over the row; pass 2 carries the prefix P, so that U - P is what the
 // samples behind this one still add, and scatters 8 (1 + 3 K) contributions per sample as 64-bit integers of `quantum`:
@@ -619,13 +487,15 @@ __global__ __launch_bounds__(kThreads) void k_volume_march_bwd(MarchRows<DenseSt
         return ((gc[0] * c0 + gc[1] * c1) + gc[2] * c2) + ga;
     };
     double U = 0.0;
-    march_row<kDeg>(a, row, Y, [&](const int(&)[3], const double(&)[8], const double(&s)[3], double, double wgt, double) {
-        U = U + wgt * upstream(s);
-    });
+    const auto no_tap = [] {};
+    march_row<kDeg>(a, row, Y, no_tap,
+                    [&](const int(&)[3], const double(&)[8], const DenseStore::Tap&, double, const double(&s)[3], double,
+                        double wgt, double) { U = U + wgt * upstream(s); });
     double P = 0.0;
     bool bad = false;
-    march_row<kDeg>(a, row, Y,
-                    [&](const int(&c)[3], const double(&w)[8], const double(&s)[3], double alpha, double wgt, double T) {
+    march_row<kDeg>(a, row, Y, no_tap,
+                    [&](const int(&c)[3], const double(&w)[8], const DenseStore::Tap&, double, const double(&s)[3],
+                        double alpha, double wgt, double T) {
                         const double u = upstream(s);
                         P = P + wgt * u;
                         const double Tn = T * (1.0 - alpha);
@@ -674,15 +544,6 @@ bool grid_ok(int nx, int ny, int nz) {
     return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
 }
 
-template <class Store, int kDeg>
-void launch_march(const MarchArgs<Store>& a, bool attrs, hipStream_t s) {
-    const dim3 grid(nblk(a.R, kThreads)), block(kThreads);
-    if (attrs)
-        hipLaunchKernelGGL((k_volume_march<Store, kDeg, PN_VOLUME_MAX_ATTR>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((k_volume_march<Store, kDeg, 0>), grid, block, 0, s, a);
-}
-
 // the argument checks of every marcher, forward and reverse
 bool rows_ok(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float (&lo)[3], const float (&st)[3], float step,
              float t_min) {
@@ -698,30 +559,52 @@ bool quantum_ok(double quantum) {
     return quantum >= 0x1p-60 && quantum <= 1.0 && frexp(quantum, &e) == 0.5;
 }
 
-// what pn_volume_march and pn_volume_march_sparse share: the argument checks and the dispatch over the SH degree
+// The MarchRows of every marcher, forward and reverse: the checks, then the block the kernels take.  `have`: the caller's
+// own pointers (the store's, the workspace's) are there.  PN_OK with R == 0 leaves nothing to launch.
 template <class Store>
-int march(const Store& store, bool have_store, int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float (&lo)[3],
-          const float (&st)[3], const float* origins, const float* directions, const float* near, const float* far,
-          float step, float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
+int march_rows(MarchRows<Store>& a, const Store& store, bool have, int64_t R, int nx, int ny, int nz, int sh_degree, int E,
+               float x0, float y0, float z0, float dx, float dy, float dz, const float* origins, const float* directions,
+               const float* near, const float* far, float step, float t_min) {
+    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
     if (!rows_ok(R, nx, ny, nz, sh_degree, E, lo, st, step, t_min)) return PN_ERR_BAD_SHAPE;
     if (R == 0) return PN_OK;
-    if (!have_store || !origins || !directions || !near || !far) return PN_ERR_NULL;
-    MarchArgs<Store> a{R, {nx, ny, nz}, E, store, {}, {}, origins, directions, near, far, (double)step, (double)t_min,
-                       rgb, depth, acc, attrs, taps};
+    if (!have || !origins || !directions || !near || !far) return PN_ERR_NULL;
+    a = {R, {nx, ny, nz}, E, store, {}, {}, origins, directions, near, far, (double)step, (double)t_min};
     for (int x = 0; x < 3; ++x) a.lo[x] = (double)lo[x], a.st[x] = (double)st[x];
-    const bool with_attrs = E > 0 && attrs;
+    return PN_OK;
+}
+
+// the marchers are instances over the SH degree: launch(std::integral_constant<int, degree>) of a checked sh_degree
+template <class F>
+void by_degree(int sh_degree, F&& launch) {
     switch (sh_degree) {
-        case 0: launch_march<Store, 0>(a, with_attrs, ST(stream)); break;
-        case 1: launch_march<Store, 1>(a, with_attrs, ST(stream)); break;
-        default: launch_march<Store, 2>(a, with_attrs, ST(stream)); break;
+        case 0: launch(std::integral_constant<int, 0>{}); break;
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        default: launch(std::integral_constant<int, 2>{}); break;
     }
+}
+
+// what pn_volume_march and pn_volume_march_sparse share
+template <class Store>
+int march(const Store& store, bool have_store, int64_t R, int nx, int ny, int nz, int sh_degree, int E, float x0, float y0,
+          float z0, float dx, float dy, float dz, const float* origins, const float* directions, const float* near,
+          const float* far, float step, float t_min, const MarchOut& out, void* stream) {
+    MarchRows<Store> a;
+    const int rc = march_rows(a, store, have_store, R, nx, ny, nz, sh_degree, E, x0, y0, z0, dx, dy, dz, origins, directions,
+                              near, far, step, t_min);
+    if (rc != PN_OK || R == 0) return rc;
+    const dim3 grid(nblk(R, kThreads)), block(kThreads);
+    by_degree(sh_degree, [&](auto deg) {
+        if (E > 0 && out.attrs)
+            hipLaunchKernelGGL((k_volume_march<Store, deg.value, PN_VOLUME_MAX_ATTR>), grid, block, 0, ST(stream), a, out);
+        else
+            hipLaunchKernelGGL((k_volume_march<Store, deg.value, 0>), grid, block, 0, ST(stream), a, out);
+    });
     PN_CHECK_LAUNCH();
     return PN_OK;
 }
 
-int64_t brick_count(int nx, int ny, int nz) {
-    return (int64_t)((nx + kBrick - 2) >> kShift) * ((ny + kBrick - 2) >> kShift) * ((nz + kBrick - 2) >> kShift);
-}
+int64_t brick_count(int nx, int ny, int nz) { return (int64_t)bricks_along(nx) * bricks_along(ny) * bricks_along(nz); }
 
 // the checks pack and unpack share; B 729 C < 2^40 keeps every value index far inside 64 bits
 bool pool_ok(int nx, int ny, int nz, int channels, int64_t B) {
@@ -741,9 +624,9 @@ int64_t pn_volume_bricks(int nx, int ny, int nz) {
 int pn_volume_occupancy(int nx, int ny, int nz, int channels, const float* data, uint8_t* occupancy, void* stream) {
     if (!grid_ok(nx, ny, nz) || channels < 1) return PN_ERR_BAD_SHAPE;
     if (!data || !occupancy) return PN_ERR_NULL;
-    const int nby = (ny + kBrick - 2) >> kShift, nbz = (nz + kBrick - 2) >> kShift;
-    const dim3 grid((unsigned)pn_volume_bricks(nx, ny, nz)), block(kThreads);
-    hipLaunchKernelGGL(k_volume_occupancy, grid, block, 0, ST(stream), nx, ny, nz, channels, data, nby, nbz, occupancy);
+    const dim3 grid((unsigned)brick_count(nx, ny, nz)), block(kThreads);
+    hipLaunchKernelGGL(k_volume_occupancy, grid, block, 0, ST(stream), nx, ny, nz, channels, data, bricks_along(ny),
+                       bricks_along(nz), occupancy);
     PN_CHECK_LAUNCH();
     return PN_OK;
 }
@@ -752,29 +635,23 @@ int pn_volume_march(int64_t R, int nx, int ny, int nz, int sh_degree, int E, con
                     float x0, float y0, float z0, float dx, float dy, float dz, const float* origins,
                     const float* directions, const float* near, const float* far, float step, float t_min, float* rgb,
                     float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
-    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
-    return march(DenseStore{data, occupancy}, data != nullptr, R, nx, ny, nz, sh_degree, E, lo, st, origins, directions, near,
-                 far, step, t_min, rgb, depth, acc, attrs, taps, stream);
+    return march(DenseStore{data, occupancy}, data != nullptr, R, nx, ny, nz, sh_degree, E, x0, y0, z0, dx, dy, dz, origins,
+                 directions, near, far, step, t_min, {rgb, depth, acc, attrs, taps}, stream);
 }
 
 int pn_volume_march_bwd(int64_t R, int nx, int ny, int nz, int sh_degree, int E, const float* data, const uint8_t* occupancy,
                         float x0, float y0, float z0, float dx, float dy, float dz, const float* origins,
                         const float* directions, const float* near, const float* far, float step, float t_min,
                         const float* g_rgb, const float* g_acc, double quantum, int64_t* sums, int32_t* flag, void* stream) {
-    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
-    if (!rows_ok(R, nx, ny, nz, sh_degree, E, lo, st, step, t_min) || !quantum_ok(quantum)) return PN_ERR_BAD_SHAPE;
-    if (R == 0) return PN_OK;
-    if (!data || !origins || !directions || !near || !far || !sums || !flag) return PN_ERR_NULL;
-    MarchRows<DenseStore> a{R, {nx, ny, nz}, E, DenseStore{data, occupancy}, {}, {}, origins, directions, near, far,
-                            (double)step, (double)t_min};
-    for (int x = 0; x < 3; ++x) a.lo[x] = (double)lo[x], a.st[x] = (double)st[x];
+    if (!quantum_ok(quantum)) return PN_ERR_BAD_SHAPE;
+    MarchRows<DenseStore> a;
+    const int rc = march_rows(a, DenseStore{data, occupancy}, data && sums && flag, R, nx, ny, nz, sh_degree, E, x0, y0, z0, dx,
+                              dy, dz, origins, directions, near, far, step, t_min);
+    if (rc != PN_OK || R == 0) return rc;
     const GradArgs g{g_rgb, g_acc, 1.0 / quantum, (long long*)sums, flag};
     const dim3 grid(nblk(R, kThreads)), block(kThreads);
-    switch (sh_degree) {
-        case 0: hipLaunchKernelGGL(k_volume_march_bwd<0>, grid, block, 0, ST(stream), a, g); break;
-        case 1: hipLaunchKernelGGL(k_volume_march_bwd<1>, grid, block, 0, ST(stream), a, g); break;
-        default: hipLaunchKernelGGL(k_volume_march_bwd<2>, grid, block, 0, ST(stream), a, g); break;
-    }
+    by_degree(sh_degree,
+              [&](auto deg) { hipLaunchKernelGGL(k_volume_march_bwd<deg.value>, grid, block, 0, ST(stream), a, g); });
     PN_CHECK_LAUNCH();
     return PN_OK;
 }
@@ -803,7 +680,7 @@ int pn_volume_pack(int nx, int ny, int nz, int channels, const int32_t* table, i
     if (!table || !(dense || by_rows) || (by_rows && (!vertex_row || (M > 0 && !rows)))) return PN_ERR_NULL;
     if (B == 0) return PN_OK;
     if (!pool) return PN_ERR_NULL;
-    const int nby = (ny + kBrick - 2) >> kShift, nbz = (nz + kBrick - 2) >> kShift;
+    const int nby = bricks_along(ny), nbz = bricks_along(nz);
     const dim3 grid((unsigned)brick_count(nx, ny, nz)), block(kCopyThreads);
     if (half)
         hipLaunchKernelGGL(k_volume_pack<_Float16>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B, data, rows, M,
@@ -819,7 +696,7 @@ int pn_volume_unpack(int nx, int ny, int nz, int channels, const int32_t* table,
                      float* data, void* stream) {
     if (!pool_ok(nx, ny, nz, channels, B)) return PN_ERR_BAD_SHAPE;
     if (!table || !data || (B > 0 && !pool)) return PN_ERR_NULL;
-    const int nbx = (nx + kBrick - 2) >> kShift, nby = (ny + kBrick - 2) >> kShift, nbz = (nz + kBrick - 2) >> kShift;
+    const int nbx = bricks_along(nx), nby = bricks_along(ny), nbz = bricks_along(nz);
     const dim3 grid(nblk((int64_t)nx * ny * nz, kCopyThreads)), block(kCopyThreads);
     if (half)
         hipLaunchKernelGGL(k_volume_unpack<_Float16>, grid, block, 0, ST(stream), nx, ny, nz, channels, table, B,
@@ -835,12 +712,12 @@ int pn_volume_march_sparse(int64_t R, int nx, int ny, int nz, int sh_degree, int
                            int half, int skip, float x0, float y0, float z0, float dx, float dy, float dz,
                            const float* origins, const float* directions, const float* near, const float* far, float step,
                            float t_min, float* rgb, float* depth, float* acc, float* attrs, int32_t* taps, void* stream) {
-    const float lo[3] = {x0, y0, z0}, st[3] = {dx, dy, dz};
-    if (half)
-        return march(BrickStore<_Float16>{table, (const _Float16*)pool, skip}, table != nullptr, R, nx, ny, nz, sh_degree, E,
-                     lo, st, origins, directions, near, far, step, t_min, rgb, depth, acc, attrs, taps, stream);
-    return march(BrickStore<float>{table, (const float*)pool, skip}, table != nullptr, R, nx, ny, nz, sh_degree, E, lo, st,
-                 origins, directions, near, far, step, t_min, rgb, depth, acc, attrs, taps, stream);
+    const auto go = [&](auto store) {
+        return march(store, table != nullptr, R, nx, ny, nz, sh_degree, E, x0, y0, z0, dx, dy, dz, origins, directions, near,
+                     far, step, t_min, {rgb, depth, acc, attrs, taps}, stream);
+    };
+    return half ? go(BrickStore<_Float16>{table, (const _Float16*)pool, skip})
+                : go(BrickStore<float>{table, (const float*)pool, skip});
 }
 
 }  // extern "C"

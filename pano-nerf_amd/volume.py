@@ -60,7 +60,7 @@ from .rays import CameraRig, RayPool
 
 BRICK = 8          # PN_VOLUME_BRICK
 BRICK_VERTICES = (BRICK + 1) ** 3  # a stored brick: its 8^3 cells' vertices, the shared far faces included
-_SPARSE_FORMAT = "pano_nerf_amd.sparse_radiance_volume"
+_DENSE_FORMAT, _SPARSE_FORMAT = "pano_nerf_amd.radiance_volume", "pano_nerf_amd.sparse_radiance_volume"
 MAX_ATTR = 8       # PN_VOLUME_MAX_ATTR
 GOLDEN_ANGLE = 2.399963229728653  # PN_VOLUME_GOLDEN_ANGLE = pi (3 - sqrt 5)
 _SH_C = (0.28209479177387814, 0.48860251190291992, 1.0925484305920792, 0.31539156525252005, 0.54627421529603959)
@@ -114,6 +114,11 @@ def _attributes(attributes):
     return tuple(out)
 
 
+def _channels(sh_degree, attrs=()):
+    """1 + 3 K + E: sigma, K coefficient triples and the attribute channels"""
+    return 1 + 3 * _sh_count(sh_degree) + sum(w for _, w in attrs)
+
+
 def _bounds(bounds):
     b = tuple(tuple(float(v) for v in c) for c in bounds)
     if len(b) != 2 or len(b[0]) != 3 or len(b[1]) != 3:
@@ -128,39 +133,69 @@ def _grid(bounds, res):
     return lo, step
 
 
+def _device_only(device, what):
+    if device.type != "cuda":
+        raise RuntimeError(f"pano_nerf_amd.volume runs on a HIP device only ({what} on {device}); there is no CPU fallback")
+
+
+class _Header:
+    """What both kinds of volume carry, checked in one place: sh_degree, the attributes (_attrs, attribute_names), the
+    resolution, the bounds, the grid's lo / step and the channel count 1 + 3 K + E."""
+
+    def __init__(self, bounds, resolution, sh_degree, attributes=()):
+        self._attrs = _attributes(attributes)
+        self.channels = _channels(sh_degree, self._attrs)
+        self.sh_degree = int(sh_degree)
+        self.attribute_names = tuple(n for n, _ in self._attrs)
+        self.resolution = _resolution(resolution)
+        self.bounds = _bounds(bounds)
+        self.lo, self.step = _grid(self.bounds, self.resolution)
+
+
 # ------------------------------------------------------------------------------------------------------------ files
+def _write_header(path, fmt, h, mid, tail):
+    """path/volume.json: the fields every volume has, with a format's own fields before (mid) and after (tail) lo / step.
+    Two dicts only because the key order of the files is kept as it was: the sparse format has fields on both sides."""
+    os.makedirs(path, exist_ok=True)
+    meta = dict(format=fmt, version=1, bounds=[list(c) for c in h.bounds], resolution=list(h.resolution),
+                sh_degree=h.sh_degree, attributes=[[n, w] for n, w in h._attrs], channels=h.channels, **mid, lo=list(h.lo),
+                step=list(h.step), **tail)
+    with open(os.path.join(path, "volume.json"), "w") as fh:
+        json.dump(meta, fh, indent=1)
+
+
+def _read_meta(path):
+    with open(os.path.join(path, "volume.json")) as fh:
+        return json.load(fh)
+
+
+def _read_header(path, fmt, what):
+    """-> (the fields of path/volume.json, their _Header); a file of another format or version raises"""
+    meta = _read_meta(path)
+    if meta.get("format") != fmt or meta.get("version") != 1:
+        raise ValueError(f"{path}: not {what} (format {meta.get('format')!r}, version {meta.get('version')!r})")
+    return meta, _Header(meta["bounds"], meta["resolution"], meta["sh_degree"], [tuple(a) for a in meta["attributes"]])
+
+
 def write_volume_files(path, data, bounds, sh_degree, attributes=()):
     """Write a host array data [nx, ny, nz, C] as path/volume.json + path/volume.bin (raw little-endian fp32)."""
     a = np.asarray(data)
-    attrs = _attributes(attributes)
-    if a.ndim != 4 or a.dtype != np.float32 or a.shape[3] != 1 + 3 * _sh_count(sh_degree) + sum(w for _, w in attrs):
+    h = _Header(bounds, a.shape[:3], sh_degree, attributes) if a.ndim == 4 else None
+    if h is None or a.dtype != np.float32 or a.shape[3] != h.channels:
         raise ValueError(f"data must be fp32 [nx, ny, nz, 1 + 3 K + E]; got {a.dtype} {a.shape}")
-    res = _resolution(a.shape[:3])
-    b = _bounds(bounds)
-    lo, step = _grid(b, res)
-    os.makedirs(path, exist_ok=True)
-    meta = dict(format="pano_nerf_amd.radiance_volume", version=1, bounds=[list(c) for c in b], resolution=list(res),
-                sh_degree=int(sh_degree), attributes=[[n, w] for n, w in attrs], channels=int(a.shape[3]), lo=list(lo),
-                step=list(step), dtype="<f4", order="[nx, ny, nz, C], C fastest")
-    with open(os.path.join(path, "volume.json"), "w") as fh:
-        json.dump(meta, fh, indent=1)
+    _write_header(path, _DENSE_FORMAT, h, {}, dict(dtype="<f4", order="[nx, ny, nz, C], C fastest"))
     with open(os.path.join(path, "volume.bin"), "wb") as fh:
         fh.write(np.ascontiguousarray(a, dtype="<f4").tobytes())
 
 
 def read_volume_files(path):
     """-> (data fp32 [nx, ny, nz, C] host array, bounds, sh_degree, attributes) of what write_volume_files wrote"""
-    with open(os.path.join(path, "volume.json")) as fh:
-        meta = json.load(fh)
-    if meta.get("format") != "pano_nerf_amd.radiance_volume" or meta.get("version") != 1:
-        raise ValueError(f"{path}: not a radiance volume (format {meta.get('format')!r}, version {meta.get('version')!r})")
-    res = _resolution(meta["resolution"])
-    attrs = _attributes([tuple(a) for a in meta["attributes"]])
-    C = 1 + 3 * _sh_count(meta["sh_degree"]) + sum(w for _, w in attrs)
+    _, h = _read_header(path, _DENSE_FORMAT, "a radiance volume")
+    res, C = h.resolution, h.channels
     raw = np.fromfile(os.path.join(path, "volume.bin"), dtype="<f4")
     if raw.size != res[0] * res[1] * res[2] * C:
         raise ValueError(f"{path}: volume.bin holds {raw.size} floats, the header asks for {res} x {C}")
-    return raw.astype(np.float32, copy=False).reshape(*res, C), _bounds(meta["bounds"]), int(meta["sh_degree"]), attrs
+    return raw.astype(np.float32, copy=False).reshape(*res, C), h.bounds, h.sh_degree, h._attrs
 
 
 def _brick_counts(res):
@@ -177,25 +212,17 @@ def write_sparse_volume_files(path, table, pool, bounds, resolution, sh_degree, 
     """Write host arrays table int32 [nbx, nby, nbz] and pool fp32 / fp16 [B, 9, 9, 9, C] as path/volume.json +
     path/table.bin (<i4) + path/pool.bin (<f4 or <f2): the layout of include/panonerf_hip.h, "sparse radiance volume"."""
     t, p = np.asarray(table), np.asarray(pool)
-    attrs = _attributes(attributes)
-    res = _resolution(resolution)
-    C = 1 + 3 * _sh_count(sh_degree) + sum(w for _, w in attrs)
+    h = _Header(bounds, resolution, sh_degree, attributes)
+    res, C = h.resolution, h.channels
     if t.dtype != np.int32 or t.shape != _brick_counts(res):
         raise ValueError(f"table must be int32 {_brick_counts(res)} for resolution {res}; got {t.dtype} {t.shape}")
     if p.dtype not in (np.float32, np.float16) or p.ndim != 5 or p.shape[1:] != (BRICK + 1,) * 3 + (C,):
         raise ValueError(f"pool must be fp32 or fp16 [B, 9, 9, 9, 1 + 3 K + E = {C}]; got {p.dtype} {p.shape}")
     if int((t >= 0).sum()) != p.shape[0]:
         raise ValueError(f"table marks {int((t >= 0).sum())} bricks present, the pool holds {p.shape[0]}")
-    b = _bounds(bounds)
-    lo, step = _grid(b, res)
-    os.makedirs(path, exist_ok=True)
     dtype = "<f4" if p.dtype == np.float32 else "<f2"
-    meta = dict(format=_SPARSE_FORMAT, version=1, bounds=[list(c) for c in b], resolution=list(res),
-                sh_degree=int(sh_degree), attributes=[[n, w] for n, w in attrs], channels=C, bricks=int(p.shape[0]),
-                dtype=dtype, lo=list(lo), step=list(step), brick=BRICK,
-                order="table [nbx, nby, nbz] slot or -1; pool [B, 9, 9, 9, C], C fastest")
-    with open(os.path.join(path, "volume.json"), "w") as fh:
-        json.dump(meta, fh, indent=1)
+    _write_header(path, _SPARSE_FORMAT, h, dict(bricks=int(p.shape[0]), dtype=dtype),
+                  dict(brick=BRICK, order="table [nbx, nby, nbz] slot or -1; pool [B, 9, 9, 9, C], C fastest"))
     with open(os.path.join(path, "table.bin"), "wb") as fh:
         fh.write(np.ascontiguousarray(t, dtype="<i4").tobytes())
     with open(os.path.join(path, "pool.bin"), "wb") as fh:
@@ -205,14 +232,8 @@ def write_sparse_volume_files(path, table, pool, bounds, resolution, sh_degree, 
 def read_sparse_volume_files(path):
     """-> (table int32 [nbx, nby, nbz], pool [B, 9, 9, 9, C] fp32 or fp16, bounds, resolution, sh_degree, attributes): host
     arrays of what write_sparse_volume_files wrote"""
-    with open(os.path.join(path, "volume.json")) as fh:
-        meta = json.load(fh)
-    if meta.get("format") != _SPARSE_FORMAT or meta.get("version") != 1:
-        raise ValueError(f"{path}: not a sparse radiance volume (format {meta.get('format')!r}, version "
-                         f"{meta.get('version')!r})")
-    res = _resolution(meta["resolution"])
-    attrs = _attributes([tuple(a) for a in meta["attributes"]])
-    C = 1 + 3 * _sh_count(meta["sh_degree"]) + sum(w for _, w in attrs)
+    meta, h = _read_header(path, _SPARSE_FORMAT, "a sparse radiance volume")
+    res, C = h.resolution, h.channels
     B = int(meta["bricks"])
     if meta.get("dtype") not in ("<f4", "<f2"):
         raise ValueError(f"{path}: the pool's dtype must be '<f4' or '<f2'; got {meta.get('dtype')!r}")
@@ -225,60 +246,52 @@ def read_sparse_volume_files(path):
         raise ValueError(f"{path}: pool.bin holds {pool.size} values, the header asks for {B} x {BRICK_VERTICES} x {C}")
     dtype = np.float32 if meta["dtype"] == "<f4" else np.float16
     return (table.astype(np.int32, copy=False).reshape(nb), pool.astype(dtype, copy=False).reshape(B, *(BRICK + 1,) * 3, C),
-            _bounds(meta["bounds"]), res, int(meta["sh_degree"]), attrs)
+            h.bounds, res, h.sh_degree, h._attrs)
 
 
 def load_volume(path, device=None):
     """RadianceVolume.load or SparseRadianceVolume.load, by the `format` field of path/volume.json"""
-    with open(os.path.join(path, "volume.json")) as fh:
-        fmt = json.load(fh).get("format")
+    fmt = _read_meta(path).get("format")
     if fmt == _SPARSE_FORMAT:
         return SparseRadianceVolume.load(path, device)
-    if fmt == "pano_nerf_amd.radiance_volume":
+    if fmt == _DENSE_FORMAT:
         return RadianceVolume.load(path, device)
     raise ValueError(f"{path}: not a radiance volume of either kind (format {fmt!r})")
 
 
 def _load_device(device):
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (device=%s); there is no CPU fallback" % dev)
+    _device_only(dev, "a volume cannot be loaded")
     return dev
 
 
 # ----------------------------------------------------------------------------------------------------------- volume
-class RadianceVolume:
+def _occupancy(res, C, data, dev):
+    """uint8 [nbx, nby, nbz]: pn_volume_occupancy of channel 0 of a packed [nx, ny, nz, C] device tensor"""
+    occ = torch.empty(_brick_counts(res), dtype=torch.uint8, device=dev)
+    _lib.call("pn_volume_occupancy", *res, C, data.data_ptr(), occ.data_ptr(), _lib.stream(dev))
+    return occ
+
+
+class RadianceVolume(_Header):
     """One packed fp32 tensor data [nx, ny, nz, C] on the vertex grid of geometry.density_grid (bounds are the inclusive
     corner vertices, vertex (i ny + j) nz + k): channel 0 sigma, then K = (sh_degree + 1)^2 RGB coefficient triples in
     lighting's SH order, then the attribute channels.  `attributes`: names (width 3) or (name, width) pairs, e.g.
     (("albedo", 3), ("normal", 3)).  The tensor is held, not copied: edit it in place and call refresh()."""
 
     def __init__(self, data, bounds, sh_degree, attributes=()):
-        K = _sh_count(sh_degree)
-        self.sh_degree = int(sh_degree)
-        self._attrs = _attributes(attributes)
         if not isinstance(data, torch.Tensor) or data.dim() != 4:
             raise ValueError(f"data must be an [nx, ny, nz, C] tensor; got {getattr(data, 'shape', type(data))}")
-        if data.device.type != "cuda":
-            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the data is on %s); there is no CPU "
-                               "fallback" % data.device)
-        C = 1 + 3 * K + sum(w for _, w in self._attrs)
-        if data.shape[3] != C:
+        _device_only(data.device, "the data is")
+        super().__init__(bounds, tuple(int(s) for s in data.shape[:3]), sh_degree, attributes)
+        if data.shape[3] != self.channels:
             raise ValueError(f"data has {data.shape[3]} channels; sh_degree {sh_degree} with attributes {self._attrs} "
-                             f"takes 1 + 3 K + E = {C}")
+                             f"takes 1 + 3 K + E = {self.channels}")
         if data.dtype != torch.float32 or not data.is_contiguous():
             raise ValueError("data must be a contiguous fp32 tensor (it is held and read in place)")
-        self.resolution = _resolution(tuple(int(s) for s in data.shape[:3]))
-        self.bounds = _bounds(bounds)
-        self.lo, self.step = _grid(self.bounds, self.resolution)
         self.data = data.detach()
         self.device = data.device
-        self.attribute_names = tuple(n for n, _ in self._attrs)
         self._occ = None
-
-    @property
-    def channels(self):
-        return int(self.data.shape[3])
 
     @property
     def sigma(self):
@@ -291,7 +304,7 @@ class RadianceVolume:
 
     @property
     def attributes(self):
-        out, first = {}, 1 + 3 * _sh_count(self.sh_degree)
+        out, first = {}, _channels(self.sh_degree)
         for name, w in self._attrs:
             out[name] = self.data[..., first:first + w]
             first += w
@@ -306,12 +319,8 @@ class RadianceVolume:
 
     def refresh(self):
         """Rebuild the occupancy from data (one launch of pn_volume_occupancy); call it after editing data.  Returns self."""
-        nb = tuple((n + BRICK - 2) // BRICK for n in self.resolution)
         with torch.no_grad(), torch.cuda.device(self.device):
-            occ = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            _lib.call("pn_volume_occupancy", *self.resolution, self.channels, self.data.data_ptr(), occ.data_ptr(),
-                      _lib.stream(self.device))
-        self._occ = occ
+            self._occ = _occupancy(self.resolution, self.channels, self.data, self.device)
         return self
 
     def save(self, path):
@@ -346,12 +355,12 @@ def _brick_table(occ):
 
 
 def _channel_name(ch, sh_degree, attrs):
-    K = _sh_count(sh_degree)
     if ch == 0:
         return "sigma"
-    if ch < 1 + 3 * K:
+    first = _channels(sh_degree)  # the first attribute channel
+    if ch < first:
         return f"coeff[{(ch - 1) // 3}][{'rgb'[(ch - 1) % 3]}]"
-    ch -= 1 + 3 * K
+    ch -= first
     for name, w in attrs:
         if ch < w:
             return f"{name}[{ch}]"
@@ -369,7 +378,7 @@ def _pack(res, C, table, B, dtype, dev, data=None, rows=None, vertex_row=None):
     return pool
 
 
-class SparseRadianceVolume:
+class SparseRadianceVolume(_Header):
     """The radiance volume with its unoccupied bricks left out: table int32 [nbx, nby, nbz] (a brick's slot in the pool,
     or -1; slots ascend with the brick index) and pool [B, 9, 9, 9, C] in fp32 or fp16, a present brick's 9^3 vertices
     with C fastest (include/panonerf_hip.h, "sparse radiance volume").  Made by RadianceVolume.to_sparse / from_dense or
@@ -377,21 +386,15 @@ class SparseRadianceVolume:
     faces are stored once per present brick, so this is not a volume to edit in place: go through to_dense()."""
 
     def __init__(self, table, pool, bounds, resolution, sh_degree, attributes=()):
-        K = _sh_count(sh_degree)
-        self.sh_degree = int(sh_degree)
-        self._attrs = _attributes(attributes)
-        self.resolution = _resolution(resolution)
+        super().__init__(bounds, resolution, sh_degree, attributes)
         for t, what in ((table, "table"), (pool, "pool")):
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{what} must be a tensor; got {type(t).__name__}")
-            if t.device.type != "cuda":
-                raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the %s is on %s); there is no CPU "
-                                   "fallback" % (what, t.device))
-        nb = _brick_counts(self.resolution)
+            _device_only(t.device, f"the {what} is")
+        nb, C = _brick_counts(self.resolution), self.channels
         if table.dtype != torch.int32 or tuple(table.shape) != nb or not table.is_contiguous():
             raise ValueError(f"table must be a contiguous int32 {nb} tensor for resolution {self.resolution}; got "
                              f"{table.dtype} {tuple(table.shape)}")
-        C = 1 + 3 * K + sum(w for _, w in self._attrs)
         if pool.dim() != 5 or tuple(pool.shape[1:]) != (BRICK + 1,) * 3 + (C,):
             raise ValueError(f"pool must be [B, 9, 9, 9, C] with 1 + 3 K + E = {C} channels for sh_degree {sh_degree} and "
                              f"attributes {self._attrs}; got {tuple(pool.shape)}")
@@ -407,11 +410,8 @@ class SparseRadianceVolume:
         want = torch.where(present, torch.cumsum(present.to(torch.int64), 0) - 1, -1)
         if not bool(((flat == want).all()) & (present.sum() == B)):
             raise ValueError(f"table must hold -1 or the slots 0 .. {B - 1} of the pool in ascending brick index")
-        self.bounds = _bounds(bounds)
-        self.lo, self.step = _grid(self.bounds, self.resolution)
         self.table, self.pool = table.detach(), pool.detach()
         self.device = table.device
-        self.attribute_names = tuple(n for n, _ in self._attrs)
 
     @property
     def dtype(self):
@@ -420,10 +420,6 @@ class SparseRadianceVolume:
     @property
     def bricks(self):
         return int(self.pool.shape[0])
-
-    @property
-    def channels(self):
-        return int(self.pool.shape[4])
 
     @property
     def occupancy(self):
@@ -532,10 +528,9 @@ def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_m
     dirs32 = np.ascontiguousarray(dirs, dtype=np.float32)
     P = np.linalg.pinv(sh_basis(dirs32.astype(np.float64), sh_degree))  # [K, D]
     dev = _model_device(model)
-    E = 3 * len(attributes)
     N = res[0] * res[1] * res[2]
-    C = 1 + 3 * K + E
     attrs = tuple((a, 3) for a in attributes)
+    C = _channels(sh_degree, attrs)
 
     def fill(dst, sel, idx):
         """the survivors' channels into dst[sel]: the dense tensor at rows idx, or the compact rows themselves"""
@@ -568,10 +563,8 @@ def bake_volume(model, bounds, resolution, sh_degree=1, directions=None, sigma_m
         idx = torch.nonzero(keep).reshape(-1)
         M = int(idx.shape[0])
         pruned = torch.where(keep, sigma, 0.0).contiguous()
-        occ = torch.empty(_brick_counts(res), dtype=torch.uint8, device=dev)
-        _lib.call("pn_volume_occupancy", *res, 1, pruned.data_ptr(), occ.data_ptr(), _lib.stream(dev))
-        table, B = _brick_table(occ)
-        del pruned, keep, occ
+        table, B = _brick_table(_occupancy(res, 1, pruned, dev))
+        del pruned, keep
         rows = torch.zeros(M, C, dtype=torch.float32, device=dev)
         if M:
             fill(rows, slice(None), idx)
@@ -595,9 +588,7 @@ def default_step(vol):
 
 def _rows(t, R, width, what, dev):
     if isinstance(t, torch.Tensor):
-        if t.device.type != "cuda":
-            raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (%s is on %s); there is no CPU fallback"
-                               % (what, t.device))
+        _device_only(t.device, f"{what} is")
         if t.device != dev:
             raise ValueError(f"{what} is on {t.device} but the volume on {dev}")
         if t.numel() != R * width:
@@ -606,6 +597,21 @@ def _rows(t, R, width, what, dev):
     if width != 1:
         raise ValueError(f"{what} must be an [R, {width}] tensor; got {type(t).__name__}")
     return torch.full((R, 1), float(t), dtype=torch.float32, device=dev)
+
+
+def _ray_rows(vol, origins, directions, near, far, step, t_min):
+    """(R, origins [R, 3], directions [R, 3], near [R, 1], far [R, 1], step, t_min) as every marcher takes them: fp32 rows
+    on the volume's device and the two march parameters as the fp32 values the kernel sees"""
+    for t, what in ((origins, "origins"), (directions, "directions")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
+    step = default_step(vol) if step is None else float(np.float32(step))
+    t_min = float(np.float32(t_min))
+    if not (step > 0.0 and math.isfinite(step)) or not (t_min >= 0.0 and math.isfinite(t_min)):
+        raise ValueError(f"step must be positive and finite and t_min >= 0; got {step!r}, {t_min!r}")
+    dev, R = vol.device, int(origins.shape[0])
+    return (R, _rows(origins, R, 3, "origins", dev), _rows(directions, R, 3, "directions", dev), _rows(near, R, 1, "near", dev),
+            _rows(far, R, 1, "far", dev), step, t_min)
 
 
 def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=True, outputs=("rgb", "depth", "acc")):
@@ -626,19 +632,9 @@ def march_rays(vol, origins, directions, near, far, step=None, t_min=1e-3, skip=
     bad = [o for o in outputs if o not in _CORE + vol.attribute_names + (_TAPS,)]
     if bad or not outputs:
         raise ValueError(f"outputs must be a non-empty subset of {_CORE + vol.attribute_names}; got {outputs!r}")
-    for t, what in ((origins, "origins"), (directions, "directions")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{what} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
     dev = vol.device
-    R = int(origins.shape[0])
-    step = default_step(vol) if step is None else float(np.float32(step))
-    t_min = float(np.float32(t_min))
-    if not (step > 0.0 and math.isfinite(step)) or not (t_min >= 0.0 and math.isfinite(t_min)):
-        raise ValueError(f"step must be positive and finite and t_min >= 0; got {step!r}, {t_min!r}")
-    o = _rows(origins, R, 3, "origins", dev)
-    d = _rows(directions, R, 3, "directions", dev)
-    tn, tf = _rows(near, R, 1, "near", dev), _rows(far, R, 1, "far", dev)
-    E = vol.channels - 1 - 3 * _sh_count(vol.sh_degree)
+    R, o, d, tn, tf, step, t_min = _ray_rows(vol, origins, directions, near, far, step, t_min)
+    E = vol.channels - _channels(vol.sh_degree)
     want_attr = any(k in vol.attribute_names for k in outputs)
     with torch.no_grad(), torch.cuda.device(dev):
         new = lambda w: torch.empty(R, w, dtype=torch.float32, device=dev)
@@ -716,9 +712,7 @@ def volume_probes(vol, positions, height=32, width=64, near=0.0, far=10.0, step=
     lighting.light_probes (an identity-rotation panorama camera at the position), all probes in one march_rays call.
     lighting.sh_project, irradiance, ibl.bake_ibl and emitters take the result as they take light_probes'."""
     P = views._probe_positions(positions)
-    if positions.device.type != "cuda":
-        raise RuntimeError("pano_nerf_amd.volume runs on a HIP device only (the positions are on %s); there is no CPU "
-                           "fallback" % positions.device)
+    _device_only(positions.device, "the positions are")
     H, W = int(height), int(width)
     if H < 2 or W < 2:
         raise ValueError(f"a probe needs height and width >= 2; got {height} x {width}")
@@ -753,15 +747,7 @@ def _dense(vol, what):
                          "volume (to_dense()), then to_sparse()")
     if not isinstance(vol, RadianceVolume):
         raise ValueError(f"{what} takes a RadianceVolume; got {type(vol).__name__}")
-    return 1 + 3 * _sh_count(vol.sh_degree)
-
-
-def _march_params(vol, step, t_min):
-    step = default_step(vol) if step is None else float(np.float32(step))
-    t_min = float(np.float32(t_min))
-    if not (step > 0.0 and math.isfinite(step)) or not (t_min >= 0.0 and math.isfinite(t_min)):
-        raise ValueError(f"step must be positive and finite and t_min >= 0; got {step!r}, {t_min!r}")
-    return step, t_min
+    return _channels(vol.sh_degree)
 
 
 def march_rays_grad(vol, origins, directions, near, far, grad_rgb=None, grad_acc=None, step=None, t_min=1e-3, skip=True,
@@ -775,15 +761,8 @@ def march_rays_grad(vol, origins, directions, near, far, grad_rgb=None, grad_acc
     (2^23 at the default).  The rays, step, t_min and skip are march_rays'.  finish_grad turns the sums into fp32."""
     Cg = _dense(vol, "march_rays_grad")
     quantum = _quantum(quantum)
-    for t, what in ((origins, "origins"), (directions, "directions")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{what} must be an [R, 3] tensor; got {getattr(t, 'shape', type(t))}")
     dev = vol.device
-    R = int(origins.shape[0])
-    step, t_min = _march_params(vol, step, t_min)
-    o = _rows(origins, R, 3, "origins", dev)
-    d = _rows(directions, R, 3, "directions", dev)
-    tn, tf = _rows(near, R, 1, "near", dev), _rows(far, R, 1, "far", dev)
+    R, o, d, tn, tf, step, t_min = _ray_rows(vol, origins, directions, near, far, step, t_min)
     g_rgb = None if grad_rgb is None else _rows(grad_rgb, R, 3, "grad_rgb", dev)
     g_acc = None if grad_acc is None else _rows(grad_acc, R, 1, "grad_acc", dev)
     N = vol.resolution[0] * vol.resolution[1] * vol.resolution[2]
